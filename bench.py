@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """Headline benchmark: denoise train steps/s of the cc12m_64x64 U-Net (bf16, batch 64 per GPU).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path over one synthetic batch: Diffusion.get_loss (noising +
 U-Net forward + loss) -> backward -> gradient all-reduce (N > 1) -> clip -> AdamW -> EMA, i.e. the
 reference's ``trainer.train_batch`` (trainer.py:13-96).  Inputs are resident in HBM before the
-timed region.  Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+timed region.  A plain run sets up, warms up, times exactly K steps and prints ONE JSON line from rank 0;
+``--dump-outputs DIR`` also writes what the last timed step computed (the return value of train_batch, a seeded
+sample of the updated parameters and of the EMA copy) as DIR/<name>.npy, float32 / float64.
+``--full`` adds the secondary measurements below to the line (each still switched off by its ``--no-...`` option):
   roofline      the GEMM-class kernel with the largest total time of a step, measured live with HIP events on the
                 launch stream; ``gemm_weighted`` = FLOP-weighted figure over every GEMM-class launch;
                 ``hbm_kernels`` = the streaming kernels as algorithmic GB/s against the 8 TB/s HBM peak
@@ -190,10 +193,11 @@ def make_step(pipe, bf16, world, plain=False, bucket_mb=256.0, wire="auto", seri
     if serial_wgrad:
         os.environ["MDM_HIP_SERIAL_WGRAD"] = "1"
 
-    def step(sample):
+    def step(sample):   # -> train_batch's return value: (loss, losses, times, x_t, means, targets)
         return trainer.train_batch(pipe, sample, opt, sched, None, args, grad_scaler=scaler, accumulate_gradient=False,
-                                   num_grad_accumulations=1, ema_model=ema, loss_factor=1.0)[0]
+                                   num_grad_accumulations=1, ema_model=ema, loss_factor=1.0)
 
+    step.ema = ema   # (bench.py --dump-outputs reads the EMA copy)
     return step, opt
 
 
@@ -204,6 +208,7 @@ def _binary_provenance():
 
 
 def timed_steps(step, sample, warmup, steps, sync):
+    """-> (seconds of the `steps` timed steps, the last timed step's return value)"""
     for _ in range(warmup):
         step(sample)
     sync()
@@ -221,7 +226,9 @@ def timed_steps(step, sample, warmup, steps, sync):
         if evs:
             evs[0].record()
         for i in range(steps):
-            step(sample)
+            res = step(sample)
+            if i + 1 < steps:
+                res = None   # only the last step's results outlive the step, as when its return value was dropped
             if evs:
                 evs[i + 1].record()
         sync()
@@ -230,7 +237,41 @@ def timed_steps(step, sample, warmup, steps, sync):
         gc.enable()   # (an exception in a timed step -- an OOM caught by an outer leg -- must not leave the collector off)
     if evs:
         print("per-step ms: " + " ".join("%.1f" % evs[i].elapsed_time(evs[i + 1]) for i in range(steps)), file=sys.stderr)
-    return dt
+    return dt, res
+
+
+DUMP_SAMPLE = 1 << 20   # elements kept of a larger array (a fixed, seeded sample): the dump stays well under 64 MB
+
+
+def _sampled(t, seed):
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed))
+        flat = flat[idx.to(flat.device)]
+    return flat
+
+
+def dump_outputs(out_dir, res, params, ema):
+    """What the timed path computed in its last step, as <out_dir>/<name>.npy: train_batch's return value (loss, per-sample
+    losses, diffusion times, noised input x_t, the model's prediction `means`, targets; a list-valued entry of the nested
+    model gives one file per resolution), and seeded samples of the updated parameters and of their EMA copy."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([res[0]], dtype=np.float64)}
+    for name, v in zip(("losses", "times", "x_t", "means", "targets"), res[1:]):
+        vs = v if isinstance(v, (list, tuple)) else [v]
+        for i, t in enumerate(vs):
+            key = name if len(vs) == 1 else "%s_%d" % (name, i)
+            arrays[key] = _sampled(t, seed=len(arrays)).float().cpu().numpy()
+    with torch.no_grad():
+        arrays["params_sample"] = _sampled(torch.cat([p.reshape(-1) for p in params]), seed=1).float().cpu().numpy()
+        arrays["ema_params_sample"] = _sampled(torch.cat([p.reshape(-1) for p in ema.module.parameters()]), seed=1).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def main():
@@ -256,7 +297,17 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="N = 1 only: run the gradient buckets through RCCL anyway (world-of-one process group)")
     ap.add_argument("--sample-batch", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (roofline, sampling, nested256, reference_loop, nested1024_sampling, "
+                         "cpu_baseline); a plain run times the headline train step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # the headline figure needs none of the secondary legs
+        args.no_roofline = args.no_sampling = args.no_nested = args.no_reference_loop = args.no_nested1024 = True
+        args.no_cpu_baseline = True
 
     from mdm_hip import distributed as mdist
     from mdm_hip import ops
@@ -303,8 +354,11 @@ def main():
     settle = int(os.environ.get("BENCH_SETTLE_STEPS", "15"))
     for _ in range(settle):
         step(sample)
-    dt = timed_steps(step, sample, args.warmup, args.steps, sync)
+    dt, last = timed_steps(step, sample, args.warmup, args.steps, sync)
     assert getattr(opt, "_mdm_fused", False) not in (None, False), getattr(opt, "_mdm_fused_reason", "the fused path did not engage")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, [p for g in opt.param_groups for p in g["params"]], step.ema)
+    last = None
     # what went over the wire, and when: per bucket of the LAST step (bucket, MB, issued at, compute stream free at; ms from
     # the first bucket's issue) -- how much of the gradient exchange hid behind backward on this node
     comm_wire, comm_timeline, comm_window = "fp32", None, None
@@ -425,7 +479,7 @@ def main():
             nstep, nopt = make_step(npipe, True, world, bucket_mb=args.bucket_mb, wire=wire)
             nsample = synthetic_batch(16, nside, device, seed=99 + rank)
             nsteps = max(3, min(args.steps, 10))
-            ndt = timed_steps(nstep, nsample, 4, nsteps, sync)   # 4 warm-up steps: the allocator re-grows after empty_cache()
+            ndt, _ = timed_steps(nstep, nsample, 4, nsteps, sync)   # 4 warm-up steps: the allocator re-grows after empty_cache()
             if world > 1:
                 tt = torch.tensor([ndt], device=device)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -454,7 +508,7 @@ def main():
             rstep, ropt = make_step(rpipe, True, world, plain=True, torch_ddp=world > 1)
             rsample = synthetic_batch(batch, rside, device, seed=1234 + rank)
             rsteps = max(2, min(args.steps, 4))
-            rdt = timed_steps(rstep, rsample, 1, rsteps, sync)
+            rdt, _ = timed_steps(rstep, rsample, 1, rsteps, sync)
             assert getattr(ropt, "_mdm_fused", None) is False
             ref_loop = {"ms_per_step": round(rdt / rsteps * 1e3, 3), "steps_per_s_whole_job": round(world * rsteps / rdt, 4), "steps": rsteps,
                         "what": "mdm_hip.trainer.train_batch, plain path: HIP denoiser kernels, but autograd gradient accumulation, "

@@ -316,7 +316,8 @@ def run_train_batch(trainer_mod, pipe, ema_cls, fp16=False, n_micro=6, accumulat
 
 def trainer_golden():
     """the REAL ``ml_mdm.trainer.train_batch`` + ``ModelEma`` + ``Diffusion`` around tests/stub_models.StubUNet, fp32 on CPU:
-    6 micro-steps with 2-step gradient accumulation (3 optimizer steps), and the same with a NaN batch at micro-step 2"""
+    6 micro-steps with 2-step gradient accumulation (3 optimizer steps), the same with a NaN batch at micro-step 2, and
+    9 micro-steps with 3-step accumulation ("acc3": what tests/test_trainer_host.py compares with when the reference is absent)"""
     import stub_models as SM
 
     R = ref_import.load()
@@ -328,6 +329,9 @@ def trainer_golden():
         pipe = D.Diffusion(SM.StubUNet(), D.DiffusionConfig(sampler_config=scfg, use_vdm_loss_weights=False))
         blob[tag] = run_train_batch(R.trainer, pipe, R.model_ema.ModelEma, nan_at=nan_at)
         print(tag, blob[tag])
+    pipe = D.Diffusion(SM.StubUNet(), D.DiffusionConfig(sampler_config=scfg, use_vdm_loss_weights=False))
+    blob["acc3"] = run_train_batch(R.trainer, pipe, R.model_ema.ModelEma, n_micro=9, accumulations=3)
+    print("acc3", blob["acc3"])
     path = os.path.join(ROOT, "tests", "golden", "train_batch.pt")
     torch.save(blob, path)
     print("wrote", path)

@@ -31,7 +31,7 @@ def _env(**kw):
 
 
 def test_one_rank_line_has_the_contract_keys():
-    d = _line([sys.executable, "bench.py", "--gpus", "1"] + QUICK, _env())
+    d = _line([sys.executable, "bench.py", "--gpus", "1", "--full"] + QUICK, _env())
     assert KEYS <= set(d), sorted(KEYS - set(d))
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "bf16" and "synthetic" in d["data"]
@@ -40,7 +40,7 @@ def test_one_rank_line_has_the_contract_keys():
     r = d["roofline"]
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(r) and r["bound"] in ("mfma", "hbm")
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
-    assert "cpu_baseline" not in d          # --no-cpu-baseline (the default run carries it: profiles/r06_bench_unet64_b64_line.json)
+    assert "cpu_baseline" not in d          # --no-cpu-baseline (a --full run carries it: profiles/r06_bench_unet64_b64_line.json)
     assert len(d["binary"]["sha256"]) == 64
 
 
@@ -52,3 +52,29 @@ def test_two_ranks_on_one_gpu_over_rccl():
     comm = d["config"]["comm"]
     assert comm["backend"] == "nccl" and comm["world_size"] == 2 and len(comm["bucket_timeline_ms"]) >= 1
     assert abs(d["value"] * d["ms_per_step"] / 1e3 - 2.0) < 2e-3                           # whole job: 2 x steps/s
+
+
+def test_plain_run_times_only_the_step_and_dumps_its_outputs(tmp_path):
+    """without --full the line carries the headline figure alone; --dump-outputs writes the last timed step's results, and
+    a second run with the same arguments starts from the same inputs"""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _line([sys.executable, "bench.py", "--gpus", "1", "--workload", "mini", "--steps", "3", "--warmup", "1",
+                   "--dump-outputs", str(out)], _env())
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-3
+        for leg in ("roofline", "sampling", "nested256", "reference_loop", "nested1024_sampling"):
+            assert d[leg] is None, leg
+        assert "cpu_baseline" not in d
+        files = {p.name: np.load(p) for p in out.glob("*.npy")}
+        assert {"loss.npy", "losses.npy", "times.npy", "x_t.npy", "means.npy", "targets.npy", "params_sample.npy",
+                "ema_params_sample.npy"} <= set(files)
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64 << 20
+        runs.append(files)
+    assert np.array_equal(runs[0]["times.npy"], runs[1]["times.npy"])
+    for name in ("x_t.npy", "targets.npy"):
+        assert np.allclose(runs[0][name], runs[1][name], rtol=0, atol=1e-6), name

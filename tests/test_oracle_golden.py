@@ -70,13 +70,21 @@ def test_oracle_matches_full_size_golden(name):
             assert abs(probe - gold["grad_probe"][k]) <= 4e-4 * max(n, floor), k
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("name", ["mini_unet", "mini_nested", "mini_nested2"] + PC.EXTRA_CASES)
 def test_oracle_matches_live_reference(name):
+    """oracle forward == the reference's forward on the case's parameters and inputs, the reference executed live; where
+    the reference tree is absent, == the outputs it produced for tests/golden/<case>.pt"""
     import dataclasses
 
     import ref_import
 
+    if not ref_import.available():
+        yr = torch.load(os.path.join(GOLD, name + ".pt"), weights_only=False)["outputs"]
+        yo, _ = PC.oracle_run(name, with_grad=False)
+        assert len(yo) == len(yr)
+        for a, b in zip(yo, yr):
+            assert O.rel_l2(a, b) < 1e-6
+        return
     R = ref_import.load()
 
     def conv(cfg):
