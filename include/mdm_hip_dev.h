@@ -13,19 +13,13 @@ int mdm_conv_fwd_tile(int M, int Cout, int dtype);
 /* host-only: 128 or 256 (square output tile edge) mdm_conv_wgrad will use */
 int mdm_conv_wgrad_tile(int M, int Cout, int K, int dtype);
 
-/* development knobs of the GEMM kernels (all 0 / default in the product; host-side state of the calling process, never
- * read from the environment inside an entry point).  Experiments recorded in DESIGN.md / profiles/.
- *   0  conv_gemm_bl_kernel: bit 0 = its LDS-DMA fetches nothing (timing only: what the k-loop costs without memory)
- *   1  epilogues skip their global stores (what the store phase costs)
- *   2  force the forward tile of conv_gemm_bl_kernel (128128 / 256192 / 256256)
- *   3, 4  unused (were the switches of conv_gemm_x_kernel, removed in round 6: profiles/r04_gemm_x8_probe.txt is its record)
- *   6  tile-fill percentage below which a forward GEMM may split its reduction (default 80; 25 = the sampling-only rule)
- *   7  1 = the narrow 3x3 convolutions of the nested models go back to the implicit-GEMM kernel (no conv3x3_direct_kernel)
- *   8  1 = the narrow weight gradients (64 output channels, >= 262144 pixels) go back to the split GEMM (no wgrad_direct_kernel)
- *   9  forward split-K: minimum k-tiles per range (default 6);  10: minimum k-tiles of serial walk a split must save (default 16)
- *  11  1 = no 4-stage instantiations of conv_gemm_bl_kernel<128, 128> for under-filled grids (small-batch sampling)
- *  12  forward split-K: blocks per CU a split aims for (0 = by problem size: 1 for M <= 2048, else 2)
- *  13  1 = mdm_conv_wgrad_reduce launches nothing (timing-only ablation: what the slab-reduce launches cost a step; WRONG gradients) */
+/* development knobs of the GEMM kernels (0 in the product; host-side state of the calling process, never read from the
+ * environment inside an entry point).  Any other index is an argument error.
+ *   0  1 = the LDS-DMA of conv_gemm_bl_kernel fetches nothing (timing only: what the k-loop costs without memory).  Its
+ *      uniform branch also keeps the compiler's register allocation of the 3x3 instantiations (see conv_args.hpp)
+ *   2  force the forward tile of conv_gemm_bl_kernel (128128 / 256192 / 256256; tools/kbench.py KB_TILE)
+ *   8  1 = the narrow weight gradients (64 output channels, >= 262144 pixels) go back to the split GEMM (no wgrad_direct_kernel:
+ *      the reference of tests/test_ops_gpu.py's direct-kernel test) */
 int mdm_dev_set_knob(int idx, int value);
 /* attention backward kernel choice: 0 = by shape, 1 = always the split (dQ + dK/dV) kernels on 16x16x32 MFMAs, 2 = the
  * one-block-per-head kernel whenever the shape allows (tests), 3 = as 2 but the 16x16x32 one, 4 = the streaming kernels on

@@ -127,37 +127,6 @@ struct RowSrc {
 // LDS returns in order, so the waits hipcc inserts are counted (lgkmcnt(n)), not drains.
 #define MDM_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-// Issue priority of a wave for one tile step.  The two waves of a SIMD (waves w and w + 4 of a block) are arbitrated by
-// priority, then age: left alone, the second-dispatched half runs its tile loops 40 % longer (measured: 17.5 K against 12.3 K
-// cycles for the nine tiles of phase Q) and every barrier waits for it; a static s_setprio for that half only swaps the roles
-// (12.1 K / 17.2 K).  Alternating the priority tile by tile lets the pair take turns, so both halves finish together.
-#ifndef MDM_ATT_SR
-#define MDM_ATT_SR 64
-#endif
-#ifndef MDM_ATT_PRIO
-#define MDM_ATT_PRIO 0
-#endif
-// timing-only ablations of the streaming kernels (development: tools/build_variant.sh -DMDM_ATT_ABL=<bits>; results are wrong):
-// 1 no v_exp, 2 no transpose reads, 4 no barrier in the stage loops, 8 no fetch / commit in the stage loops, 16 no S / dP
-// products, 32 no dQ / dV / dK products
-#ifndef MDM_ATT_ABL
-#define MDM_ATT_ABL 0
-#endif
-
-#define MDM_EXP2(x) ((MDM_ATT_ABL & 1) ? (x) : __builtin_amdgcn_exp2f(x))
-__device__ __forceinline__ void prio_flip(int step_plus_half) {
-#if MDM_ATT_PRIO == 2
-  if (__builtin_amdgcn_readfirstlane(step_plus_half) & 1) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);
-#endif
-}
-#ifndef MDM_QPF96
-#define MDM_QPF96 3
-#endif
-#ifndef MDM_KPF96
-#define MDM_KPF96 3
-#endif
-
 // A operands (K, V rows: phase Q; Q, dO rows: phase K) of the S / dP products of one tile, read one step ahead
 template <int D, int PF> struct Ops32 { bf16x8 x[PF], y[PF]; };
 template <int D, int PF>
@@ -173,7 +142,7 @@ __device__ __forceinline__ void load_ops32(Ops32<D, PF>& o, const char* Xt, cons
 // operand fragments (read during the previous step); Kn / Vn: the NEXT tile's rows (any valid tile if there is none); qf /
 // gf: the wave's Q / dO operand fragments; nl = -lse / scale, nd = -delta of the lane's query; `live`: bit k = key k of the
 // tile takes part (wave-uniform); dq: dQ^T accumulators (register r of block blk <-> channel 32 blk + 8 (r >> 2) + 4 hi + (r & 3)).
-template <int D> struct QPf { static constexpr int value = D <= 64 ? A32<D>::KS : MDM_QPF96; };
+template <int D> struct QPf { static constexpr int value = D <= 64 ? A32<D>::KS : 3; };
 template <int D>
 __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char* Kt, const char* Vt, const char* Kn, const char* Vn,
                                          const bf16x8 (&qf)[A32<D>::KS], const bf16x8 (&gf)[A32<D>::KS],
@@ -193,13 +162,11 @@ __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char*
   f32x16 sc, dp;
 #pragma unroll
   for (int s = 0; s < PF; ++s) {
-    if (MDM_ATT_ABL & 16) { sc = zero; dp = zero; continue; }
     sc = mma32(o.x[s], qf[s], s == 0 ? zero : sc);
     dp = mma32(o.y[s], gf[s], s == 0 ? zero : dp);
   }
 #pragma unroll
   for (int s = PF; s < G::KS; ++s) {
-    if (MDM_ATT_ABL & 16) continue;
     sc = mma32(xr[s - PF], qf[s], sc);
     dp = mma32(yr[s - PF], gf[s], dp);
   }
@@ -209,7 +176,7 @@ __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char*
   for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
     for (int blk = 0; blk < G::NB; ++blk)
-      tk[s2][blk] = (MDM_ATT_ABL & 2) ? o.x[blk] : lds_tr_pair(Kt + s2 * 16 * G::PITCH + fo.tr[0][blk], Kt + s2 * 16 * G::PITCH + fo.tr[1][blk]);
+      tk[s2][blk] = lds_tr_pair(Kt + s2 * 16 * G::PITCH + fo.tr[0][blk], Kt + s2 * 16 * G::PITCH + fo.tr[1][blk]);
   MDM_FENCE();
   const float nl2 = nl * c2;
   if (live == 0xffffffffu) {
@@ -220,7 +187,7 @@ __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char*
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
       const f32x2 e = f32x2{sc[r], sc[r + 1]} * c2v + nlv;
-      const f32x2 pr = {MDM_EXP2(e[0]), MDM_EXP2(e[1])};
+      const f32x2 pr = {__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])};
       const f32x2 ds = pr * (f32x2{dp[r], dp[r + 1]} + ndv);
       sc[r] = ds[0]; sc[r + 1] = ds[1];
     }
@@ -228,7 +195,7 @@ __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char*
     const unsigned lv = live >> (4 * hi);    // this lane's registers hold keys (r & 3) + 8 (r >> 2) + 4 hi
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float pr = ((lv >> ((r & 3) + 8 * (r >> 2))) & 1u) ? MDM_EXP2(fmaf(sc[r], c2, nl2)) : 0.f;
+      const float pr = ((lv >> ((r & 3) + 8 * (r >> 2))) & 1u) ? __builtin_amdgcn_exp2f(fmaf(sc[r], c2, nl2)) : 0.f;
       sc[r] = pr * (dp[r] + nd);
     }
   }
@@ -237,9 +204,9 @@ __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char*
   load_ops32<D, PF>(o, Kn, Vn, fo);
   MDM_FENCE();
 #pragma unroll
-  for (int blk = 0; blk < G::NB; ++blk) if (!(MDM_ATT_ABL & 32)) dq[blk] = mma32(tk[0][blk], ds0, dq[blk]); else dq[blk][0] += (float)ds0[0] + (float)tk[0][blk][0];
+  for (int blk = 0; blk < G::NB; ++blk) dq[blk] = mma32(tk[0][blk], ds0, dq[blk]);
 #pragma unroll
-  for (int blk = 0; blk < G::NB; ++blk) if (!(MDM_ATT_ABL & 32)) dq[blk] = mma32(tk[1][blk], ds1, dq[blk]); else dq[blk][1] += (float)ds1[0] + (float)tk[1][blk][0];
+  for (int blk = 0; blk < G::NB; ++blk) dq[blk] = mma32(tk[1][blk], ds1, dq[blk]);
 }
 
 // One 32-query tile for a wave that owns 32 keys (lane <-> key).  Qt / Gt: the tile's rows of Q / dO in swizzled images; o:
@@ -247,7 +214,7 @@ __device__ __forceinline__ void q_step32(Ops32<D, QPf<D>::value>& o, const char*
 // tile if none); nl / nd: -lse / scale and -delta of the tile's 32 queries (LDS) -- they ARE the initial accumulators;
 // kf / vf: the wave's K / V operand fragments; dk / dv: dK^T / dV^T accumulators (register <-> channel as in q_step32).
 // PF: how many of the KS reduction steps are read one tile ahead (registers: all of them at d = 64, half at d = 96).
-template <int D> struct KPf { static constexpr int value = D <= 64 ? A32<D>::KS : MDM_KPF96; };
+template <int D> struct KPf { static constexpr int value = D <= 64 ? A32<D>::KS : 3; };
 template <int D>
 __device__ __forceinline__ void k_step32(Ops32<D, KPf<D>::value>& o, const char* Qt, const char* Gt, const char* Qn, const char* Gn,
                                          const float* nl, const float* nd,
@@ -272,13 +239,11 @@ __device__ __forceinline__ void k_step32(Ops32<D, KPf<D>::value>& o, const char*
   }
 #pragma unroll
   for (int s = 0; s < PF; ++s) {
-    if (MDM_ATT_ABL & 16) continue;
     sc = mma32(o.x[s], kf[s], sc);
     dp = mma32(o.y[s], vf[s], dp);
   }
 #pragma unroll
   for (int s = PF; s < G::KS; ++s) {
-    if (MDM_ATT_ABL & 16) continue;
     sc = mma32(xr[s - PF], kf[s], sc);
     dp = mma32(yr[s - PF], vf[s], dp);
   }
@@ -288,14 +253,14 @@ __device__ __forceinline__ void k_step32(Ops32<D, KPf<D>::value>& o, const char*
   for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
     for (int blk = 0; blk < G::NB; ++blk)
-      tg[s2][blk] = (MDM_ATT_ABL & 2) ? o.y[blk] : lds_tr_pair(Gt + s2 * 16 * G::PITCH + fo.tr[0][blk], Gt + s2 * 16 * G::PITCH + fo.tr[1][blk]);
+      tg[s2][blk] = lds_tr_pair(Gt + s2 * 16 * G::PITCH + fo.tr[0][blk], Gt + s2 * 16 * G::PITCH + fo.tr[1][blk]);
   MDM_FENCE();
   if (__builtin_amdgcn_readfirstlane(__all(key_live))) {   // (the common case: no select per score; packed as in q_step32)
     const f32x2 c2v = {c2, c2};
 #pragma unroll
     for (int r = 0; r < 16; r += 2) {
       const f32x2 e = f32x2{sc[r], sc[r + 1]} * c2v;
-      const f32x2 pr = {MDM_EXP2(e[0]), MDM_EXP2(e[1])};
+      const f32x2 pr = {__builtin_amdgcn_exp2f(e[0]), __builtin_amdgcn_exp2f(e[1])};
       const f32x2 ds = pr * f32x2{dp[r], dp[r + 1]};
       sc[r] = pr[0]; sc[r + 1] = pr[1];
       dp[r] = ds[0]; dp[r + 1] = ds[1];
@@ -303,7 +268,7 @@ __device__ __forceinline__ void k_step32(Ops32<D, KPf<D>::value>& o, const char*
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float pr = key_live ? MDM_EXP2(sc[r] * c2) : 0.f;
+      const float pr = key_live ? __builtin_amdgcn_exp2f(sc[r] * c2) : 0.f;
       sc[r] = pr;
       dp[r] = pr * dp[r];
     }
@@ -315,19 +280,19 @@ __device__ __forceinline__ void k_step32(Ops32<D, KPf<D>::value>& o, const char*
   for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
     for (int blk = 0; blk < G::NB; ++blk)
-      tq[s2][blk] = (MDM_ATT_ABL & 2) ? kf[blk] : lds_tr_pair(Qt + s2 * 16 * G::PITCH + fo.tr[0][blk], Qt + s2 * 16 * G::PITCH + fo.tr[1][blk]);
+      tq[s2][blk] = lds_tr_pair(Qt + s2 * 16 * G::PITCH + fo.tr[0][blk], Qt + s2 * 16 * G::PITCH + fo.tr[1][blk]);
   MDM_FENCE();
 #pragma unroll
-  for (int blk = 0; blk < G::NB; ++blk) if (!(MDM_ATT_ABL & 32)) dv[blk] = mma32(tg[0][blk], p0, dv[blk]); else dv[blk][0] += (float)p0[0] + (float)tg[0][blk][0];
+  for (int blk = 0; blk < G::NB; ++blk) dv[blk] = mma32(tg[0][blk], p0, dv[blk]);
 #pragma unroll
-  for (int blk = 0; blk < G::NB; ++blk) if (!(MDM_ATT_ABL & 32)) dv[blk] = mma32(tg[1][blk], p1, dv[blk]); else dv[blk][1] += (float)p1[0] + (float)tg[1][blk][0];
+  for (int blk = 0; blk < G::NB; ++blk) dv[blk] = mma32(tg[1][blk], p1, dv[blk]);
   MDM_FENCE();
   load_ops32<D, PF>(o, Qn, Gn, fo);
   MDM_FENCE();
 #pragma unroll
-  for (int blk = 0; blk < G::NB; ++blk) if (!(MDM_ATT_ABL & 32)) dk[blk] = mma32(tq[0][blk], s0, dk[blk]); else dk[blk][0] += (float)s0[0] + (float)tq[0][blk][0];
+  for (int blk = 0; blk < G::NB; ++blk) dk[blk] = mma32(tq[0][blk], s0, dk[blk]);
 #pragma unroll
-  for (int blk = 0; blk < G::NB; ++blk) if (!(MDM_ATT_ABL & 32)) dk[blk] = mma32(tq[1][blk], s1, dk[blk]); else dk[blk][1] += (float)s1[0] + (float)tq[1][blk][0];
+  for (int blk = 0; blk < G::NB; ++blk) dk[blk] = mma32(tq[1][blk], s1, dk[blk]);
 }
 
 // a wave's [d][32] accumulator block (lane <-> row of the tensor, register <-> channel) -> bf16 rows in global memory.
@@ -585,7 +550,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_small32_kernel(AttnArgs p) {
       const char* Vn = kn >= nt ? VC : R1 + kn * T32;
       const int rem = L - kt * 32;
       const unsigned live = cross ? tmask : (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u));
-      prio_flip(kt + (wave >> 2));
       q_step32<D>(ko, Kt, Vt, Kn, Vn, qf, gf, cross ? nlc : nls, cross ? ndc : nds, live, c2, hi, fo, dq);
     }
     ATT_STAMP(4);
@@ -628,7 +592,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_small32_kernel(AttnArgs p) {
     load_ops32<D, KPf<D>::value>(qo, R2, R0, fo);
     for (int qt = 0; qt < nt; ++qt) {
       const int qn = qt + 1 < nt ? qt + 1 : qt;
-      prio_flip(qt + (wave >> 2));
       k_step32<D>(qo, R2 + qt * T32, R0 + qt * T32, R2 + qn * T32, R0 + qn * T32, nlse_self + qt * 32, ndel_self + qt * 32,
                   kf, vf, key < L, c2, hi, fo, dk, dv);
     }
@@ -687,7 +650,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_small32_kernel(AttnArgs p) {
 // ---------------------------------------------------------------------------------------------------------------------
 template <int D, int NTHR = 512> struct Stream32 {
   using G = A32<D>;
-  static constexpr int SR = MDM_ATT_SR;                      // rows (keys / queries) of a stage: SR / 32 tiles per barrier
+  static constexpr int SR = 64;                              // rows (keys / queries) of a stage: SR / 32 tiles per barrier
   static constexpr int NSUB = SR / 32;
   static constexpr int HALF = SR * G::PITCH;                 // one tensor's rows
   static constexpr int NVS = 2 * SR * G::CPR / NTHR;         // 16-byte chunks per thread and stage (two tensors)
@@ -795,8 +758,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq32_kernel(AttnArgs p) {
   auto stage = [&](auto cur_c, const int t) {
     constexpr int CUR = decltype(cur_c)::value, NXT = (CUR + 1) % 3, NN = (CUR + 2) % 3;
     const char* Ks = smem + CUR * STAGE;
-    if (!(MDM_ATT_ABL & 4)) __syncthreads();
-    const bool more = t + 2 < ntot && !(MDM_ATT_ABL & 8);
+    __syncthreads();
+    const bool more = t + 2 < ntot;
     if (more) fetch(t + 2);
     if (w_active) {
       const bool cross = t >= nself;
@@ -804,7 +767,6 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dq32_kernel(AttnArgs p) {
 #pragma unroll
       for (int sub = 0; sub < NSUB; ++sub) {
         if (sub >= nsub) break;
-        prio_flip(t * NSUB + sub + (wave >> 2));
         const int rem = L - (t * SR + sub * 32);
         const unsigned live = cross ? tmask : (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u));
         // the next tile: the next tile of this stage, else the first of the next stage, else (nothing left) itself
@@ -905,15 +867,14 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkv32_kernel(AttnArgs p) {
       constexpr int CUR = decltype(cur_c)::value, NXT = (CUR + 1) % 3, NN = (CUR + 2) % 3;
       const char* Qs = smem + CUR * STAGE;
       const float* nl = reinterpret_cast<const float*>(Qs + 2 * ST::HALF);
-      if (!(MDM_ATT_ABL & 4)) __syncthreads();
-      const bool more = t + 2 < nst && !(MDM_ATT_ABL & 8);
+      __syncthreads();
+      const bool more = t + 2 < nst;
       if (more) fetch(t + 2);
       if (w_active) {
         const int nsub = min(NSUB, (L - t * SR + 31) >> 5);
 #pragma unroll
         for (int sub = 0; sub < NSUB; ++sub) {
           if (sub >= nsub) break;
-          prio_flip(t * NSUB + sub + (wave >> 2));
           const bool in_stage = sub + 1 < nsub, last = !in_stage && t + 1 >= nst;
           const char* Qn = in_stage ? Qs + (sub + 1) * T32 : (last ? Qs + sub * T32 : smem + NXT * STAGE);
           k_step32<D>(qo, Qs + sub * T32, Qs + ST::HALF + sub * T32, Qn, Qn + ST::HALF, nl + sub * 32, nl + SR + sub * 32,

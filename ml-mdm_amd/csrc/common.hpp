@@ -344,16 +344,10 @@ struct DGeluCode {
     g[0] = a[0]; g[1] = a[1]; g[2] = b[0]; g[3] = b[1];
   }
 };
-#if defined(MDM_GELU_EXACT)   // development A/B (tools/build_variant_gemm.sh): the erf form for bf16 tensors too
-template <typename T> __device__ __forceinline__ float gelu_t(float z) { return gelu_f(z); }
-template <typename T> __device__ __forceinline__ float dgelu_t(float z) { return dgelu_f(z); }
-#else
 template <typename T> __device__ __forceinline__ float gelu_t(float z) { return sizeof(T) == 2 ? gelu_poly(z) : gelu_f(z); }
 template <typename T> __device__ __forceinline__ float dgelu_t(float z) { return sizeof(T) == 2 ? dgelu_poly(z) : dgelu_f(z); }
-#endif
 // v[e] = gelu(v[e]) / v[e] *= gelu'(a[e]) over a chunk (N even): bf16 tensors take the packed polynomial forms
 template <typename T, int N> __device__ __forceinline__ void gelu_vec(float (&v)[N]) {
-#if !defined(MDM_GELU_EXACT) && !defined(MDM_GELU_SCALAR)   // (MDM_GELU_SCALAR: development A/B, the per-element forms)
   if constexpr (sizeof(T) == 2) {
 #pragma unroll
     for (int e = 0; e < N; e += 2) {
@@ -362,12 +356,10 @@ template <typename T, int N> __device__ __forceinline__ void gelu_vec(float (&v)
     }
     return;
   }
-#endif
 #pragma unroll
   for (int e = 0; e < N; ++e) v[e] = gelu_t<T>(v[e]);
 }
 template <typename T, int N> __device__ __forceinline__ void mul_dgelu_vec(float (&v)[N], const float (&a)[N]) {
-#if !defined(MDM_GELU_EXACT) && !defined(MDM_GELU_SCALAR)   // (MDM_GELU_SCALAR: development A/B, the per-element forms)
   if constexpr (sizeof(T) == 2) {
 #pragma unroll
     for (int e = 0; e < N; e += 2) {
@@ -376,7 +368,6 @@ template <typename T, int N> __device__ __forceinline__ void mul_dgelu_vec(float
     }
     return;
   }
-#endif
 #pragma unroll
   for (int e = 0; e < N; ++e) v[e] *= dgelu_t<T>(a[e]);
 }

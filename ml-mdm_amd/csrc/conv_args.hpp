@@ -34,23 +34,11 @@ struct ConvArgs {
   // pixel-shuffled store (ps_cout > 0): output column (phase, co), row (n, bh, bw) of a ps_H x ps_W grid goes to
   // y[n, 2 bh + ph, 2 bw + pw, co] of a [N, 2 ps_H, 2 ps_W, ps_cout] tensor (a column tile lies inside one phase)
   int ps_cout, ps_H, ps_W;
-  // GroupNorm of the OUTPUT fused into the epilogue (gn_y != null; 256x192 tile, bf16): a row tile is the 256 pixels of
-  // one sample and a column tile 8 whole groups of 24 channels, so the tile holds everything the statistics need.
-  // Besides y the launch writes gn_y = act(GroupNorm(y)), the norm's stats [N][G][2] and coef [N][C][2] (what
-  // mdm_gn_fwd would have produced from y: the standalone norm kernel and its read of y disappear).
-  void* gn_y;
-  const float* gn_gamma;
-  const float* gn_beta;
-  float* gn_stats;
-  float* gn_coef;
-  float gn_eps;
-  int gn_act, gn_groups;
-  // development flags (include/mdm_hip_dev.h knobs 0 and 1; always 0 in the product), filled in by the launch helpers.
-  // They travel in the ARGUMENT block -- a wave-uniform scalar load at kernel start -- and NOT in a __device__ variable:
-  // rounds 3-5 read `g_knobs[1]` (a mutable global, hence a VECTOR load) inside the epilogue's store loop, and the
-  // `s_waitcnt vmcnt(0)` in front of its use made every chunk's store wait for the acknowledgement of the previous one
-  // (round 6; HISTORY.md section 4.1)
-  //   bit 0: the epilogue skips its global stores (timing only);  bit 1: the LDS-DMA fetches nothing (timing only)
+  // development knob 0 (include/mdm_hip_dev.h; always 0 in the product), filled in by the launch helpers: bit 1 = the
+  // LDS-DMA fetches nothing (timing only).  It travels in the ARGUMENT block (a wave-uniform scalar load), not in a
+  // __device__ variable (round 6).  Kept although timing-only: without this uniform branch in the
+  // tile setup the compiler gives the 3x3 GEMM instantiations 6-8 more VGPRs (256x256: 17 spilled instead of 9), and the
+  // train step ran 0.7 ms slower.
   int dev_flags;
 };
 

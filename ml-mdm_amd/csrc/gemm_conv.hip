@@ -64,7 +64,7 @@ struct NoPrefetch { __device__ __forceinline__ void operator()() const {} };
 //     (their DMA is older than the stores) -- the bookkeeping cost 8-14 more spilled registers in the 256-wide kernels and
 //     the train step nothing or worse (88.8 vs 86.4 ms, profiles/r06_did_not_pay.md); branch-free store loops per epilogue
 //     kind: 82-129 spilled registers, half the speed (tools/mfma_hazard_scan.py's spill cap caught both before the GPU did).
-template <typename T, int BM, int BN, int WM, int WN, int LDS_BYTES, typename AfterLds = NoPrefetch, bool GN = false>
+template <typename T, int BM, int BN, int WM, int WN, int LDS_BYTES, typename AfterLds = NoPrefetch>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], char* smem,
                                               int m0, int n0, AfterLds after_lds = AfterLds()) {
   constexpr int EPV = Tr<T>::EPV;
@@ -177,119 +177,12 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, f32x4 (&acc)[BM
     // this wave is the next tile's DMA (after_lds) and, younger than it, this tile's stores
     if (PSRC) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
     after_lds();
-    if constexpr (GN && BM == 256 && BN == 192 && sizeof(T) == 2) {
-      {
-        // ---- epilogue with the GroupNorm of the output (host-checked: whole tiles, no activation on y itself) ----
-        constexpr int NG = 8, CPG = 24;                         // groups per column tile, channels per group
-        float* const gsum = reinterpret_cast<float*>(smem + LDS_BYTES);   // scratch behind the k-loop stages:
-        float* const gsq = gsum + NG * 16;                       //   [NG][16] partial sums, partial squares,
-        float* const gmean = gsq + NG * 16;                      //   [NG] mean, [NG] rstd,
-        float* const grstd = gmean + NG;                         //   [192][2] coefficients a, b
-        float* const cab = grstd + NG;
-        if (tid < 2 * NG * 16) gsum[tid] = 0.f;
-        float part[NG];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) part[g] = 0.f;
-        // pass 1: finish y (residual), store it, keep the ROUNDED values (what a separate norm kernel would read)
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-          const int idx = tid + i * NT_;
-          const int row = idx / OCH, ch = idx - row * OCH;
-          const size_t o = (size_t)(m0 + row) * p.Cout + n0 + ch * EPV;
-          Chunk<T> c;
-          c.load(reinterpret_cast<const T*>(&raw[i]));
-          if (R) {
-            Chunk<T> rr;
-            rr.load(reinterpret_cast<const T*>(&pre[i]));
-#pragma unroll
-            for (int e = 0; e < EPV; ++e) c.v[e] += rr.v[e];
-            c.store(reinterpret_cast<T*>(&raw[i]));
-            c.load(reinterpret_cast<const T*>(&raw[i]));
-          }
-          *reinterpret_cast<uint4*>(Y + o) = raw[i];
-          float sv = 0.f;
-#pragma unroll
-          for (int e = 0; e < EPV; ++e) sv += c.v[e];
-          const int g = ch / 3;
-#pragma unroll
-          for (int gg = 0; gg < NG; ++gg) part[gg] += g == gg ? sv : 0.f;
-        }
-        __syncthreads();   // scratch zeroed
-#pragma unroll
-        for (int gg = 0; gg < NG; ++gg) atomicAdd(&gsum[gg * 16 + (lane & 15)], part[gg]);
-        __syncthreads();
-        if (tid < NG) {
-          float t = 0.f;
-          for (int k = 0; k < 16; ++k) t += gsum[tid * 16 + k];
-          gmean[tid] = t / (float)(BM * CPG);
-        }
-        __syncthreads();
-        // pass 2: centred squares
-#pragma unroll
-        for (int g = 0; g < NG; ++g) part[g] = 0.f;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-          const int ch = (tid + i * NT_) % OCH;
-          Chunk<T> c;
-          c.load(reinterpret_cast<const T*>(&raw[i]));
-          const int g = ch / 3;
-          const float mu = gmean[g];
-          float sv = 0.f;
-#pragma unroll
-          for (int e = 0; e < EPV; ++e) { const float d = c.v[e] - mu; sv += d * d; }
-#pragma unroll
-          for (int gg = 0; gg < NG; ++gg) part[gg] += g == gg ? sv : 0.f;
-        }
-#pragma unroll
-        for (int gg = 0; gg < NG; ++gg) atomicAdd(&gsq[gg * 16 + (lane & 15)], part[gg]);
-        __syncthreads();
-        const int img = m0 / BM;                                // the sample this row tile is
-        if (tid < NG) {
-          float t = 0.f;
-          for (int k = 0; k < 16; ++k) t += gsq[tid * 16 + k];
-          const float rstd = rsqrtf(t / (float)(BM * CPG) + p.gn_eps);
-          grstd[tid] = rstd;
-          const int g = n0 / CPG + tid;
-          p.gn_stats[((size_t)img * p.gn_groups + g) * 2] = gmean[tid];
-          p.gn_stats[((size_t)img * p.gn_groups + g) * 2 + 1] = rstd;
-        }
-        __syncthreads();
-        if (tid < BN) {
-          const int cglob = n0 + tid, g = tid / CPG;
-          const float ga = p.gn_gamma[cglob], be = p.gn_beta[cglob];
-          const float a_ = ga * grstd[g], b_ = be - gmean[g] * grstd[g] * ga;
-          cab[2 * tid] = a_; cab[2 * tid + 1] = b_;
-          p.gn_coef[((size_t)img * p.Cout + cglob) * 2] = a_;
-          p.gn_coef[((size_t)img * p.Cout + cglob) * 2 + 1] = b_;
-        }
-        __syncthreads();
-        // pass 3: the normalised output
-        T* __restrict__ Y2 = reinterpret_cast<T*>(p.gn_y);
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) {
-          const int idx = tid + i * NT_;
-          const int row = idx / OCH, ch = idx - row * OCH;
-          const size_t o = (size_t)(m0 + row) * p.Cout + n0 + ch * EPV;
-          Chunk<T> c;
-          c.load(reinterpret_cast<const T*>(&raw[i]));
-#pragma unroll
-          for (int e = 0; e < EPV; ++e) {
-            const float z = cab[2 * (ch * EPV + e)] * c.v[e] + cab[2 * (ch * EPV + e) + 1];
-            c.v[e] = p.gn_act ? silu_f(z) : z;
-          }
-          c.store(Y2 + o);
-        }
-        __syncthreads();   // the scratch may be zeroed again by the next tile's epilogue
-        return;
-      }
-    }
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       const int idx = tid + i * NT_;
       const int row = idx / OCH, ch = idx - row * OCH;
       const int m = m0 + row, n = n0 + ch * EPV;
       if (m >= p.M || n >= p.Cout) continue;
-      if (p.dev_flags & 1) continue;   // development knob 1 (a kernel ARGUMENT: see conv_args.hpp)
       size_t o = (size_t)m * p.Cout + n;
       if (p.ps_cout > 0) {   // (phase, co) column of low-res pixel (n, bh, bw) -> its place in the 2x larger image
         const int ph = n / p.ps_cout, co = n - ph * p.ps_cout;
@@ -563,12 +456,10 @@ struct NoConvGroup {};
 // channel block: k-tile kt = (channel block kt >> 2, tap 4 + (kt & 1) + 3 * ((kt >> 1) & 1)), K = 4 * Cin.  That is the
 // input gradient of a STRIDE-2 3x3 convolution in its pixel-unshuffled form (mdm_conv_s2_dgrad): dx[2b + p] only draws
 // from dy[b] and dy[b + 1], so over the 2x2-blocked dx (4 Cin channels per block) it is a 2x2 stride-1 correlation.
-// GN: the epilogue also normalises the output (ConvArgs::gn_*; its own instantiation, so the extra registers of that
-// epilogue do not touch the other kernels' allocation).
 // NSTG: LDS stages of the k-loop (2 in every training instantiation; 4 for the under-filled grids of small-batch sampling,
 // one block per CU: there a k-tile is 0.25 us of MFMA work behind a ~1.3 us DMA round trip, and with two stages every
 // k-tile waits for its own fetch -- with four, three fetches are in flight and the loop runs at the DMA's throughput).
-template <int BM, int BN, int WM, int WN, int MODE, bool GROUPED = false, bool SPLITK = false, bool SEL4 = false, bool GN = false, int NSTG = 2>
+template <int BM, int BN, int WM, int WN, int MODE, bool GROUPED = false, bool SPLITK = false, bool SEL4 = false, int NSTG = 2>
 __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm_bl_kernel(ConvArgs p, std::conditional_t<GROUPED, ConvGroup, NoConvGroup> gr) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the buffer-resource type has no host-side counterpart: the host pass only needs the stub
   using T = bf16;
@@ -820,7 +711,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm_bl_kernel(ConvArgs 
           MDM_TILE_PROLOGUE();
         }
       };
-      conv_epilogue<T, BM, BN, WM, WN, NSTG * STAGE, decltype(prefetch_next), GN>(pe, acc, smem, cur_m0, cur_n0, prefetch_next);
+      conv_epilogue<T, BM, BN, WM, WN, NSTG * STAGE, decltype(prefetch_next)>(pe, acc, smem, cur_m0, cur_n0, prefetch_next);
     }
     if (next >= tiles_total) break;
     tile = next;
@@ -2214,9 +2105,7 @@ __global__ __launch_bounds__(256) void upconv_bfold_kernel(const float* __restri
   db[co] = accumulate ? db[co] + v : v;
 }
 
-static int g_no_deep_pipe = 0;      // development knob 11: 1 = no 4-stage instantiations for under-filled grids
-static int g_one_tile_blocks = 0;   // development knob 5
-static int g_dev_flags = 0;         // development knobs 0 / 1 -> ConvArgs::dev_flags (bit 1 / bit 0) of every GEMM launch
+static int g_dev_flags = 0;   // development knob 0 -> ConvArgs::dev_flags (bit 1) of every GEMM launch
 static inline ConvArgs with_dev_flags(const ConvArgs& a) { ConvArgs b = a; b.dev_flags = g_dev_flags; return b; }
 static thread_local char g_last_gemm[96] = "";
 extern "C" const char* mdm_last_gemm_kernel(void) { return g_last_gemm; }
@@ -2242,8 +2131,8 @@ static int launch_conv_bl(const ConvArgs& a_, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
   if constexpr (BM == 128 && BN == 128) {
     // under-filled grid (sampling at batch 1-4): one block per CU, four LDS stages (see the kernel's NSTG note)
-    if (tiles <= device_cus() && !g_no_deep_pipe) {
-      auto kern4 = conv_gemm_bl_kernel<BM, BN, WM, WN, MODE, false, false, false, false, 4>;
+    if (tiles <= device_cus()) {
+      auto kern4 = conv_gemm_bl_kernel<BM, BN, WM, WN, MODE, false, false, false, 4>;
       ensure_dynamic_lds(kern4, 2 * smem);
       hipLaunchKernelGGL(kern4, dim3(tiles), dim3(WM * WN * 64), 2 * smem, st, a, NoConvGroup{});
       MDM_NOTE_KERNEL("conv_gemm_bl_kernel<%d, %d, %d, %d, %d, 4 stages>", BM, BN, WM, WN, MODE);
@@ -2251,25 +2140,9 @@ static int launch_conv_bl(const ConvArgs& a_, hipStream_t st) {
     }
   }
   const int resident = device_cus() * (WM * WN == 4 ? 2 : 1);   // persistent blocks: one (8 waves) or two (4 waves) per CU
-  // development knob 5: 1 = one block per output tile (a block's stores drain while its successor on the CU starts), 0 =
-  // persistent blocks (the next tile's first DMA is issued from inside the epilogue)
-  const int grid = (g_one_tile_blocks || tiles < resident) ? tiles : resident;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(WM * WN * 64), smem, st, a, NoConvGroup{});
-  MDM_NOTE_KERNEL("conv_gemm_bl_kernel<%d, %d, %d, %d, %d>", BM, BN, WM, WN, MODE);
-  MDM_LAUNCH_STATUS();
-}
-
-template <int MODE>
-static int launch_conv_bl_gn(const ConvArgs& a_, hipStream_t st) {
-  const ConvArgs a = with_dev_flags(a_);
-  constexpr int BM = 256, BN = 192, WM = 2, WN = 4;
-  constexpr int smem = 2 * (BM + BN) * 128 + 4096;   // + the epilogue's statistics scratch
-  auto kern = conv_gemm_bl_kernel<BM, BN, WM, WN, MODE, false, false, false, true>;
-  ensure_dynamic_lds(kern, smem);
-  const int tiles = ((a.M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN);
-  const int resident = device_cus();
+  // persistent blocks: the next tile's first DMA is issued from inside the epilogue
   hipLaunchKernelGGL(kern, dim3(tiles < resident ? tiles : resident), dim3(WM * WN * 64), smem, st, a, NoConvGroup{});
-  MDM_NOTE_KERNEL("conv_gemm_bl_kernel<%d, %d, %d, %d, %d, +gn>", BM, BN, WM, WN, MODE);
+  MDM_NOTE_KERNEL("conv_gemm_bl_kernel<%d, %d, %d, %d, %d>", BM, BN, WM, WN, MODE);
   MDM_LAUNCH_STATUS();
 }
 
@@ -2316,25 +2189,20 @@ static bool conv_bl_ok(const ConvArgs& a) {
 // k-tiles of serial walk (~10 us) -- the second launch costs about that much.  1 = do not split.
 // Considered whenever the tiles fill less than `fill` percent of the 2-per-CU slots: 80 also catches the training shapes
 // of the nested model's inner U-Net at batch 16 (M = 4096: 192 tiles of 128x128 at N = 768), 25 was the sampling-only rule.
-static int g_split_fill = 80;   // development knob 6
-static int g_no_direct = 0;     // development knob 7: 1 = narrow 3x3 convolutions back on the implicit-GEMM kernel
-static int g_no_wgrad_direct = 0;   // development knob 8 (mdm_dev_set_knob): 1 = no wgrad_direct_kernel (split GEMM for the narrow weight gradients too)
-static int g_split_minkt = 6, g_split_minsave = 16;   // development knobs 9, 10
-static int g_split_per_cu = 0;                        // development knob 12: blocks per CU a split aims for (0 = by M, below)
 static int conv_ksplit(int M, int Cout, int K, int dtype) {
   if (dtype != DT_BF16 || K % 64 != 0 || Cout % 8 != 0 || Cout <= 64) return 1;
-  const int fill = g_split_fill;   // development knob 6 (mdm_dev_set_knob), default 80
+  constexpr int fill = 80, minkt = 6, minsave = 16;
   const long tiles = (long)((M + 127) / 128) * ((Cout + 127) / 128);
   const int nt = K / 64, cus = device_cus();
-  if (tiles * 100 > (long)fill * 2 * cus || nt < 2 * g_split_minkt) return 1;
+  if (tiles * 100 > (long)fill * 2 * cus || nt < 2 * minkt) return 1;
   // blocks per CU a split aims for: two 2-stage blocks for the training shapes (M = 4096 of the nested models' inner U-Net),
   // ONE 4-stage block for the sampling shapes (M <= 2048: 5.98 -> 5.84 ms per graphed UNet-64 iteration at batch 4,
   // 20.8 -> 20.4 nested-1024; the nested-256 train step is indifferent, 59.4 vs 59.4)
-  const int per_cu = g_split_per_cu ? g_split_per_cu : (M <= 2048 ? 1 : 2);
+  const int per_cu = M <= 2048 ? 1 : 2;
   long sp = ((long)per_cu * cus) / tiles;
-  if (sp > nt / g_split_minkt) sp = nt / g_split_minkt;
+  if (sp > nt / minkt) sp = nt / minkt;
   if (sp > 16) sp = 16;
-  if (sp < 2 || nt - (nt + sp - 1) / sp < g_split_minsave) return 1;
+  if (sp < 2 || nt - (nt + sp - 1) / sp < minsave) return 1;
   return (int)sp;
 }
 
@@ -2358,8 +2226,8 @@ static int launch_conv_bl_splitk(ConvArgs a, int splits, float* ws, hipStream_t 
   a.part = ws;
   const int tiles = ((a.M + BM - 1) / BM) * ((a.Cout + BN - 1) / BN) * a.ksplit;
   const int resident = device_cus() * 2;
-  if (tiles <= device_cus() && !g_no_deep_pipe) {   // one block per CU: four LDS stages
-    auto kern4 = conv_gemm_bl_kernel<BM, BN, WM, WN, MODE, false, true, false, false, 4>;
+  if (tiles <= device_cus()) {   // one block per CU: four LDS stages
+    auto kern4 = conv_gemm_bl_kernel<BM, BN, WM, WN, MODE, false, true, false, 4>;
     ensure_dynamic_lds(kern4, 2 * smem);
     hipLaunchKernelGGL(kern4, dim3(tiles), dim3(WM * WN * 64), 2 * smem, st, a, NoConvGroup{});
   } else
@@ -2376,6 +2244,7 @@ static int launch_conv_bl_splitk(ConvArgs a, int splits, float* ws, hipStream_t 
 // (relative efficiencies measured with tools/kbench.py: the larger tiles move fewer LDS bytes per FLOP; N = 768 --
 // 130 GEMMs of a step -- is exactly one round of 256x192 tiles at M = 16384).
 static int g_force_tile = 0;   // development knob 2 (mdm_dev_set_knob): 128128 / 256192 / 256256, 0 = cost model
+static int g_no_wgrad_direct = 0;   // development knob 8 (mdm_dev_set_knob): 1 = no wgrad_direct_kernel (split GEMM for the narrow weight gradients too)
 static int conv_tile_code(int M, int Cout, int dtype) {
   if (Cout <= 32) return 128032;
   if (Cout <= 64) return 128064;
@@ -2553,7 +2422,7 @@ static int launch_conv_direct(const ConvArgs& a, hipStream_t st) {
 
 // usable for this problem?  (bf16, 3x3 stride 1, plain epilogue, 32 / 64 channels both sides, tile-aligned image)
 static bool conv_direct_ok(const ConvArgs& a, int ksize, int transposed, int dtype) {
-  if (g_no_direct || dtype != DT_BF16 || ksize != 3 || transposed || a.stride != 1 || a.act != 0 || a.aux || a.ypre) return false;
+  if (dtype != DT_BF16 || ksize != 3 || transposed || a.stride != 1 || a.act != 0 || a.aux || a.ypre) return false;
   if (!(a.Cin == 32 || a.Cin == 64) || !(a.Cout == 32 || a.Cout == 64)) return false;
   if (a.kblk != 0 && !(a.kblk == 64 && a.Cin == 64)) return false;      // [Cout][tap][Cin] either way
   if (a.Ho != a.H || a.Wo != a.W || a.H % 8 != 0 || a.W % 64 != 0) return false;
@@ -2778,36 +2647,6 @@ extern "C" int mdm_conv_up_dgrad(const void* dyb, const void* w_t, void* dx, int
   return launch_sel4(a, code == 256256 ? 256 : (code == 256192 ? 192 : 128), reinterpret_cast<hipStream_t>(stream));
 }
 
-// ---- convolution + GroupNorm of its output in one launch ------------------------------------------------------
-// host-only: does (problem, norm) fit the fused epilogue?  bf16; 16x16 images (a 256-row tile = one sample); 24 channels
-// per group and Cout a multiple of 192 (a 192-column tile = 8 whole groups); a problem the buffer-addressed loader takes
-extern "C" int mdm_conv_fwd_gn_ok(int N, int H, int W, int Cin, int Cout, int ksize, int kblock, int groups, int dtype) {
-  if (dtype != DT_BF16 || H * W != 256 || Cout % 192 != 0 || groups <= 0 || Cout != groups * 24 || Cin % 64 != 0) return 0;
-  if (ksize != 1 && !(ksize == 3 && kblock == 64)) return 0;
-  ConvArgs a = {};
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.K = ksize * ksize * Cin; a.kblk = kblock;
-  return (ksize == 1 ? conv_bl_ok<bf16, MODE_1x1>(a) : conv_bl_ok<bf16, MODE_3x3>(a)) ? 1 : 0;
-}
-
-// y = conv(x, w_packed) + bias (+ res)  AND  y_norm = act(GroupNorm(y; gamma, beta, groups, eps)), stats [N][G][2],
-// coef [N][Cout][2] (the outputs of mdm_gn_fwd on y) from ONE launch -- replaces nn.Conv2d followed by nn.GroupNorm
-// (models/unet.py:310-311 proj_out -> ffn[0]; :312 -> the next layer's norm; :238 -> :300).  stride 1, no activation on y.
-extern "C" int mdm_conv_fwd_gn(const void* x, const void* w_packed, const float* bias, const void* res, void* y, int N, int H,
-                               int W, int Cin, int Cout, int ksize, int kblock, const float* gamma, const float* beta,
-                               int groups, float eps, int gn_act, void* y_norm, float* stats, float* coef, int dtype,
-                               void* stream) {
-  MDM_CHECK_ARG(x && w_packed && y && gamma && beta && y_norm && stats && coef);
-  MDM_CHECK_ARG(mdm_conv_fwd_gn_ok(N, H, W, Cin, Cout, ksize, kblock, groups, dtype));
-  ConvArgs a = {};
-  a.x = x; a.w = w_packed; a.bias = bias; a.res = res; a.y = y;
-  a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = H; a.Wo = W; a.Cout = Cout; a.stride = 1;
-  a.M = N * H * W; a.K = ksize * ksize * Cin; a.kblk = kblock; a.ksplit = 1;
-  a.gn_y = y_norm; a.gn_gamma = gamma; a.gn_beta = beta; a.gn_stats = stats; a.gn_coef = coef; a.gn_eps = eps;
-  a.gn_act = gn_act; a.gn_groups = groups;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return ksize == 1 ? launch_conv_bl_gn<MODE_1x1>(a, st) : launch_conv_bl_gn<MODE_3x3>(a, st);
-}
-
 // y[g] [M, Cout] = x[g] [M, Cin] * w_packed[g]^T + bias[g] for `groups` (<= 32) linear layers of one shape, bf16, in ONE
 // launch.  The pointer arrays are HOST arrays of device pointers; bias may be NULL (no bias at all) .  Passing the
 // dgrad packs and the output gradients computes the input gradients of the same layers.  Cin % 64 == 0.
@@ -2835,22 +2674,11 @@ extern "C" int mdm_linear_grouped(const void* const* x, const void* const* w_pac
 
 extern "C" int mdm_dev_ffn_aux_bytes(void) { return kFfnAuxByte ? 1 : 2; }
 
-static int g_skip_wgrad_reduce = 0;   // development knob 13: timing-only ablation, the slab reduces are not launched (WRONG gradients)
 extern "C" int mdm_dev_set_knob(int idx, int value) {
-  MDM_CHECK_ARG(idx >= 0 && idx < 14);
-  if (idx == 13) { g_skip_wgrad_reduce = value; return 0; }
-  if (idx == 12) { g_split_per_cu = value > 0 ? value : 0; return 0; }
-  if (idx == 11) { g_no_deep_pipe = value; return 0; }
-  if (idx == 8) { g_no_wgrad_direct = value; return 0; }
-  if (idx == 9) { g_split_minkt = value > 0 ? value : 6; return 0; }
-  if (idx == 10) { g_split_minsave = value > 0 ? value : 16; return 0; }
-  if (idx == 5) { g_one_tile_blocks = value; return 0; }
-  if (idx == 3 || idx == 4) return 0;   // (were conv_gemm_x_kernel switches; the kernel was removed in round 6)
-  if (idx == 6) { g_split_fill = value > 0 ? value : 80; return 0; }
-  if (idx == 7) { g_no_direct = value; return 0; }
-  if (idx == 2) { g_force_tile = value; return 0; }
-  if (idx == 0) { g_dev_flags = (g_dev_flags & ~2) | ((value & 1) ? 2 : 0); return 0; }
-  if (idx == 1) { g_dev_flags = (g_dev_flags & ~1) | (value ? 1 : 0); return 0; }
+  MDM_CHECK_ARG(idx == 0 || idx == 2 || idx == 8);
+  if (idx == 0) g_dev_flags = value ? 2 : 0;
+  else if (idx == 2) g_force_tile = value;
+  else g_no_wgrad_direct = value;
   return 0;
 }
 
@@ -3249,7 +3077,6 @@ extern "C" int mdm_conv_wgrad_grouped(const void* const* x, const void* const* d
 extern "C" int mdm_conv_wgrad_reduce(const float* ws, float* dw_oihw, float* dbias, const void* dy, int M, int Cin,
                                      int Cout, int ksize, int accumulate, int dtype, void* stream) {
   MDM_CHECK_ARG(ws && dw_oihw && (ksize == 1 || ksize == 3));
-  if (g_skip_wgrad_reduce) return 0;
   const int K = ksize * ksize * Cin;
   int splits; size_t wsb;
   int rc = mdm_conv_wgrad_plan(M, Cout, K, dtype, &splits, &wsb);

@@ -17,7 +17,7 @@ import os as _os
 # streams than queues -- the data-parallel step has six: main, weight-gradient, communication, completion, RCCL's own, the
 # null stream -- kernels of one stream wait behind barrier packets (or collectives) of another.  Measured with every bucket
 # forced through RCCL in a world of one: +2.65 -> +1.6 ms per step under 8 queues, the plain step unchanged
-# (tools/calls/r6/c47_hw_queues.sh).  Read when the HIP runtime initialises (the first HIP call of the process), so this
+# (profiles/r06_did_not_pay.md).  Read when the HIP runtime initialises (the first HIP call of the process), so this
 # has to happen before any; an explicit setting in the environment wins.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 

@@ -183,37 +183,8 @@ def lib():
         if handle.mdm_abi_version() != ABI_VERSION:
             raise MdmHipError("libmdm_hip.so was built for ABI %d, include/mdm_hip.h declares %d: rebuild (__graft_entry__.build())"
                               % (handle.mdm_abi_version(), ABI_VERSION))
-        _apply_dev_env(handle)
         _lib = handle
     return _lib
-
-
-def _apply_dev_env(handle):
-    """Development A/B switches: environment variables of THIS Python layer, applied once through the setters of
-    include/mdm_hip_dev.h -- the C entry points themselves never look at the environment."""
-    mode = os.environ.get("MDM_HIP_ATTN_BWD")
-    if mode:
-        handle.mdm_dev_set_attn_bwd({"split": 1, "small": 2, "small16": 3, "stream32": 4, "long16": 5}.get(mode, 0))
-    if os.environ.get("MDM_HIP_SKIP_WGRAD_REDUCE") == "1":      # timing-only ablation, wrong gradients
-        handle.mdm_dev_set_knob(13, 1)
-    if os.environ.get("MDM_HIP_GN_CHUNK_MB"):
-        handle.mdm_dev_set_gn_chunk_mb(int(os.environ["MDM_HIP_GN_CHUNK_MB"]))
-    if os.environ.get("MDM_HIP_ONE_TILE_BLOCKS"):
-        handle.mdm_dev_set_knob(5, int(os.environ["MDM_HIP_ONE_TILE_BLOCKS"]))
-    if os.environ.get("MDM_HIP_SPLIT_FILL"):
-        handle.mdm_dev_set_knob(6, int(os.environ["MDM_HIP_SPLIT_FILL"]))
-    if os.environ.get("MDM_HIP_CONV_DIRECT") == "0":
-        handle.mdm_dev_set_knob(7, 1)
-    if os.environ.get("MDM_HIP_SPLIT_MINKT"):
-        handle.mdm_dev_set_knob(9, int(os.environ["MDM_HIP_SPLIT_MINKT"]))
-    if os.environ.get("MDM_HIP_SPLIT_MINSAVE"):
-        handle.mdm_dev_set_knob(10, int(os.environ["MDM_HIP_SPLIT_MINSAVE"]))
-    if os.environ.get("MDM_HIP_SPLIT_PER_CU"):
-        handle.mdm_dev_set_knob(12, int(os.environ["MDM_HIP_SPLIT_PER_CU"]))
-    if os.environ.get("MDM_HIP_DEEP_PIPE") == "0":   # no 4-stage GEMM instantiations for under-filled grids
-        handle.mdm_dev_set_knob(11, 1)
-    if os.environ.get("MDM_HIP_WGRAD_DIRECT") == "0":   # narrow weight gradients by the split GEMM
-        handle.mdm_dev_set_knob(8, 1)
 
 
 def check(rc: int, what: str):

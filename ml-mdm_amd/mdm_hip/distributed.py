@@ -280,8 +280,7 @@ class GradReducer:
                 # fp32 on the wire: the 1 / n rides inside the collective (ncclAvg) -- no pass over the bucket at all.  (Round 5
                 # scaled every bucket with its own `mul_` on this stream: 1.66 GB read + written per step next to backward.)
                 if self._avg_ok is None:
-                    self._avg_ok = (dist.get_backend(self.group) == "nccl" and hasattr(dist.ReduceOp, "AVG")
-                                    and os.environ.get("MDM_HIP_NO_AVG") != "1")   # (development A/B switch)
+                    self._avg_ok = dist.get_backend(self.group) == "nccl" and hasattr(dist.ReduceOp, "AVG")
                 if self._avg_ok and self.nranks > 1:   # (a world of one has nothing to scale; RCCL's AVG of one rank still runs
                     #                                      a kernel over the bucket: +3.9 ms per step, round 6)
                     h = dist.all_reduce(buf, op=dist.ReduceOp.AVG, group=self.group, async_op=True)

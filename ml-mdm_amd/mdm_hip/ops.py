@@ -9,7 +9,6 @@ Parameters stay fp32 in the reference's layout; packed copies for the kernels
 are cached per parameter version.
 """
 import ctypes
-import os
 import weakref
 
 import torch
@@ -22,7 +21,7 @@ F32, BF16, F32_SPLIT, F32_SPLIT_W = 0, 1, 2, 3
 # sampling at the reference's precision (it samples in fp32, diffusion.py:181-197) at about a third of the bf16 rate.  Only
 # the forward matmul-class launches have the path (convolutions / linears, attention); training in fp32 stays exact.
 _fp32_split = False
-_weight_planes_on = os.environ.get("MDM_HIP_NO_WEIGHT_PLANES", "0") != "1"   # development A/B: split the weights in the k-loop too
+_weight_planes_on = True   # split the weights in the k-loop too (tests turn it off for the in-loop split)
 
 
 class fp32_split:
@@ -78,8 +77,6 @@ def _p(t):
 # lead.  The C entry point behind it returns the same handle in ~0.2 us.
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _raw_device = getattr(torch._C, "_cuda_getDevice", None)
-if os.environ.get("MDM_HIP_SLOW_STREAM_LOOKUP", "0") == "1":   # development A/B
-    _raw_stream = None
 
 
 def _stream():
@@ -173,12 +170,10 @@ def enable_async_wgrad(flag: bool):
 
 
 def side_stream():
-    """the weight-gradient stream.  MDM_HIP_SIDE_PRIO (development A/B): its HIP stream priority (-1 high, 0 the default
-    streams', 1 low where the runtime has a third level)"""
+    """the weight-gradient stream"""
     global _side_stream
     if _side_stream is None:
-        prio = int(os.environ.get("MDM_HIP_SIDE_PRIO", "0"))
-        _side_stream = torch.cuda.Stream(priority=prio) if prio else torch.cuda.Stream()
+        _side_stream = torch.cuda.Stream()
     return _side_stream
 
 
@@ -195,10 +190,6 @@ def join_side_stream():
     if _side_stream is not None:
         torch.cuda.current_stream().wait_stream(_side_stream)
     _side_keep.clear()   # every later main-stream write is ordered behind the side stream's reads now
-
-
-_side_record_stream = os.environ.get("MDM_HIP_RECORD_STREAM", "0") == "1"   # development A/B: the old belt-and-braces form
-_late_wgrad_first = os.environ.get("MDM_HIP_LATE_WGRAD_FIRST", "1") != "0"     # development A/B (SharedInputLinearsFn.backward)
 
 
 def _off_critical_path(tensors, fn):
@@ -228,12 +219,9 @@ def _off_critical_path(tensors, fn):
     # Tensor.record_stream is needed.  (Rounds 2-6 called it as well: the caching allocator then records one event per block
     # on the side stream when the block is freed -- a purge of 64 entries freed ~330 blocks at once, 0.5-1.3 ms of
     # hipEventRecord calls = as many marker packets in the side stream's queue, and at the end of backward, where the main
-    # stream waits for the side stream, a gap of that length with the whole GPU idle: tools/fwd_gaps.py --gaps,
-    # tools/calls/r6/c39_hip_trace.sh; the host itself is 57-117 ms ahead, profiles/r06_host_lead.txt.)
+    # stream waits for the side stream, a gap of that length with the whole GPU idle: tools/fwd_gaps.py --gaps;
+    # the host itself is 57-117 ms ahead, profiles/r06_host_lead.txt.)
     live = [t for t in tensors if t is not None]
-    if _side_record_stream:
-        for t in live:
-            t.record_stream(side)
     _side_keep.append((done, live))
     if len(_side_keep) >= 64:
         _side_keep[:] = [e for e in _side_keep if not e[0].query()]
@@ -837,72 +825,9 @@ def conv(x, weight, bias=None, residual=None, stride=1):
 def conv_tap(x, weight, bias=None, stride=1):
     """(conv(x), x'): x' is x for a second consumer whose gradient is then added inside the convolution's input-gradient
     kernel (mdm_conv_s2_dgrad_res for the stride-2 3x3 case) rather than by a separate accumulation pass"""
-    if not (torch.is_grad_enabled() and x.requires_grad) or os.environ.get("MDM_HIP_NO_CONV_TAP", "0") == "1":
+    if not (torch.is_grad_enabled() and x.requires_grad):
         return ConvFn.apply(x, weight, bias, None, stride), x
     return ConvFn.apply(x, weight, bias, None, stride, True)
-
-
-# --------------------------------------------------------------------------------------
-# convolution + the GroupNorm that reads its output, one launch
-# --------------------------------------------------------------------------------------
-def conv_gn_enabled():
-    """whether the model uses the fused launch where it applies.  Off unless MDM_HIP_CONV_GN=1: measured in one call
-    against conv + group_norm on the 64x64 U-Net step (profiles/r03_did_not_pay.md) it is neutral -- the norm kernel it
-    removes is an HBM-bound launch that already overlaps the weight-gradient stream, and the epilogue's three passes over
-    the staged tile cost the convolution what the norm cost."""
-    return os.environ.get("MDM_HIP_CONV_GN", "0") == "1"
-
-
-def conv_gn_supported(x, weight, gamma, groups, stride=1):
-    """the fused epilogue takes bf16 16x16 images with 24 channels per group (the 768-channel level of the 64x64 U-Net)"""
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4 or stride != 1:
-        return False
-    ks = weight.shape[2] if weight.dim() == 4 else 1
-    cin, cout = weight.shape[1], weight.shape[0]
-    kb = 64 if (ks == 3 and cin % 64 == 0) else 0
-    return bool(_lib.lib().mdm_conv_fwd_gn_ok(x.shape[0], x.shape[1], x.shape[2], cin, cout, ks, kb, groups, BF16)) and \
-        gamma.numel() == cout
-
-
-class ConvGNFn(torch.autograd.Function):
-    """(y, y_norm) with y = conv(x, weight) + bias (+ residual) and y_norm = act(GroupNorm(y; gamma, beta)): the norm's
-    statistics and its normalised output come out of the convolution's epilogue (C ABI mdm_conv_fwd_gn) -- the separate
-    norm kernel and its read of y are gone.  Backward = the GroupNorm backward kernel (the gradient that reaches y
-    directly -- the residual branch, a skip connection -- rides in as its ``dres``) followed by the convolution's."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, residual, gamma, beta, groups, eps, act):
-        _require_gpu(x)
-        x, residual = _c(x), _c(residual)
-        ks = weight.shape[2] if weight.dim() == 4 else 1
-        wf, wd, bp, cin_pad, cout_pad, kbf, kbd = packed_weight(weight, bias, x.dtype)
-        N, H, W = x.shape[0], x.shape[1], x.shape[2]
-        g32, b32 = _c(gamma.detach().float()), _c(beta.detach().float())
-        y = torch.empty((N, H, W, cout_pad), dtype=x.dtype, device=x.device)
-        yn = torch.empty_like(y)
-        stats = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device)
-        coef = torch.empty((N, cout_pad, 2), dtype=torch.float32, device=x.device)
-        _prof_wrap("conv_gemm_bl_kernel<256, 192, +gn> M=%d N=%d K=%d" % (N * H * W, cout_pad, ks * ks * cin_pad),
-                   2.0 * N * H * W * cout_pad * ks * ks * cin_pad, lambda: _lib.check(
-            _lib.lib().mdm_conv_fwd_gn(_p(x), _p(wf), _p(bp), _p(residual), _p(y), N, H, W, cin_pad, cout_pad, ks, kbf, _p(g32), _p(b32),
-                                       groups, float(eps), act, _p(yn), _p(stats), _p(coef), BF16, _stream()), "mdm_conv_fwd_gn"))
-        ctx.save_for_backward(x, weight, bias, y, gamma, beta, stats, coef)
-        ctx.ks, ctx.stride, ctx.has_res = ks, 1, residual is not None
-        ctx.groups, ctx.act = groups, act
-        return y, yn
-
-    @staticmethod
-    def backward(ctx, dy_direct, dyn):
-        x, weight, bias, y, gamma, beta, stats, coef = ctx.saved_tensors
-        # gradient w.r.t. y: through the norm (dyn) plus whatever reached y directly
-        dy, dgamma, dbeta, _ = _gn_backward(dyn, y, gamma, beta, None, stats, coef, dy_direct, None, ctx.groups, ctx.act)
-        dx, dw, db, dres = _conv_backward(ctx, x, weight, bias, dy)
-        return dx, dw, db, dres, dgamma, dbeta, None, None, None
-
-
-def conv_gn(x, weight, bias, residual, gamma, beta, groups, eps=1e-5, silu=False):
-    """-> (y, act(GroupNorm(y))) with y = conv(x) + bias (+ residual); see ConvGNFn / conv_gn_supported"""
-    return ConvGNFn.apply(x, weight, bias, residual, gamma, beta, groups, eps, 1 if silu else 0)
 
 
 # --------------------------------------------------------------------------------------
@@ -931,8 +856,6 @@ def packed_upconv_weights(weight: torch.Tensor, bias):
 def upsample_conv_supported(x, weight):
     """bf16, channel counts the 256-square weight-gradient tiles divide, power-of-two images (the sampling / fp32 /
     odd-size cases take upsample2x + conv)"""
-    if os.environ.get("MDM_HIP_UPCONV", "1") == "0":   # development A/B switch
-        return False
     return x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and weight.dim() == 4 and weight.shape[2] == 3 and \
         weight.shape[0] % 256 == 0 and weight.shape[1] % 256 == 0 and x.shape[-1] == weight.shape[1] and \
         (x.shape[1] & (x.shape[1] - 1)) == 0 and (x.shape[2] & (x.shape[2] - 1)) == 0
@@ -1284,9 +1207,7 @@ class TextKVFn(torch.autograd.Function):
                                        _ptr_array([dcn[l] for l in idx]), len(idx), R, cout, D, _dt(cond), _stream()),
                 "mdm_linear_grouped"))
 
-        for cout, idx in groups.items():
-            if not _late_wgrad_first:   # (see SharedInputLinearsFn.backward: the weight gradients are handed over first)
-                dgrad(cout, idx)
+        for cout, idx in groups.items():   # (see SharedInputLinearsFn.backward: the weight gradients are handed over first)
             # weight / bias gradients: one grouped launch, into the gradient arena when there is one
             slots = [(_slot(ws[l]), _slot(bs[l])) for l in idx]
             sunk = all(a is not None and b is not None for a, b in slots)
@@ -1311,9 +1232,8 @@ class TextKVFn(torch.autograd.Function):
                 go()
                 for k, l in enumerate(idx):
                     grads[4 * l + 2], grads[4 * l + 3] = dws[k], dbs[k]
-        if _late_wgrad_first:
-            for cout, idx in groups.items():
-                dgrad(cout, idx)
+        for cout, idx in groups.items():
+            dgrad(cout, idx)
         g32 = [_c(t.detach().float()) for t in lnw]
         nslots = [(_slot(lnw[l]), _slot(lnb[l])) for l in range(L)]
         nsunk = all(a is not None and b is not None for a, b in nslots)
@@ -1383,8 +1303,6 @@ class SharedInputLinearsFn(torch.autograd.Function):
         # gradients (side stream) are handed over BEFORE the input-gradient launches, so that they wait for what precedes
         # those, not for them (the hand-off makes the side stream wait for everything queued on the main stream so far).
         for cout, idx in groups.items():
-            if not _late_wgrad_first:
-                dgrad(cout, idx)
             slots = [(_slot(ws[l]), _slot(bs[l])) for l in idx]
             sunk = all(a is not None and b is not None for a, b in slots)
             if sunk:
@@ -1407,9 +1325,8 @@ class SharedInputLinearsFn(torch.autograd.Function):
                 go()
                 for k, l in enumerate(idx):
                     grads[2 * l], grads[2 * l + 1] = dws[k], dbs[k]
-        if _late_wgrad_first:
-            for cout, idx in groups.items():
-                dgrad(cout, idx)
+        for cout, idx in groups.items():
+            dgrad(cout, idx)
         dx = dxs[0] if L == 1 else torch.stack(dxs).sum(0)
         return (dx,) + tuple(grads)
 

@@ -310,11 +310,6 @@ def train_batch(model, sample, optimizer, scheduler, logger, args, grad_scaler=N
     return loss_val, losses, times, x_t, means, targets
 
 
-# the loss is read AFTER backward and the optimizer tail are queued (0: where the reference reads it, before backward --
-# the host then cannot queue the backward until the forward has drained; A/B switch, HISTORY.md section 6.1)
-_LATE_LOSS_READ = os.environ.get("MDM_HIP_EARLY_LOSS_SYNC", "0") != "1"
-
-
 def _train_batch_fused(st, model, sample, optimizer, scheduler, logger, args, accumulate_gradient, num_grad_accumulations,
                        ema_model, loss_factor, lr, fp16):
     """The fused path of `train_batch`.  Same observable sequence as the reference (trainer.py:27-96), but the host never
@@ -337,13 +332,9 @@ def _train_batch_fused(st, model, sample, optimizer, scheduler, logger, args, ac
         loss = _loss_of(losses, weights)
         if fp16:
             loss = loss * loss_factor          # (the reference's fp32 branch has no loss_factor, trainer.py:58-63)
-        if _LATE_LOSS_READ:
-            st.post_scalar("loss", loss)
-            loss_val = None
-        else:
-            loss_val = loss.item()
-            if math.isnan(loss_val) and not lockstep:
-                return _fused_nan_return(st, optimizer, scheduler, fp16, loss_val, losses, times, x_t, means, targets, True)
+        # the loss is read AFTER backward and the optimizer tail are queued (where the reference reads it, before backward,
+        # the host could not queue the backward until the forward has drained; HISTORY.md section 6.1)
+        st.post_scalar("loss", loss)
         if fp16 and num_grad_accumulations != 1:
             loss = loss / num_grad_accumulations
     st.reducer.mark("bw0")
@@ -361,8 +352,7 @@ def _train_batch_fused(st, model, sample, optimizer, scheduler, logger, args, ac
                           decay, torch.bfloat16 if fp16 else torch.float32, loss=loss)
         optimizer._opt_called = True   # the step happened (silences lr_scheduler's call-order warning)
         skip_flag = st.post_skip_flag()
-    if loss_val is None:
-        loss_val = st.read_scalar("loss")
+    loss_val = st.read_scalar("loss")
     if not lockstep and math.isnan(loss_val):
         # the device has skipped the update and cleared the arena (final micro-step), or the arena holds this micro-step's
         # NaNs on top of the earlier micro-steps' gradients, which the reference drops too (trainer.py:39, 66)

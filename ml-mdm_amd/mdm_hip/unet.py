@@ -93,9 +93,6 @@ def zero_module(module):
     return module
 
 
-_SKIP_TAP = os.environ.get("MDM_HIP_SKIP_TAP", "1") != "0"   # A/B switch of the skip-gradient pass-through (ResNet.forward)
-
-
 def compute_dtype() -> torch.dtype:
     """bf16 under ``torch.autocast`` (the reference's ``fp16: 1`` path, trainer.py:29-30) or
     when MDM_HIP_DTYPE=bf16; otherwise exact fp32."""
@@ -130,7 +127,7 @@ class ResNet(nn.Module):
         pass-through output of norm1, so that in backward the skip connection's gradient reaches x inside the
         GroupNorm kernel instead of through an accumulation kernel of the autograd engine."""
         g = self.config.num_groups_norm
-        if tap is not None and x.requires_grad and tap[0][tap[1]] is x and _SKIP_TAP:
+        if tap is not None and x.requires_grad and tap[0][tap[1]] is x:
             h, x, tap[0][tap[1]] = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=2)
         else:
             h, x = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=True)
@@ -227,11 +224,6 @@ class SelfAttention(nn.Module):
                 kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
         a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
         a = a.reshape(N, H, W, C)
-        if self.ffn is not None and ops.conv_gn_enabled() and ops.conv_gn_supported(a, self.proj_out.weight, self.ffn[0].weight, 32):
-            # proj_out and the GroupNorm that opens the FFN in one launch (the norm's statistics need exactly what a
-            # 256-pixel x 8-group output tile of the convolution holds)
-            x, fn = ops.conv_gn(a, self.proj_out.weight, self.proj_out.bias, x, self.ffn[0].weight, self.ffn[0].bias, 32, self.ffn[0].eps)
-            return ops.ffn(fn, self.ffn[1].weight, self.ffn[1].bias, self.ffn[3].weight, self.ffn[3].bias, residual=x)
         x = ops.conv(a, self.proj_out.weight, self.proj_out.bias, residual=x)
         if self.ffn is not None:
             fn, x = ops.group_norm(x, self.ffn[0].weight, self.ffn[0].bias, 32, self.ffn[0].eps, passthrough=True)

@@ -9,7 +9,7 @@ import torch
 import parity_cases as PC
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_abi6():
     from mdm_hip import _lib
 
     protos = _lib.header_prototypes()
@@ -20,7 +20,7 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(handle, n), n
     L = _lib.lib()
-    assert L.mdm_abi_version() == _lib.ABI_VERSION == 5
+    assert L.mdm_abi_version() == _lib.ABI_VERSION == 6
 
 
 def test_plan_functions_are_host_only():

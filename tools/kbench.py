@@ -107,7 +107,7 @@ def main():
                 ys = [torch.empty(B, H, H, cout, device=dev, dtype=DT) for _ in range(ring)]
                 from mdm_hip import _lib
                 byte = DT == torch.bfloat16 and _lib.lib().mdm_dev_ffn_aux_bytes() == 1   # gelu' as a byte code (round 6)
-                yps = [torch.empty(B, H, H, cout * (2 if os.environ.get('KB_KNOB3_UNUSED') else 1), device=dev, dtype=torch.uint8 if byte else DT) for _ in range(ring)] if act == 1 else [None] * ring
+                yps = [torch.empty(B, H, H, cout, device=dev, dtype=torch.uint8 if byte else DT) for _ in range(ring)] if act == 1 else [None] * ring
                 if act == 2 and byte:
                     auxs = [torch.randint(3, 250, (B, H, H, cout), device=dev, dtype=torch.uint8) for _ in range(ring)]
                 else:
@@ -120,38 +120,12 @@ def main():
                         ops._conv_launch(x, wf, bp, auxs[j], None, ys[j], None, B, H, H, cin, H, H, cout, 1, 1, 0, 0, kbf)
                     else:
                         ops._conv_launch(x, wf, bp if act != 2 else None, None, auxs[j], ys[j], yps[j], B, H, H, cin, H, H, cout, 1, 1, 0, act, kbf)
-                if os.environ.get("KB_KNOB3_UNUSED"):
-                    _lib.lib().mdm_dev_set_knob(3, int(os.environ["KB_KNOB3_UNUSED"]))
                 t = timeit(one, iters=3 * ring)
                 it[0] = 0
                 t1 = timeit(lambda: (it.__setitem__(0, 0), one())[1], iters=3 * ring)
                 out_mb = (ys[0].numel() * 2 + (yps[0].numel() * yps[0].element_size() if act == 1 else 0)) / 1e6
                 print("%-20s act=%d out %6.0f MB  fresh buffers %7.1f us %6.0f TF | same buffer %7.1f us %6.0f TF" % (
                     name, act, out_mb, t * 1e6, flops / t / 1e12, t1 * 1e6, flops / t1 / 1e12), flush=True)
-    if what in ("stores",):
-        # what the store phase of the 1x1 GEMMs costs: the same launch with the epilogue's global stores skipped (dev knob 1)
-        from mdm_hip import _lib
-        L = _lib.lib()
-        for idx, (name, H, cin, cout, ks, stride) in enumerate(SHAPES):
-            if ks != 1:
-                continue
-            for act in (0, 1):
-                if act == 1 and cout < cin * 2:
-                    continue
-                x = torch.randn(B, H, H, cin, device=dev).to(DT)
-                w = (torch.randn(cout, cin, 1, 1, device=dev) / cin ** 0.5)
-                wf, wd, bp, cin_p, cout_p, kbf, kbd = ops.packed_weight(w, torch.randn(cout, device=dev), DT)
-                y = torch.empty(B, H, H, cout, device=dev, dtype=DT)
-                ypre = torch.empty_like(y) if act == 1 else None
-                flops = 2.0 * B * H * H * cout * cin
-                line = "%-20s act=%d tile=%d " % (name, act, L.mdm_conv_fwd_tile(B * H * H, cout, 1))
-                for tile in (0, 128128):
-                    for knob1 in (0, 1):
-                        L.mdm_dev_set_knob(2, tile); L.mdm_dev_set_knob(1, knob1)
-                        t = timeit(lambda: ops._conv_launch(x, wf, bp, None, None, y, ypre, B, H, H, cin, H, H, cout, 1, 1, 0, act, kbf), iters=20)
-                        line += " | %s %s %6.1f us %5.0f TF" % ("128x128" if tile else "model  ", "nostore" if knob1 else "store  ", t * 1e6, flops / t / 1e12)
-                L.mdm_dev_set_knob(2, 0); L.mdm_dev_set_knob(1, 0)
-                print(line, flush=True)
     if what in ("grouped",):
         G = int(os.environ.get("KB_GROUPS", "26"))
         for name, H, cin, cout, ks, stride in SHAPES:
