@@ -310,6 +310,34 @@ int mdm_input_stage(const void* u8_nhwc, float* out_nchw, int B, int H, int W, v
 int mdm_dropout(const void* x, void* y, size_t n, float p, unsigned long long seed, unsigned long long offset, int dtype,
                 void* stream);
 
+/* ---- frozen T5 v1.1 / flan text encoder over PACKED tokens (pure additions: no exported signature changed) ------------
+ * replaces T5Encoder.forward = T5ForConditionalGeneration.encoder (language_models/factory.py:14-38) as LanguageModel
+ * calls it on every batch (factory.py:84-101), eval mode; the seven projections of a layer are mdm_conv_fwd launches.
+ * A batch [B, S] with a 0/1 mask (holes allowed) is run on its T valid tokens only, row after row:
+ *   seq_start [B + 1] (int) first packed token of each row, seq_start[B] = T;  pos [T] (int) a token's ORIGINAL index in
+ *   its row (what the relative bias is taken over: padded keys never reach a valid query, factory.py:101 zeroes the rest).
+ * The residual stream x [T, D] is always fp32; h / delta / qkv / out are of `dtype` (MDM_F32 | MDM_BF16); D % 8 == 0.
+ *   mdm_t5_embed_rms   x[t] = table[ids[t]] (fp32 [vocab, D]; ids clamped to the table);  h[t] = rms(x[t]; ln_w)
+ *                      rms(x; w) = w * x * rsqrt(mean(x^2) + eps): no mean subtraction, no bias, statistics in fp32
+ *   mdm_t5_add_rms     x[t] += delta[t] (delta: a GEMM output, or NULL);  h[t] = rms(x[t]; ln_w)
+ *   mdm_t5_final_rms   out [R = B * S, D] fp32: row r = rms(x[s] + delta[s]; ln_w) with s = src[r], exact zeros where
+ *                      src[r] < 0 (the padded positions); x is not modified
+ *   mdm_t5_gated_gelu  y [T, F] = gelu_new(u[:, :F]) * u[:, F:] for u [T, 2F], the output of ONE GEMM over Wi0 | Wi1;
+ *                      gelu_new(u) = 0.5 u (1 + tanh(sqrt(2 / pi) (u + 0.044715 u^3))); F % 8 == 0
+ *   mdm_t5_attn_fwd    out [T, H d] = softmax(q k^T + bias_table[h][pos_k - pos_q + S - 1]) v per row and head, with NO
+ *                      1 / sqrt(d) scaling; qkv [T, 3 H d] = (q | k | v), bias_table [H][2 S - 1] fp32.  d must be 64,
+ *                      S <= 512; max_len (<= S) = the longest row (it sizes the grid: S is always a valid value).
+ *                      Scores and softmax in fp32; nothing is saved for a backward pass (there is none). */
+int mdm_t5_embed_rms(const int* ids, const float* table, const float* ln_w, float* x, void* h, int T, int D, int vocab,
+                     float eps, int dtype, void* stream);
+int mdm_t5_add_rms(float* x, const void* delta, const float* ln_w, void* h, int T, int D, float eps, int dtype,
+                   void* stream);
+int mdm_t5_final_rms(const float* x, const void* delta, const float* ln_w, const int* src, float* out, int R, int D,
+                     float eps, int dtype, void* stream);
+int mdm_t5_gated_gelu(const void* u, void* y, int T, int F, int dtype, void* stream);
+int mdm_t5_attn_fwd(const void* qkv, const int* seq_start, const int* pos, const float* bias_table, void* out, int B,
+                    int T, int S, int max_len, int H, int d, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

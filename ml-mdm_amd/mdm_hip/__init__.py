@@ -10,6 +10,8 @@ Layout of the package
   configs.py      the three shipped architectures (cc12m 64 / 256 / 1024)
   distributed.py  one-process-per-GPU data parallel gradient reducer over RCCL
   registry.py     plug into the reference's ml_mdm.config registries when present
+  text_encoder.py T5Encoder / LanguageModel: the frozen flan-T5 text encoder on packed tokens (mirror of
+                  ml_mdm.language_models.factory)
 """
 import os as _os
 
@@ -29,6 +31,7 @@ from .nested_unet import (  # noqa: E402  # noqa: F401
     NestedUNet,
     NestedUNetConfig,
 )
+from .text_encoder import LanguageModel, T5Encoder, T5EncoderConfig  # noqa: F401,E402
 from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
 
 __all__ = [
@@ -40,4 +43,7 @@ __all__ = [
     "Nested2UNetConfig",
     "Nested3UNetConfig",
     "Nested4UNetConfig",
+    "T5Encoder",
+    "T5EncoderConfig",
+    "LanguageModel",
 ]

@@ -418,10 +418,12 @@ def _round_up(v, m):
     return (v + m - 1) // m * m
 
 
-def packed_weight(weight: torch.Tensor, bias, dtype: torch.dtype):
+def packed_weight(weight: torch.Tensor, bias, dtype: torch.dtype, forward_only: bool = False):
     """(w_fwd, w_dgrad, bias_padded, Cin_pad, Cout_pad) for a reference-layout weight
-    ``(Cout, Cin, k, k)`` or ``(Cout, Cin)``; refreshed when the parameter version changes."""
-    key = dtype
+    ``(Cout, Cin, k, k)`` or ``(Cout, Cin)``; refreshed when the parameter version changes.
+    ``forward_only``: no input-gradient copy is built (w_dgrad is None) -- for a model that never runs backward (the
+    frozen text encoder: the second copy of flan-t5-xl's weights would be 2.4 GB); cached apart from the default pack."""
+    key = (dtype, "fwd") if forward_only else dtype
     ent = _cache_slot(weight)
     ver = (weight._version, None if bias is None else bias._version, weight.data_ptr(), _pack_epoch)
     if key in ent and ent[key][0] == ver:
@@ -434,7 +436,7 @@ def packed_weight(weight: torch.Tensor, bias, dtype: torch.dtype):
     cin_pad, cout_pad = _round_up(cin, epv), _round_up(cout, epv)
     taps = ks * ks
     w32 = _c(weight.detach().float())
-    need_d = cin_pad == cin
+    need_d = cin_pad == cin and not forward_only
     prev = ent[key][1] if key in ent else None   # re-pack into the same buffers: their addresses stay valid (repack_all table)
     if prev is not None and prev[0].numel() == cout_pad * taps * cin_pad and prev[0].device == weight.device:
         wf, wd = prev[0], prev[1]
