@@ -271,6 +271,21 @@ int mdm_adamw_ema_step(float* p, float* g, float* m, float* v, float* ema, const
  *     mode 0 (ddim_eta None): x_last = x0 beta sqrt(gl) / (1-g) + x_t sqrt(alpha) (1-gl) / (1-g)
  *     mode 1: eps = (x_t - x0 sqrt(g)) / sqrt(1-g); x_last = x0 sqrt(gl) + eps sqrt(1 - gl - eta^2 beta~) (eta = 0: no noise)
  *     need_noise: x_last += sqrt(beta~) * noise_gate[0] * n, n = noise[] if given, else drawn from rng_state
+ * mdm_sampler_step_2m (a pure addition, no reference line: the reference has only the two first-order solvers above):
+ *   one step of DPM-Solver++(2M) -- Lu, Zhou, Bao, Chen, Li, Zhu 2022, "DPM-Solver++: Fast Solver for Guided Sampling
+ *   of Diffusion Probabilistic Models", the multistep second-order solver on the data prediction (their Algorithm 2).
+ *   With g = gamma (current), gl = gamma_last (target), gp = gamma_prev (where x0_prev was formed), alpha = sqrt(gamma),
+ *   sigma = sqrt(1 - gamma), lambda = log(alpha / sigma), h = lambda_gl - lambda_g, h_prev = lambda_g - lambda_gp:
+ *     p, x0: as mdm_sampler_step, clip 0 / 1 / 2 (same units: x0 is divided by image_scale again after the clip)
+ *     second = x0_prev && order_gate && order_gate[0] != 0
+ *     D   = second ? (1 + h / (2 h_prev)) x0 - (h / (2 h_prev)) x0_prev : x0
+ *     x_last = (sigma_gl / sigma_g) x_t + (alpha_gl - sigma_gl alpha_g / sigma_g) D        (= -alpha_gl expm1(-h) D)
+ *   x0 goes to x0_out (the next step's x0_prev), x_last to x_last_out.  order_gate is a DEVICE float[1], like noise_gate:
+ *   one captured graph serves every step of a trajectory.  The flag SELECTS: with it off no logarithm is evaluated and
+ *   x0_prev is not read, so the last step of a schedule (gl == 1: sigma = 0, h = inf, x_last = x0) is exact whatever
+ *   x0_prev holds; the caller clears it on the first step (no history) and on the last.  Second order needs gl < 1 and
+ *   gp < g.  x0_out MAY alias x0_prev (every thread reads its elements of x0_prev before it writes them); x_last_out may
+ *   alias neither.  Dynamic thresholding: mdm_sampler_step(clip = 3) -> quantile -> this entry with clip = 2 and thr.
  * mdm_noise_images (N3, samplers.py:244-246): x_t = sqrt(g) images inv_scale + sqrt(1-g) eps; eps == NULL draws it
  *   from rng_state and stores it to eps_out.
  * mdm_diffusion_loss_fwd / _bwd (N3, diffusion.py:144-168 + samplers.py:266-279, 347-390): loss[b] = mean over chw of
@@ -288,6 +303,10 @@ int mdm_sampler_step(const float* x_t, const float* pred, const float* pred_unco
                      const unsigned long long* rng_state, int rng_stream, float* x0_out, float* x_last_out, int B,
                      size_t chw, int pred_type, int mode, float ddim_eta, int need_noise, int clip, float image_scale,
                      void* stream);
+int mdm_sampler_step_2m(const float* x_t, const float* pred, const float* pred_uncond, float guidance,
+                        const float* gamma, const float* gamma_last, const float* gamma_prev, const float* order_gate,
+                        const float* thr, const float* x0_prev, float* x0_out, float* x_last_out, int B, size_t chw,
+                        int pred_type, int clip, float image_scale, void* stream);
 int mdm_noise_images(const float* images, const float* eps, const float* gamma, float inv_scale, float* x_t,
                      float* eps_out, const unsigned long long* rng_state, int rng_stream, int B, size_t chw,
                      void* stream);

@@ -126,6 +126,64 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(StepArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models",
+// multistep, data prediction) on a [B, chw] image: same guidance combine, x0 and clip as above, then
+//   D = second ? x0 + r (x0 - x0_prev) : x0,   r = h / (2 h_prev)
+//   x_s = (sigma_s / sigma_t) x_t + (alpha_s - sigma_s alpha_t / sigma_t) D
+// with alpha = sqrt(gamma), sigma = sqrt(1 - gamma), lambda = log(alpha / sigma).  The differences of lambda are
+// taken without cancellation: 2 (lambda_s - lambda_t) = log(g_s (1 - g_t) / (g_t (1 - g_s))) = log1p((g_s - g_t) /
+// (g_t (1 - g_s))).  `second` is uniform over the launch (order_gate[0]); when it is off neither a logarithm nor
+// x0_prev is touched (the last step has gamma_s = 1: sigma_s = 0, h = inf, x_s = x0).  x0_out may alias x0_prev: a
+// thread reads its four elements of x0_prev before it writes them.
+// ---------------------------------------------------------------------------------------------------------
+struct Step2MArgs {
+  const float* x_t; const float* pred; const float* pred_uncond; float guidance;
+  const float* gamma; const float* gamma_last; const float* gamma_prev; const float* order_gate; const float* thr;
+  const float* x0_prev; float* x0_out; float* x_last_out;
+  size_t chw4; int B; int ptype, clip; float scale;
+};
+
+__global__ __launch_bounds__(256) void sampler_step_2m_kernel(Step2MArgs a) {
+  const size_t total4 = (size_t)a.B * a.chw4;
+  const bool second = a.x0_prev && a.gamma_prev && a.order_gate && a.order_gate[0] != 0.f;
+  for_each_vec4(total4, [&](size_t i) {
+    const int b = (int)(i / a.chw4);
+    const float g = a.gamma[b], gl = a.gamma_last[b];
+    const float sg = sqrtf(g), s1g = sqrtf(1.f - g);
+    const float cx = sqrtf(1.f - gl) / s1g;   // sigma_s / sigma_t
+    const float cd = sqrtf(gl) - cx * sg;     // alpha_s - sigma_s alpha_t / sigma_t
+    const f32x4 xt = reinterpret_cast<const f32x4*>(a.x_t)[i];
+    f32x4 p = reinterpret_cast<const f32x4*>(a.pred)[i];
+    if (a.pred_uncond) {
+      const f32x4 pu = reinterpret_cast<const f32x4*>(a.pred_uncond)[i];
+      p = pu + a.guidance * (p - pu);
+    }
+    float r = 0.f;
+    f32x4 xp = {0.f, 0.f, 0.f, 0.f};
+    if (second) {
+      const float gp = a.gamma_prev[b];
+      const float h2 = log1pf((gl - g) / (g * (1.f - gl)));    // 2 h
+      const float hp2 = log1pf((g - gp) / (gp * (1.f - g)));   // 2 h_prev
+      r = 0.5f * h2 / hp2;
+      xp = reinterpret_cast<const f32x4*>(a.x0_prev)[i];
+    }
+    const float thr = a.clip == 2 ? a.thr[b] : 1.f;
+    f32x4 x0, xl;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v = x0_of(xt[e], p[e], sg, s1g, a.ptype);
+      if (a.clip == 1) v = fminf(fmaxf(v * a.scale, -1.f), 1.f) / a.scale;
+      else if (a.clip == 2) v = fminf(fmaxf(v * a.scale, -thr), thr) / thr / a.scale;
+      x0[e] = v;
+      const float d = second ? v + r * (v - xp[e]) : v;
+      xl[e] = cx * xt[e] + cd * d;
+    }
+    reinterpret_cast<f32x4*>(a.x0_out)[i] = x0;
+    reinterpret_cast<f32x4*>(a.x_last_out)[i] = xl;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // N3 (a): x_t = sqrt(g) * images * inv_scale + sqrt(1 - g) * eps; eps given, or drawn here (and stored)
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void noise_images_kernel(const float* __restrict__ images, const float* __restrict__ eps_in,
@@ -391,6 +449,28 @@ extern "C" int mdm_sampler_step(const float* x_t, const float* pred, const float
   a.need_noise = need_noise; a.clip = clip; a.scale = image_scale;
   MDM_CHECK_ARG(!need_noise || (mode == 1 && ddim_eta <= 0.f) || noise || rng_state);
   hipLaunchKernelGGL(sampler_step_kernel, dim3(stream_blocks((size_t)B * a.chw4)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), a);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_sampler_step_2m(const float* x_t, const float* pred, const float* pred_uncond, float guidance,
+                                   const float* gamma, const float* gamma_last, const float* gamma_prev,
+                                   const float* order_gate, const float* thr, const float* x0_prev, float* x0_out,
+                                   float* x_last_out, int B, size_t chw, int pred_type, int clip, float image_scale,
+                                   void* stream) {
+  MDM_CHECK_ARG(x_t && pred && gamma && gamma_last && x0_out && x_last_out);
+  MDM_CHECK_ARG(B > 0 && chw > 0 && chw % 4 == 0);
+  MDM_CHECK_ARG(pred_type >= 0 && pred_type <= 2 && clip >= 0 && clip <= 2);
+  MDM_CHECK_ARG(clip != 2 || thr);
+  MDM_CHECK_ARG(image_scale > 0.f);
+  MDM_CHECK_ARG(!(order_gate && x0_prev) || gamma_prev);   // second order needs the gamma x0_prev was formed at
+  MDM_CHECK_ARG(x_last_out != x0_out && x_last_out != x0_prev);
+  Step2MArgs a;
+  a.x_t = x_t; a.pred = pred; a.pred_uncond = pred_uncond; a.guidance = guidance;
+  a.gamma = gamma; a.gamma_last = gamma_last; a.gamma_prev = gamma_prev; a.order_gate = order_gate; a.thr = thr;
+  a.x0_prev = x0_prev; a.x0_out = x0_out; a.x_last_out = x_last_out;
+  a.chw4 = chw / 4; a.B = B; a.ptype = pred_type == 2 ? PT_V : PT_EPS; a.clip = clip; a.scale = image_scale;
+  hipLaunchKernelGGL(sampler_step_2m_kernel, dim3(stream_blocks((size_t)B * a.chw4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
   MDM_LAUNCH_STATUS();
 }

@@ -14,11 +14,12 @@ batch the ~1500 kernel launches of one call are host-bound (Python + launch, wha
 Inference only (no autograd through a replay); parameters must not change between replays -- call ``reset()`` after
 loading a checkpoint (the packed kernel-layout weights baked into the graph would be stale otherwise).
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import ops
-from .samplers import NestedSampler, ThresholdType
+from .samplers import NestedSampler, ThresholdType, _check_solver
 
 
 class GraphedDenoiser(nn.Module):
@@ -88,7 +89,9 @@ class GraphedSampler:
 
     Semantics are those of ``Sampler._sample`` with ``resample_steps=True`` (reference samplers.py:516-609, 655-713):
     DDPM (``ddim_eta=None``) or DDIM(eta), classifier-free guidance, CLIP / NONE / DYNAMIC / DYNAMIC_IF thresholding (the
-    dynamic ones: x0 kernel -> ``torch.quantile`` -> update kernel, all inside the graph).  The ancestral noise comes
+    dynamic ones: x0 kernel -> ``torch.quantile`` -> update kernel, all inside the graph), or ``solver="dpmpp_2m"``
+    (DPM-Solver++(2M): deterministic, the x0 history of every scale lives in a static buffer that the step kernel updates
+    in place, the order flag of each step comes from a device table).  The ancestral noise comes
     from the library's counter-based generator (``ops.DeviceRng``, replayable on the host); the START noise is drawn
     like the eager path (CPU generator for the top scale, reference diffusion.py:177), or passed in."""
 
@@ -113,9 +116,16 @@ class GraphedSampler:
         # the last step adds no noise: Sampler tests `last != 0` (:421), NestedSampler `time_step != 1` (:700)
         gate = (t != 1) if nested else (s != 0)
         mk = lambda a, dt: torch.as_tensor(a.copy()).to(device=device, dtype=dt)
-        return mk(t, torch.long), mk(s, torch.long), mk(gate.astype("float32"), torch.float32)
+        # dpmpp_2m: the time of the step before (step 0 has none: its own, never used) and the order gate -- second order
+        # wherever there is history and a finite step in log-SNR, i.e. not on the first and not on the last step
+        # (0, 1, ..., 1, 0; all zeros for n <= 2)
+        p = np.concatenate((t[:1], t[:-1]))
+        order = np.zeros(len(t), dtype="float32")
+        order[1:-1] = (p[1:-1] > t[1:-1])
+        return (mk(t, torch.long), mk(s, torch.long), mk(gate.astype("float32"), torch.float32), mk(p, torch.long),
+                mk(order, torch.float32))
 
-    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros):
+    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None):
         smp, cfg = self.sampler, self.sampler._config
         model = self.pipe.get_model()
         vm = model.vision_model
@@ -123,10 +133,13 @@ class GraphedSampler:
         nested = isinstance(smp, NestedSampler)
         B = xs[0].shape[0]
         scales = (vm.nest_ratio + [1]) if nested else [1]
-        tab_t, tab_s, tab_gate = self._tables(n_steps, dev)
+        tab_t, tab_s, tab_gate, tab_p, tab_order = self._tables(n_steps, dev)
         idx = torch.zeros(1, dtype=torch.long, device=dev)
         rng = ops.DeviceRng(self._seed, dev)
         x_static = [x.clone() for x in xs]
+        # dpmpp_2m: the x0 of the step before, per scale.  Read only where the order gate is on, so what a warm-up pass or
+        # an earlier sample() call left in it is never seen: step 0 (gate off) rewrites it
+        x0_prev = [torch.zeros_like(x) for x in xs] if solver is not None else None
         micros_s = {k: v.clone() for k, v in micros.items()}   # micro-conditioning ([B] per key, diffusion.py:136-141): static inputs
         # the text path (lm_proj, masked mean, cond_emb) does not depend on t: computed once per sample() call into
         # static buffers, outside the per-step graph
@@ -139,7 +152,7 @@ class GraphedSampler:
         # the step kernel (x0 only, then the update with the threshold) -- torch.quantile is a sort + lerp on the
         # device, so it is captured with the rest
         dyn = {ThresholdType.DYNAMIC: (0.995, 100.0), ThresholdType.DYNAMIC_IF: (0.95, 1.5)}.get(fn)
-        noisy = not (ddim_eta is not None and ddim_eta <= 0)
+        noisy = solver is None and not (ddim_eta is not None and ddim_eta <= 0)
 
         def body():
             t = tab_t.index_select(0, idx)
@@ -150,6 +163,10 @@ class GraphedSampler:
                 g_t, g_s = smp.get_gammas(g_t, scales), smp.get_gammas(g_s, scales)
             else:
                 g_t, g_s = [g_t], [g_s]
+            if solver is not None:
+                order = tab_order.index_select(0, idx)
+                g_p = smp.gammas.index_select(0, tab_p.index_select(0, idx)).expand(B)
+                g_p = smp.get_gammas(g_p, scales) if nested else [g_p]
             times = (t - 1).expand(B)
             if guidance != 1:
                 xin = [torch.cat([x, x]) for x in x_static]
@@ -170,6 +187,13 @@ class GraphedSampler:
                     x0s, _ = ops.sampler_step(x, p, g_t[i], g_s[i], cfg.prediction_type, ddim_eta=ddim_eta, clip="X0_ONLY",
                                               image_scale=img_scale, pred_uncond=pu, guidance_scale=guidance)
                     thr = torch.quantile(x0s.reshape(B, -1).abs(), dyn[0], dim=1).clamp(min=1, max=dyn[1])
+                if solver is not None:
+                    _, x_last = ops.sampler_step_2m(x, p, g_t[i], g_s[i], cfg.prediction_type, g_prev=g_p[i],
+                                                    x0_prev=x0_prev[i], second_order=order, clip=clip, thr=thr,
+                                                    image_scale=img_scale, pred_uncond=pu, guidance_scale=guidance,
+                                                    x0_out=x0_prev[i])
+                    x.copy_(x_last)
+                    continue
                 _, x_last = ops.sampler_step(x, p, g_t[i], g_s[i], cfg.prediction_type, ddim_eta=ddim_eta, need_noise=noisy,
                                              rng=rng, clip=clip, thr=thr, image_scale=img_scale, pred_uncond=pu,
                                              guidance_scale=guidance, noise_gate=gate)
@@ -196,15 +220,17 @@ class GraphedSampler:
         # function; once freed, a later allocation reuses their memory and the replayed index_select reads garbage
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=n_steps, micros=micros_s,
-                   keep=(tab_t, tab_s, tab_gate))
+                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, x0_prev))
         self._graphs[key] = ent
         return ent
 
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
-               start_noise=None, seed=None):
+               start_noise=None, seed=None, solver=None):
         """-> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
-        guidance_scale=w)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the drawn x_T."""
+        guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
+        drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on)."""
+        _check_solver(solver, ddim_eta)
         self.pipe.eval()
         smp = self.sampler
         nested = isinstance(smp, NestedSampler)
@@ -228,8 +254,9 @@ class GraphedSampler:
         key = (tuple(tuple(x.shape) for x in xs), tuple(cond.shape), int(num_inference_steps), ddim_eta, float(guidance_scale),
                torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
                ops.fp32_split_enabled(),   # a captured graph keeps the arithmetic it was captured with
-               tuple(sorted((k, tuple(v.shape)) for k, v in micros.items())))
-        ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros)
+               tuple(sorted((k, tuple(v.shape)) for k, v in micros.items())), solver)
+        ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
+                                                   solver)
         for sx, x in zip(ent["x"], xs):
             sx.copy_(x)
         for k, v in micros.items():

@@ -1702,6 +1702,54 @@ def sampler_step(x_t, pred, g, g_last, prediction_type, ddim_eta=None, need_nois
     return x0, xl
 
 
+_ORDER_ON = {}   # device -> float[1] of 1.0: the order gate of an eager second-order step (no fill launch per step)
+
+
+def sampler_step_2m(x_t, pred, g, g_last, prediction_type, g_prev=None, x0_prev=None, second_order=False, clip="CLIP",
+                    image_scale=1.0, pred_uncond=None, guidance_scale=1.0, thr=None, x0_out=None):
+    """One DPM-Solver++(2M) update (Lu et al. 2022, multistep, data prediction; include/mdm_hip.h) as ONE kernel.
+    -> (x0, x_last).  ``second_order``: False / True, or a device float[1] gate (0 = first order) so that one captured
+    graph serves every step.  Second order needs ``x0_prev`` and ``g_prev`` (the x0 of the step before and the gamma
+    it was formed at).  ``x0_out`` may be ``x0_prev`` itself: the history is then updated in place.
+    ``clip``: "NONE" | "CLIP" | "DYNAMIC" (needs ``thr`` [B], from ``sampler_step(clip="X0_ONLY")`` + quantile)."""
+    x_t, pred = _img(x_t), _img(pred)
+    B = x_t.shape[0]
+    chw = x_t.numel() // B
+    g, gl = _vec(g, B), _vec(g_last, B)
+    pu = _img(pred_uncond) if pred_uncond is not None else None
+    th = _vec(thr, B) if thr is not None else None
+    cm = {"NONE": 0, "CLIP": 1, "DYNAMIC": 2}[clip]
+    gate = gp = xp = None
+    if torch.is_tensor(second_order):
+        gate = _c(second_order.detach().reshape(-1).float())
+        _require_gpu(gate)
+    elif second_order:
+        gate = _ORDER_ON.get(x_t.device)
+        if gate is None:
+            gate = _ORDER_ON[x_t.device] = torch.ones(1, dtype=torch.float32, device=x_t.device)
+    if gate is not None:
+        if x0_prev is None or g_prev is None:
+            raise _lib.MdmHipError("sampler_step_2m: second order needs x0_prev= and g_prev=")
+        xp, gp = _img(x0_prev), _vec(g_prev, B)
+        if xp.shape != x_t.shape:
+            raise _lib.MdmHipError("sampler_step_2m: x0_prev %s vs x_t %s" % (tuple(xp.shape), tuple(x_t.shape)))
+    if x0_out is None:
+        x0 = torch.empty_like(x_t)
+    else:
+        x0 = x0_out
+        _require_gpu(x0)
+        if x0.dtype != torch.float32 or not x0.is_contiguous() or x0.shape != x_t.shape:
+            raise _lib.MdmHipError("sampler_step_2m: x0_out must be a contiguous fp32 tensor shaped like x_t")
+    xl = torch.empty_like(x_t)
+    _lib.check(
+        _lib.lib().mdm_sampler_step_2m(_p(x_t), _p(pred), _p(pu), float(guidance_scale), _p(g), _p(gl), _p(gp), _p(gate),
+                                       _p(th), _p(xp), _p(x0), _p(xl), B, chw, _ptype(prediction_type), cm,
+                                       float(image_scale) if image_scale else 1.0, _stream()),
+        "mdm_sampler_step_2m",
+    )
+    return x0, xl
+
+
 def noise_images(images, g, eps=None, rng=None, rng_stream=0, inv_scale=1.0):
     """x_t = sqrt(g) * images * inv_scale + sqrt(1 - g) * eps (reference samplers.py:244-246).  ``eps=None`` draws the
     noise inside the kernel from ``rng``.  -> (x_t, eps)"""

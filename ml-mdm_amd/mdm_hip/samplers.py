@@ -13,6 +13,10 @@ with torch ops serve CPU tensors: that is what the host-logic tests drive agains
 reference's golden outputs (tests/test_diffusion_host.py), and what a custom ``clip_fn``
 gets.  One deliberate difference from the reference: gammas are per-sample ``[B, 1, 1, 1]``
 tensors, broadcast, instead of being materialised at full image size (:196-199).
+
+Beyond the reference: ``sample(..., solver="dpmpp_2m")`` replaces the first-order update by
+DPM-Solver++(2M) (Lu et al. 2022; ``get_prediction_xt_last_2m`` -> ``ops.sampler_step_2m``),
+same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.
 """
 import math
 from dataclasses import dataclass
@@ -97,6 +101,18 @@ def gammas_squaredcos_cap_v2(n):
 def _b(v):
     """[B] -> [B, 1, 1, 1]"""
     return v.reshape(-1, 1, 1, 1)
+
+
+SOLVERS = ("dpmpp_2m",)
+
+
+def _check_solver(solver, ddim_eta):
+    if solver is None:
+        return
+    if solver not in SOLVERS:
+        raise ValueError("unknown solver %r (known: %s; None = DDPM / DDIM)" % (solver, ", ".join(SOLVERS)))
+    if ddim_eta is not None:
+        raise ValueError("solver=%r is deterministic and takes no ddim_eta (got %r)" % (solver, ddim_eta))
 
 
 class Sampler(nn.Module):
@@ -225,6 +241,21 @@ class Sampler(nn.Module):
         x_t, pred = x_t.float(), pred.float()
         kw = dict(prediction_type=pt, ddim_eta=ddim_eta, image_scale=scale, guidance_scale=guidance_scale,
                   pred_uncond=None if pred_uncond is None else pred_uncond.float())
+        clip, thr = self._hip_clip(x_t, pred, g, g_last, use_clip_sample, scale, kw)
+        noisy = need_noise and not (ddim_eta is not None and ddim_eta <= 0)
+        noise = input_noise
+        if noisy and noise is None and self.device_rng is None:
+            noise = torch.randn_like(x_t)   # torch's generator, like the reference (:340)
+        x0, x_last = ops.sampler_step(x_t, pred, g, g_last, need_noise=noisy, noise=noise, rng=self.device_rng, clip=clip,
+                                      thr=thr, **kw)
+        if noisy and noise is None:
+            self.device_rng.advance(x_t.numel())
+        eps = (x_last - _b(g_last).sqrt() * x0) / (1 - _b(g_last)).sqrt() if return_eps else None
+        return x0, x_last, eps
+
+    def _hip_clip(self, x_t, pred, g, g_last, use_clip_sample, scale, kw):
+        """-> (clip mode of the step kernel, per-sample threshold or None); the dynamic thresholds cost one launch for
+        the unclipped x0 and the quantile"""
         fn = self._config.threshold_function if use_clip_sample else None
         thr, clip = None, "NONE"
         if fn in (ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF):
@@ -239,16 +270,48 @@ class Sampler(nn.Module):
             if scale != 1:
                 raise NotImplementedError("clip_fn=None with image_scale != 1 on the HIP path")
             clip = "CLIP"
-        noisy = need_noise and not (ddim_eta is not None and ddim_eta <= 0)
-        noise = input_noise
-        if noisy and noise is None and self.device_rng is None:
-            noise = torch.randn_like(x_t)   # torch's generator, like the reference (:340)
-        x0, x_last = ops.sampler_step(x_t, pred, g, g_last, need_noise=noisy, noise=noise, rng=self.device_rng, clip=clip,
-                                      thr=thr, **kw)
-        if noisy and noise is None:
-            self.device_rng.advance(x_t.numel())
-        eps = (x_last - _b(g_last).sqrt() * x0) / (1 - _b(g_last)).sqrt() if return_eps else None
-        return x0, x_last, eps
+        return clip, thr
+
+    # ---- one step of DPM-Solver++(2M) (not in the reference) ------------------------------------------
+    def get_prediction_xt_last_2m(self, x_t, pred, g, g_last, g_prev=None, x0_prev=None, second_order=False,
+                                  prediction_type=None, clip_fn=None, image_scale=None, pred_uncond=None,
+                                  guidance_scale=1):
+        """One update of DPM-Solver++(2M) (Lu et al. 2022, multistep, data prediction) -> (x0, x_last).
+
+        Guidance combine, x0 and threshold as ``get_prediction_xt_last``; then, with alpha = sqrt(gamma), sigma =
+        sqrt(1 - gamma), lambda = log(alpha / sigma), h = lambda(g_last) - lambda(g), h_prev = lambda(g) - lambda(g_prev),
+
+            D      = (1 + h / (2 h_prev)) x0 - (h / (2 h_prev)) x0_prev     if second_order else x0
+            x_last = (sigma_last / sigma) x_t + (alpha_last - sigma_last alpha / sigma) D
+
+        ``second_order`` must be off when there is no history (first step) and when ``g_last == 1`` (last step: h is
+        infinite; first order gives x_last = x0 there, as DDIM does).  First order is DDIM(eta = 0).  Gammas are
+        per-sample tensors and need not lie on the schedule.  GPU tensors take ``ops.sampler_step_2m`` (where
+        ``second_order`` may also be a device float[1] gate), CPU tensors the torch ops below."""
+        if x_t.is_cuda and (clip_fn is None or clip_fn == self.clip_sample):
+            pt = prediction_type or self._config.prediction_type
+            scale = 1 if image_scale is None else image_scale
+            x_t, pred = x_t.float(), pred.float()
+            kw = dict(prediction_type=pt, image_scale=scale, guidance_scale=guidance_scale,
+                      pred_uncond=None if pred_uncond is None else pred_uncond.float())
+            clip, thr = self._hip_clip(x_t, pred, g, g_last, clip_fn is not None, scale, kw)
+            return ops.sampler_step_2m(x_t, pred, g, g_last, g_prev=g_prev, x0_prev=x0_prev, second_order=second_order,
+                                       clip=clip, thr=thr, **kw)
+        if pred_uncond is not None:
+            pred = pred_uncond + guidance_scale * (pred - pred_uncond)
+        x0 = self.get_x0_eps_from_pred(x_t, pred, g, prediction_type=prediction_type, return_eps=False)
+        scale = 1 if image_scale is None else image_scale
+        x0 = torch.clip(x0, -scale, scale) / scale if clip_fn is None else clip_fn(x0, scale)
+        D = x0
+        if second_order:
+            # 2 (lambda_a - lambda_b) = log(a (1 - b) / (b (1 - a))) = log1p((a - b) / (b (1 - a))): no cancellation
+            h2 = torch.log1p((g_last - g) / (g * (1 - g_last)))
+            h2_prev = torch.log1p((g - g_prev) / (g_prev * (1 - g)))
+            r = 0.5 * h2 / h2_prev
+            D = x0 + r * (x0 - x0_prev)
+        ratio = ((1 - g_last) / (1 - g)).sqrt()
+        x_last = ratio * x_t + (g_last.sqrt() - ratio * g.sqrt()) * D
+        return x0, x_last
 
     def _threshold_sample(self, sample, ratio=0.995, max_value=100):
         """Imagen dynamic thresholding (:461-498)."""
@@ -284,12 +347,25 @@ class Sampler(nn.Module):
         return pred, None, extras
 
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
-                       guidance_scale=1, ddim_eta=None, return_details=False):
+                       guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
+                       second_order=False):
+        """``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is the caller's
+        dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
+        ``second_order`` (decided by the caller: off on the first and on the last step) uses it."""
+        _check_solver(solver, ddim_eta)
         ones = torch.ones(x_t.shape[0], dtype=torch.long, device=self.gammas.device)
         last = time_step - 1 if time_step_last is None else time_step_last
         t, s = ones * time_step, ones * last
         g, g_last = self.read_gamma(t), self.read_gamma(s)
         pc, pu, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
+        if solver is not None:
+            st = {} if solver_state is None else solver_state
+            x0, x_s = self.get_prediction_xt_last_2m(
+                x_t, pc, g, g_last, g_prev=st.get("g"), x0_prev=st.get("x0"), second_order=second_order,
+                prediction_type=self._config.prediction_type, clip_fn=self.clip_sample,
+                image_scale=self._config.rescale_signal, pred_uncond=pu, guidance_scale=guidance_scale)
+            st["x0"], st["g"] = x0, g
+            return (x0, x_s, (g, g_last)) if return_details else x_s
         x0, x_s, _ = self.get_prediction_xt_last(
             x_t, pc, g, g_last, prediction_type=self._config.prediction_type, need_noise=bool(last != 0),
             ddim_eta=ddim_eta, clip_fn=self.clip_sample, image_scale=self._config.rescale_signal, return_eps=False,
@@ -302,13 +378,18 @@ class Sampler(nn.Module):
         return (np.arange(0, num_inference_steps + 1) * ratio).round()[::-1].copy().astype(np.int64)
 
     def sample(self, *args, **kwargs):
+        """``solver=None``: ancestral DDPM, or DDIM with ``ddim_eta`` (the reference's two).  ``solver="dpmpp_2m"``:
+        DPM-Solver++(2M), deterministic, second order, one denoiser call per step -- made for few steps
+        (``resample_steps=True, num_inference_steps=20..50``)."""
+        _check_solver(kwargs.get("solver"), kwargs.get("ddim_eta"))   # here, not at the generator's first next()
         gen = self._sample(*args, **kwargs)
         return gen if kwargs.get("yield_output", False) else next(gen)
 
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
-                yield_output=False, **post_args):
+                yield_output=False, solver=None, **post_args):
         assert not (yield_output and return_sequence)
+        _check_solver(solver, ddim_eta)
         if not resample_steps:
             num_inference_steps = self.n_steps
         steps = torch.from_numpy(self.set_timesteps(num_inference_steps)).to(self.gammas.device)
@@ -316,10 +397,15 @@ class Sampler(nn.Module):
             steps = steps[steps <= t]
         seq = [x_t] if return_sequence else []
         x0 = extra = None
+        history = {}   # dpmpp_2m: x0 and gamma of the step before, per scale
         for i, ts in enumerate(steps[:-1]):
+            # second order needs history (not on the first step of this trajectory, wherever it starts) and a finite
+            # step in log-SNR (not on the last one: it goes to gamma = 1)
+            order = dict(solver=solver, solver_state=history, second_order=bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)) \
+                if solver is not None else {}
             x0, x_t, extra = self.get_xt_minus_1(
                 model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
-                guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True)
+                guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, **order)
             if yield_output:
                 yield self._postprocess(x_t, x0, extra, **post_args)
             if return_sequence:
@@ -373,7 +459,11 @@ class NestedSampler(Sampler):
         return list(p_t), [None] * len(p_t)
 
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
-                       guidance_scale=1, ddim_eta=None, return_details=False):
+                       guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
+                       second_order=False):
+        """``solver`` / ``solver_state`` / ``second_order`` as ``Sampler.get_xt_minus_1``; the history holds one x0 and
+        one gamma per scale"""
+        _check_solver(solver, ddim_eta)
         scales = model.vision_model.nest_ratio + [1]
         if isinstance(x_t, torch.Tensor):  # first step: draw independent noise at every lower resolution (:669-676)
             pyramid = [x_t]
@@ -388,6 +478,19 @@ class NestedSampler(Sampler):
         g_s = self.get_gammas(self.read_gamma(s), scales)
         pcs, pus = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
         x0, x_s = [], []
+        if solver is not None:
+            st = {} if solver_state is None else solver_state
+            x0_prev, g_prev = st.get("x0") or [None] * len(scales), st.get("g") or [None] * len(scales)
+            for x, pc, pu, g, gl, gp, xp, sc in zip(x_t, pcs, pus, g_t, g_s, g_prev, x0_prev, scales):
+                a, b = self.get_prediction_xt_last_2m(
+                    x, pc, g, gl, g_prev=gp, x0_prev=xp, second_order=second_order,
+                    prediction_type=self._config.prediction_type, clip_fn=self.clip_sample,
+                    image_scale=sc if not self._config.schedule_shifted else 1, pred_uncond=pu,
+                    guidance_scale=guidance_scale)
+                x0.append(a)
+                x_s.append(b)
+            st["x0"], st["g"] = x0, g_t
+            return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
         for x, pc, pu, g, gl, sc in zip(x_t, pcs, pus, g_t, g_s, scales):
             a, b, _ = self.get_prediction_xt_last(
                 x, pc, g, gl, prediction_type=self._config.prediction_type, need_noise=bool(time_step != 1),

@@ -1,9 +1,18 @@
 #!/usr/bin/env python
 """Sampling latency of the three shipped architectures, eager sampler vs GraphedSampler (one hipGraph replay per whole
 denoise iteration).  Development / reporting tool:
-   gpurun -- python tools/sample_bench.py [unet64|nested256|nested1024] [batch] [steps]"""
+   python tools/sample_bench.py [unet64|nested256|nested1024] [batch] [steps]
+
+With ``--solver dpmpp_2m``: the few-step solver against the first-order path it sits beside.  Two graphed legs, DDIM(eta = 0)
+and DPM-Solver++(2M), alternated call by call in ONE process (device events around every ``GraphedSampler.sample`` call of
+``steps`` iterations, ``--warmup`` calls first, ``--calls`` timed): ms per iteration as median, min, max and p10-p90.  Then
+the wall time of one ``--few``-step (25) 2M ``sample()`` next to one ``--many``-step (250) ancestral DDPM ``sample()``.
+   python tools/sample_bench.py nested1024 4 8 --solver dpmpp_2m [--calls 20] [--warmup 3] [--out FILE]
+   rocprofv3 --kernel-trace --stats -d DIR -- python tools/sample_bench.py unet64 4 8 --solver dpmpp_2m --calls 3 --many 0"""
+import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -17,10 +26,58 @@ from mdm_hip.graph import GraphedSampler  # noqa: E402
 from mdm_hip.testing import randomize_zero_params  # noqa: E402
 
 
+def solver_legs(pipe, smp, batch, side, dev, n_it, a):
+    """graphed DDIM(0) and graphed ``a.solver``, alternated; then few-step solver vs many-step DDPM wall time"""
+    gs = GraphedSampler(pipe, seed=7)
+    legs = {"ddim_eta0": dict(ddim_eta=0), a.solver: dict(solver=a.solver)}
+
+    def timed(**kw):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = gs.sample(batch, smp, side, dev, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    times, finite = {k: [] for k in legs}, True
+    for it in range(a.warmup + a.calls):
+        for k, kw in legs.items():
+            ms, out = timed(num_inference_steps=n_it, **kw)
+            if it >= a.warmup:
+                times[k].append(ms / n_it)
+            finite = finite and bool(torch.isfinite(out).all())
+    pct = lambda ts, q: sorted(ts)[min(len(ts) - 1, int(round(q * (len(ts) - 1))))]
+    res = {"ms_per_iteration": {k: {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4),
+                                    "p10_p90": [round(pct(ts, 0.1), 4), round(pct(ts, 0.9), 4)]} for k, ts in times.items()}}
+    lo, hi = res["ms_per_iteration"]["ddim_eta0"]["p10_p90"]
+    res["solver_median_inside_ddim_p10_p90"] = bool(lo <= res["ms_per_iteration"][a.solver]["median"] <= hi)
+    if a.many > 0:
+        wall = {}
+        for tag, kw in (("%s_%d_steps" % (a.solver, a.few), dict(solver=a.solver, num_inference_steps=a.few)),
+                        ("ddpm_%d_steps" % a.many, dict(num_inference_steps=a.many))):
+            timed(**kw)   # builds and warms the graph of this step count
+            ms, out = timed(**kw)
+            wall[tag] = round(ms, 2)
+            finite = finite and bool(torch.isfinite(out).all())
+        res["sample_wall_ms"] = wall
+    res["finite"] = finite
+    return res
+
+
 def main():
-    which = sys.argv[1] if len(sys.argv) > 1 else "nested1024"
-    batch = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-    n_it = int(sys.argv[3]) if len(sys.argv) > 3 else 8
+    ap = argparse.ArgumentParser()
+    ap.add_argument("which", nargs="?", default="nested1024", choices=["unet64", "nested256", "nested1024"])
+    ap.add_argument("batch", nargs="?", type=int, default=4)
+    ap.add_argument("steps", nargs="?", type=int, default=8)
+    ap.add_argument("--solver", default=None, choices=list(samplers.SOLVERS))
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--few", type=int, default=25)
+    ap.add_argument("--many", type=int, default=250, help="0: skip the wall-time comparison")
+    ap.add_argument("--out", default=None, help="append the result line to this file")
+    a = ap.parse_args()
+    which, batch, n_it = a.which, a.batch, a.steps
     dev = torch.device("cuda:0")
     sc = samplers.SamplerConfig(num_diffusion_steps=1000, schedule_type="DEEPFLOYD", prediction_type="V_PREDICTION",
                                 loss_target_type="DDPM", schedule_shifted=which != "unet64", rescale_signal=1 if which != "unet64" else None,
@@ -38,6 +95,14 @@ def main():
     pipe = pipe.to(dev)
     g = torch.Generator().manual_seed(1)
     smp = {"lm_outputs": torch.randn(batch, 32, 2048, generator=g).to(dev), "lm_mask": torch.ones(batch, 32).to(dev)}
+    if a.solver is not None:
+        res = {"model": which, "batch": batch, "steps_per_call": n_it, "calls": a.calls, "warmup": a.warmup,
+               "sampler": "GraphedSampler, CFG off, bf16, random weights"}
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            res.update(solver_legs(pipe, smp, batch, side, dev, n_it, a))
+        res["max_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2**30, 2)
+        emit(res, a.out)
+        return
     res = {"model": which, "batch": batch, "timed_steps": n_it, "sampler": "DDPM (ddim_eta=None), CFG off, bf16"}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         pipe.sampler.use_device_rng(7, dev)
@@ -56,7 +121,15 @@ def main():
         res["graphed_ms_per_step"] = round((time.perf_counter() - t0) / n_it * 1e3, 3)
     res["finite"] = bool(torch.isfinite(out).all() and torch.isfinite(out2).all())
     res["max_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2**30, 2)
+    emit(res, a.out)
+
+
+def emit(res, out):
     print(json.dumps(res), flush=True)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "a") as f:
+            f.write(json.dumps(res) + "\n")
 
 
 if __name__ == "__main__":
