@@ -286,6 +286,24 @@ int mdm_adamw_ema_step(float* p, float* g, float* m, float* v, float* ema, const
  *   x0_prev holds; the caller clears it on the first step (no history) and on the last.  Second order needs gl < 1 and
  *   gp < g.  x0_out MAY alias x0_prev (every thread reads its elements of x0_prev before it writes them); x_last_out may
  *   alias neither.  Dynamic thresholding: mdm_sampler_step(clip = 3) -> quantile -> this entry with clip = 2 and thr.
+ * mdm_sampler_known_blend (a pure addition, no reference line: the reference's Diffusion.partial_diffusion is dead code and
+ *   it has no known-region sampling): the replacement step of RePaint -- Lugmayr, Danelljan, Romero, Yu, Timofte, Van Gool
+ *   2022, "RePaint: Inpainting using Denoising Diffusion Probabilistic Models".  IN PLACE on x [B, C, H, W], the state at
+ *   noise level gamma[b]; known [B, C, H, W] in output units, mask [B, 1, H, W] in [0, 1] (broadcast over channels),
+ *   hw = H * W with hw % 4 == 0 (else an invalid-argument status):
+ *     k = sqrt(g) known inv_scale + sqrt(1 - g) n,   n = noise[] if given, else drawn from rng_state
+ *     x = (m == 0) ? x : (m == 1) ? k : m k + (1 - m) x
+ *   The mask SELECTS at 0 and 1: where m == 0 x keeps its bits (a 16-byte group whose mask is all zero is neither read nor
+ *   written), where m == 1 and g == 1 x = known inv_scale exactly.  The normals of 16-byte group i (over all B C hw / 4) are
+ *   counter block offset + i, as in mdm_noise_images: a draw is a function of position only, whatever the mask says.
+ *   x may alias neither known nor noise.  The caller advances the generator (by B C hw elements).
+ * mdm_sampler_jump (a pure addition, no reference line): the forward transition of RePaint's resampling jump, from level
+ *   gamma_s back to the noisier gamma_t (gamma_t <= gamma_s, per sample) on a [B, chw] image:
+ *     a = gamma_t / gamma_s
+ *     x_t = (jump_gate == NULL || jump_gate[0] != 0) ? sqrt(a) x_s + sqrt(max(1 - a, 0)) n : x_s
+ *   jump_gate is a DEVICE float[1], like noise_gate / order_gate (NULL = on): one captured graph serves every iteration.
+ *   The gate SELECTS: with it off no noise reaches the output.  x_t_out MAY alias x_s (every thread reads its elements
+ *   before it writes them); it may not alias noise.
  * mdm_noise_images (N3, samplers.py:244-246): x_t = sqrt(g) images inv_scale + sqrt(1-g) eps; eps == NULL draws it
  *   from rng_state and stores it to eps_out.
  * mdm_diffusion_loss_fwd / _bwd (N3, diffusion.py:144-168 + samplers.py:266-279, 347-390): loss[b] = mean over chw of
@@ -307,6 +325,12 @@ int mdm_sampler_step_2m(const float* x_t, const float* pred, const float* pred_u
                         const float* gamma, const float* gamma_last, const float* gamma_prev, const float* order_gate,
                         const float* thr, const float* x0_prev, float* x0_out, float* x_last_out, int B, size_t chw,
                         int pred_type, int clip, float image_scale, void* stream);
+int mdm_sampler_known_blend(float* x, const float* known, const float* mask, const float* gamma, float inv_scale,
+                            const float* noise, const unsigned long long* rng_state, int rng_stream, int B, int C,
+                            size_t hw, void* stream);
+int mdm_sampler_jump(const float* x_s, const float* gamma_t, const float* gamma_s, const float* noise,
+                     const float* jump_gate, const unsigned long long* rng_state, int rng_stream, float* x_t_out, int B,
+                     size_t chw, void* stream);
 int mdm_noise_images(const float* images, const float* eps, const float* gamma, float inv_scale, float* x_t,
                      float* eps_out, const unsigned long long* rng_state, int rng_stream, int B, size_t chw,
                      void* stream);

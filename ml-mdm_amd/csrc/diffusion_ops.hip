@@ -184,6 +184,72 @@ __global__ __launch_bounds__(256) void sampler_step_2m_kernel(Step2MArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Known-region sampling (the replacement method of RePaint, Lugmayr et al. 2022; not in the reference).  After a reverse
+// step has produced x at noise level gamma[b], the known pixels are replaced by the known image diffused to that level:
+//   k = sqrt(g) known inv_scale + sqrt(1 - g) n,   x = (m == 0) ? x : (m == 1) ? k : m k + (1 - m) x
+// on [B, C, H, W] with a [B, 1, H, W] mask.  The mask SELECTS at 0 and 1: a vec4 whose four mask values are 0 is neither
+// read nor written, and at m == 1, g == 1 the result is known * inv_scale exactly (1 * v + 0 * n).  hw % 4 == 0, so a
+// 16-byte access never straddles a channel plane or a mask row.  The normals of vec4 i are block offset + i whatever the
+// mask says (the indexing of noise_images_kernel).
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void known_blend_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                          const float* __restrict__ mask, const float* __restrict__ gamma,
+                                                          float inv_scale, const float* __restrict__ noise,
+                                                          const RngState* __restrict__ rng, uint32_t stream, int B, int C,
+                                                          size_t hw4) {
+  RngState st = {0ull, 0ull};
+  if (!noise) st = *rng;
+  const size_t chw4 = (size_t)C * hw4;
+  for_each_vec4((size_t)B * chw4, [&](size_t i) {
+    const size_t b = i / chw4;
+    const f32x4 m = reinterpret_cast<const f32x4*>(mask)[b * hw4 + (i - b * chw4) % hw4];
+    if (m[0] == 0.f && m[1] == 0.f && m[2] == 0.f && m[3] == 0.f) return;
+    const float g = gamma[b], sg = sqrtf(g), s1g = sqrtf(1.f - g);
+    const f32x4 kn = reinterpret_cast<const f32x4*>(known)[i];
+    f32x4 o = reinterpret_cast<const f32x4*>(x)[i];
+    float nz[4];
+    if (noise) { const f32x4 t = reinterpret_cast<const f32x4*>(noise)[i]; nz[0] = t[0]; nz[1] = t[1]; nz[2] = t[2]; nz[3] = t[3]; }
+    else normal4(st, i, stream, nz);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float k = sg * (kn[e] * inv_scale) + s1g * nz[e];
+      o[e] = m[e] == 0.f ? o[e] : (m[e] == 1.f ? k : m[e] * k + (1.f - m[e]) * o[e]);
+    }
+    reinterpret_cast<f32x4*>(x)[i] = o;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The forward transition of a resampling jump (RePaint section 4.2): from level gamma_s back to the noisier gamma_t,
+//   a = g_t / g_s,   x_t = sqrt(a) x_s + sqrt(max(1 - a, 0)) n
+// on a [B, chw] image.  jump_gate[0] (uniform over the launch; NULL = on) SELECTS: with it off x_t = x_s and no normal is
+// drawn.  x_t_out may alias x_s: a thread reads its four elements before it writes them.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void jump_kernel(const float* x_s, const float* __restrict__ gamma_t,
+                                                   const float* __restrict__ gamma_s, const float* __restrict__ noise,
+                                                   const float* __restrict__ jump_gate, const RngState* __restrict__ rng,
+                                                   uint32_t stream, float* x_t, int B, size_t chw4) {
+  const bool on = !jump_gate || jump_gate[0] != 0.f;
+  if (!on && x_t == x_s) return;
+  RngState st = {0ull, 0ull};
+  if (on && !noise) st = *rng;
+  for_each_vec4((size_t)B * chw4, [&](size_t i) {
+    f32x4 o = reinterpret_cast<const f32x4*>(x_s)[i];
+    if (on) {
+      const int b = (int)(i / chw4);
+      const float a = gamma_t[b] / gamma_s[b];
+      const float sa = sqrtf(a), s1a = sqrtf(fmaxf(1.f - a, 0.f));
+      float nz[4];
+      if (noise) { const f32x4 t = reinterpret_cast<const f32x4*>(noise)[i]; nz[0] = t[0]; nz[1] = t[1]; nz[2] = t[2]; nz[3] = t[3]; }
+      else normal4(st, i, stream, nz);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = sa * o[e] + s1a * nz[e];
+    }
+    reinterpret_cast<f32x4*>(x_t)[i] = o;
+  });
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // N3 (a): x_t = sqrt(g) * images * inv_scale + sqrt(1 - g) * eps; eps given, or drawn here (and stored)
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void noise_images_kernel(const float* __restrict__ images, const float* __restrict__ eps_in,
@@ -472,6 +538,31 @@ extern "C" int mdm_sampler_step_2m(const float* x_t, const float* pred, const fl
   a.chw4 = chw / 4; a.B = B; a.ptype = pred_type == 2 ? PT_V : PT_EPS; a.clip = clip; a.scale = image_scale;
   hipLaunchKernelGGL(sampler_step_2m_kernel, dim3(stream_blocks((size_t)B * a.chw4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_sampler_known_blend(float* x, const float* known, const float* mask, const float* gamma, float inv_scale,
+                                       const float* noise, const unsigned long long* rng_state, int rng_stream, int B,
+                                       int C, size_t hw, void* stream) {
+  MDM_CHECK_ARG(x && known && mask && gamma && B > 0 && C > 0 && hw > 0);
+  MDM_CHECK_ARG(hw % 4 == 0);
+  MDM_CHECK_ARG(noise || rng_state);
+  MDM_CHECK_ARG(x != known && x != noise);
+  hipLaunchKernelGGL(known_blend_kernel, dim3(stream_blocks((size_t)B * C * (hw / 4))), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, known, mask, gamma, inv_scale, noise,
+                     reinterpret_cast<const RngState*>(rng_state), (uint32_t)rng_stream, B, C, hw / 4);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_sampler_jump(const float* x_s, const float* gamma_t, const float* gamma_s, const float* noise,
+                                const float* jump_gate, const unsigned long long* rng_state, int rng_stream,
+                                float* x_t_out, int B, size_t chw, void* stream) {
+  MDM_CHECK_ARG(x_s && gamma_t && gamma_s && x_t_out && B > 0 && chw > 0 && chw % 4 == 0);
+  MDM_CHECK_ARG(noise || rng_state);
+  MDM_CHECK_ARG(x_t_out != noise);
+  hipLaunchKernelGGL(jump_kernel, dim3(stream_blocks((size_t)B * (chw / 4))), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), x_s, gamma_t, gamma_s, noise, jump_gate,
+                     reinterpret_cast<const RngState*>(rng_state), (uint32_t)rng_stream, x_t_out, B, chw / 4);
   MDM_LAUNCH_STATUS();
 }
 

@@ -148,6 +148,53 @@ class Diffusion(nn.Module):
         return self.sampler.sample(self.get_model(), noise, sample["lm_outputs"], sample["lm_mask"],
                                    self.get_micro_conditioning(sample), **kwargs)
 
+    def partial_diffusion(self, images, t, lm_outputs, lm_mask, device, return_sequence=False, micros={}, seed=0,
+                          noise_fn=None, graphed=None, **kwargs):
+        """Start a trajectory late, from ``images`` noised to schedule time ``t`` (SDEdit, Meng et al. 2022) -- the mirror
+        of the reference's ``Diffusion.partial_diffusion`` (diffusion.py:199-206, dead code there), made to work.  The
+        trajectory starts at the first step of the sampling schedule (``resample_steps`` / ``num_inference_steps`` as
+        ``sample``) that is <= t, and the images are noised to THAT step's gamma; t = 0 returns clip(images).  A nested
+        model gets the average-pooled pyramid with independent noise and its own (shifted) gamma per scale, as
+        ``get_loss`` builds it.  GPU tensors: ``ops.noise_images`` per scale, drawn from ``ops.DeviceRng(seed)`` on
+        stream 0 and advanced by ``numel`` per scale, hi -> lo; CPU tensors: the torch formula with ``noise_fn``
+        (default ``torch.randn_like``).  ``graphed``: a ``GraphedSampler`` of this pipeline -- the remaining steps are
+        replayed by it (``start_step``) instead of the eager sampler.  Other keywords go to ``sample`` (``ddim_eta``,
+        ``solver``, ``guidance_scale``, ``known_images`` ...)."""
+        self.eval()
+        smp, model = self.sampler, self.get_model()
+        n = kwargs.get("num_inference_steps", 2000) if kwargs.get("resample_steps", False) else smp.n_steps
+        steps = smp.set_timesteps(n)
+        if not (steps <= t).any():
+            raise ValueError("partial_diffusion: t = %r is below every step of the schedule" % (t,))
+        t0 = int(steps[steps <= t][0])
+        images = images.to(device)
+        hip = images.is_cuda
+        ratios, image_scales = smp._scale_info(model)
+        gammas = smp._scale_gammas(model, t0, images.shape[0])
+        pyr = [images.float() if hip else images]
+        for r in ratios[1:]:
+            pyr.append(ops.avgpool(pyr[0], r) if hip else F.avg_pool2d(pyr[0], r))
+        x_t = []
+        if hip:
+            rng = ops.DeviceRng(seed, images.device)
+            for img, g, sc in zip(pyr, gammas, image_scales):
+                x_t.append(ops.noise_images(img, g, rng=rng, inv_scale=1.0 / sc if sc else 1.0)[0])
+                rng.advance(img.numel())
+        else:
+            noise_fn = noise_fn or torch.randn_like
+            for img, g, sc in zip(pyr, gammas, image_scales):
+                x_t.append(samplers.Sampler.get_xt(smp, img / sc if sc else img, noise_fn(img), g))
+        nested = isinstance(smp, samplers.NestedSampler)
+        if graphed is not None:
+            if return_sequence or kwargs.get("yield_output", False):
+                raise ValueError("partial_diffusion(graphed=...) returns the final images only")
+            kw = {k: v for k, v in kwargs.items() if k not in ("resample_steps", "num_inference_steps")}
+            sample = dict(micros, lm_outputs=lm_outputs, lm_mask=lm_mask)
+            return graphed.sample(images.shape[0], sample, images.shape[-1], device, num_inference_steps=n, start_noise=x_t,
+                                  start_step=t0, **kw)
+        return smp.sample(model, x_t if nested else x_t[0], lm_outputs, lm_mask, micros, return_sequence=return_sequence,
+                          t=t0, **kwargs)
+
 
 class NestedModel(Model):
     def forward(self, x_t: List[torch.Tensor], times, lm_outputs, lm_mask, micros={}, mixed_ratio=None):

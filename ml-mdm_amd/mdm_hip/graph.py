@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .samplers import NestedSampler, ThresholdType, _check_solver
+from .samplers import NestedSampler, ThresholdType, _check_known, _check_solver
 
 
 class GraphedDenoiser(nn.Module):
@@ -93,7 +93,14 @@ class GraphedSampler:
     (DPM-Solver++(2M): deterministic, the x0 history of every scale lives in a static buffer that the step kernel updates
     in place, the order flag of each step comes from a device table).  The ancestral noise comes
     from the library's counter-based generator (``ops.DeviceRng``, replayable on the host); the START noise is drawn
-    like the eager path (CPU generator for the top scale, reference diffusion.py:177), or passed in."""
+    like the eager path (CPU generator for the top scale, reference diffusion.py:177), or passed in.
+
+    Image conditioning as in ``Sampler._sample``: ``known_images`` / ``known_mask`` live in static buffers and the body
+    ends with the blend kernel of every scale that has one, drawing from a second static generator; ``resample = r > 1``
+    repeats every row of the iteration tables but the last r times and ends the body with the jump kernel of every scale,
+    gated by a device table (1 on all but the last row of a group).  ``start_step`` starts the replay at the first row
+    whose time is <= it (the SDEdit start; ``start_noise`` then carries the noised image).  Without known images and
+    with resample == 1 the captured graph has no launch more than before."""
 
     def __init__(self, pipeline, warmup: int = 2, seed: int = 0):
         self.pipe = pipeline
@@ -109,7 +116,7 @@ class GraphedSampler:
         self._graphs.clear()
 
     # ---- host-side schedule ------------------------------------------------------------------------------
-    def _tables(self, n_steps, device):
+    def _tables(self, n_steps, device, resample=1):
         steps = self.sampler.set_timesteps(n_steps)                 # n+1 entries, descending, last = 0
         t, s = steps[:-1], steps[1:]
         nested = isinstance(self.sampler, NestedSampler)
@@ -122,10 +129,16 @@ class GraphedSampler:
         p = np.concatenate((t[:1], t[:-1]))
         order = np.zeros(len(t), dtype="float32")
         order[1:-1] = (p[1:-1] > t[1:-1])
+        # resample = r: every row but the last r times; the jump gate is on wherever the same row follows
+        reps = np.full(len(t), int(resample))
+        reps[-1] = 1
+        jump = np.ones(int(reps.sum()), dtype="float32")
+        jump[np.cumsum(reps) - 1] = 0
+        t, s, gate, p, order = (np.repeat(a, reps) for a in (t, s, gate, p, order))
         return (mk(t, torch.long), mk(s, torch.long), mk(gate.astype("float32"), torch.float32), mk(p, torch.long),
-                mk(order, torch.float32))
+                mk(order, torch.float32), mk(jump, torch.float32)), t
 
-    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None):
+    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1):
         smp, cfg = self.sampler, self.sampler._config
         model = self.pipe.get_model()
         vm = model.vision_model
@@ -133,9 +146,15 @@ class GraphedSampler:
         nested = isinstance(smp, NestedSampler)
         B = xs[0].shape[0]
         scales = (vm.nest_ratio + [1]) if nested else [1]
-        tab_t, tab_s, tab_gate, tab_p, tab_order = self._tables(n_steps, dev)
+        (tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump), t_host = self._tables(n_steps, dev, resample)
         idx = torch.zeros(1, dtype=torch.long, device=dev)
         rng = ops.DeviceRng(self._seed, dev)
+        # known-region sampling: static image / mask per scale that has one, and a generator of its own
+        kn_img = kn_mask = kn_inv = kn_rng = None
+        if known is not None:
+            kn_img = [None if k is None else k.clone() for k in known.images]
+            kn_mask = [None if m is None else m.clone() for m in known.masks]
+            kn_inv, kn_rng = known.inv_scales, ops.DeviceRng(0, dev)
         x_static = [x.clone() for x in xs]
         # dpmpp_2m: the x0 of the step before, per scale.  Read only where the order gate is on, so what a warm-up pass or
         # an earlier sample() call left in it is never seen: step 0 (gate off) rewrites it
@@ -200,6 +219,17 @@ class GraphedSampler:
                 if noisy:
                     rng.advance(x.numel())   # same draw order as the eager sampler with use_device_rng()
                 x.copy_(x_last)
+            if known is not None:   # blends hi -> lo, then jumps hi -> lo: the draw order of KnownRegion
+                for i, x in enumerate(x_static):
+                    if kn_img[i] is not None:
+                        ops.sampler_known_blend(x, kn_img[i], kn_mask[i], g_s[i], inv_scale=kn_inv[i], rng=kn_rng, rng_stream=1)
+                        kn_rng.advance(x.numel())
+                if resample > 1:
+                    jump = tab_jump.index_select(0, idx)
+                    for i, x in enumerate(x_static):
+                        ops.sampler_jump(x, g_t[i], g_s[i], rng=kn_rng, rng_stream=1, gate=jump, out=x)
+                        # the eager sampler advances only where it jumps
+                        kn_rng.state[1:2].add_((jump != 0).long() * ((x.numel() + 3) // 4))
             idx.add_(1)
 
         side = torch.cuda.Stream()
@@ -212,6 +242,8 @@ class GraphedSampler:
             # eager sampler after use_device_rng(seed)
             idx.zero_()
             rng.state.copy_(torch.tensor([self._seed & (2**63 - 1), 0], dtype=torch.int64))
+            if kn_rng is not None:
+                kn_rng.state.zero_()
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
@@ -219,18 +251,29 @@ class GraphedSampler:
         # everything the graph reads by raw pointer must outlive it: the schedule tables too (they are locals of this
         # function; once freed, a later allocation reuses their memory and the replayed index_select reads garbage
         # indices -> out-of-bounds gather)
-        ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=n_steps, micros=micros_s,
-                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, x0_prev))
+        ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
+                   t_host=t_host, order=tab_order, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
+                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev))
         self._graphs[key] = ent
         return ent
 
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
-               start_noise=None, seed=None, solver=None):
+               start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
+               start_step=None):
         """-> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
         guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
-        drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on)."""
+        drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on).
+        ``known_images`` / ``known_mask`` / ``resample`` / ``known_seed``: as ``Sampler._sample``; whether a scale has a
+        known image, and ``resample``, are part of the graph key.  ``start_step=t``: replay only the rows whose time is
+        <= t, from ``start_noise`` = the image noised to the first of them (``Diffusion.partial_diffusion(...,
+        graphed=self)`` does the noising); the first replayed row of ``dpmpp_2m`` is first order, as in the eager sampler."""
         _check_solver(solver, ddim_eta)
+        _check_known(known_images, resample, solver)
+        if known_mask is not None and known_images is None:
+            raise ValueError("known_mask without known_images")
+        if start_step is not None and start_noise is None:
+            raise ValueError("start_step needs start_noise: the image noised to that step")
         self.pipe.eval()
         smp = self.sampler
         nested = isinstance(smp, NestedSampler)
@@ -255,10 +298,19 @@ class GraphedSampler:
                torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
                ops.fp32_split_enabled(),   # a captured graph keeps the arithmetic it was captured with
                tuple(sorted((k, tuple(v.shape)) for k, v in micros.items())), solver)
+        known = None
+        if known_images is not None:
+            known = smp._known_region(model, xs, known_images, known_mask, known_seed, None)
+            key = key + (tuple(k is not None for k in known.images), int(resample))
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
-                                                   solver)
+                                                   solver, known, int(resample))
         for sx, x in zip(ent["x"], xs):
             sx.copy_(x)
+        if known is not None:
+            for dst, src in zip(ent["kn_img"] + ent["kn_mask"], known.images + known.masks):
+                if dst is not None:
+                    dst.copy_(src)
+            ent["kn_rng"].state.copy_(torch.tensor([known_seed & (2**63 - 1), 0], dtype=torch.int64))
         for k, v in micros.items():
             ent["micros"][k].copy_(v)
         ce, cs, cm = model.vision_model.forward_conditioning(cond, mask)
@@ -266,10 +318,23 @@ class GraphedSampler:
         ent["cs"].copy_(cs)
         if ent["cm"] is not None:
             ent["cm"].copy_(cm)
-        ent["idx"].zero_()
+        first = 0
+        if start_step is not None:
+            rows = np.nonzero(ent["t_host"] <= start_step)[0]
+            if start_step < 0:
+                raise ValueError("start_step = %r is below every step of the schedule" % (start_step,))
+            first = int(rows[0]) if len(rows) else ent["n"]   # t = 0: nothing left to replay
+        ent["idx"].fill_(first)
         if seed is not None:
             ent["rng"].state.copy_(torch.tensor([seed & (2**63 - 1), 0], dtype=torch.int64))
-        for _ in range(ent["n"]):
+        # dpmpp_2m from a late start: there is no history at the first replayed row -- its order gate is off for this call
+        order_row = ent["order"][first:first + 1] if (solver is not None and first > 0) else None
+        if order_row is not None:
+            saved = order_row.clone()
+            order_row.zero_()
+        for _ in range(ent["n"] - first):
             ent["graph"].replay()
+        if order_row is not None:
+            order_row.copy_(saved)
         out = [x.clone() for x in ent["x"]]
         return smp._postprocess(out if nested else out[0], clip=True)

@@ -1750,6 +1750,72 @@ def sampler_step_2m(x_t, pred, g, g_last, prediction_type, g_prev=None, x0_prev=
     return x0, xl
 
 
+def _inplace_img(t, like, what):
+    """an fp32, contiguous GPU tensor shaped like ``like`` that a kernel writes through its own pointer (no copy made)"""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != like.shape:
+        raise _lib.MdmHipError("%s must be a contiguous fp32 tensor of shape %s" % (what, tuple(like.shape)))
+    _require_gpu(t)
+    return t.detach()
+
+
+def sampler_known_blend(x, known, mask, g, inv_scale=1.0, noise=None, rng=None, rng_stream=1):
+    """Known-region replacement (RePaint, Lugmayr et al. 2022; include/mdm_hip.h) as ONE kernel, IN PLACE on ``x``
+    [B, C, H, W], the state at noise level ``g`` [B]:  k = sqrt(g) known inv_scale + sqrt(1 - g) n;  x = k where
+    ``mask`` [B, 1, H, W] is 1, untouched where it is 0, m k + (1 - m) x in between.  ``n`` is ``noise``, or drawn in
+    the kernel from ``rng`` (which the caller advances by ``x.numel()``, as for ``sampler_step``).  -> x"""
+    if x.dim() != 4:
+        raise _lib.MdmHipError("sampler_known_blend: x must be [B, C, H, W] (got %s)" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    if known.shape != x.shape:
+        raise _lib.MdmHipError("sampler_known_blend: known %s vs x %s" % (tuple(known.shape), tuple(x.shape)))
+    if tuple(mask.shape) != (B, 1, H, W):
+        raise _lib.MdmHipError("sampler_known_blend: mask must be %s (got %s)" % ((B, 1, H, W), tuple(mask.shape)))
+    if (H * W) % 4:
+        raise _lib.MdmHipError("sampler_known_blend: H * W must be a multiple of 4 (got %d x %d)" % (H, W))
+    x = _inplace_img(x, x, "sampler_known_blend: x")
+    known, mask = _img(known), _img(mask)
+    g = _vec(g, B)
+    nz = _img(noise) if noise is not None else None
+    if nz is not None and nz.shape != x.shape:
+        raise _lib.MdmHipError("sampler_known_blend: noise %s vs x %s" % (tuple(nz.shape), tuple(x.shape)))
+    if nz is None and rng is None:
+        raise _lib.MdmHipError("sampler_known_blend: give noise= or rng=")
+    _lib.check(
+        _lib.lib().mdm_sampler_known_blend(_p(x), _p(known), _p(mask), _p(g), float(inv_scale), _p(nz),
+                                           _p(rng.state) if nz is None else None, int(rng_stream), B, C, H * W, _stream()),
+        "mdm_sampler_known_blend",
+    )
+    return x
+
+
+def sampler_jump(x_s, g_t, g_s, noise=None, rng=None, rng_stream=1, gate=None, out=None):
+    """The forward transition of a resampling jump, level ``g_s`` back to the noisier ``g_t`` ([B] each), as ONE kernel:
+    x_t = sqrt(g_t / g_s) x_s + sqrt(1 - g_t / g_s) n.  ``gate``: a device float[1] (0 = x_t is x_s, no noise) so that
+    one captured graph serves every iteration; None = on.  ``out`` may be ``x_s`` itself.  The caller advances ``rng``.
+    -> x_t"""
+    x_s = _img(x_s)
+    B = x_s.shape[0]
+    chw = x_s.numel() // B
+    if chw % 4:
+        raise _lib.MdmHipError("sampler_jump: C * H * W must be a multiple of 4 (got %s)" % (tuple(x_s.shape),))
+    g_t, g_s = _vec(g_t, B), _vec(g_s, B)
+    nz = _img(noise) if noise is not None else None
+    if nz is not None and nz.shape != x_s.shape:
+        raise _lib.MdmHipError("sampler_jump: noise %s vs x_s %s" % (tuple(nz.shape), tuple(x_s.shape)))
+    if nz is None and rng is None:
+        raise _lib.MdmHipError("sampler_jump: give noise= or rng=")
+    if gate is not None:
+        gate = _c(gate.detach().reshape(-1).float())
+        _require_gpu(gate)
+    out = torch.empty_like(x_s) if out is None else _inplace_img(out, x_s, "sampler_jump: out")
+    _lib.check(
+        _lib.lib().mdm_sampler_jump(_p(x_s), _p(g_t), _p(g_s), _p(nz), _p(gate), _p(rng.state) if nz is None else None,
+                                    int(rng_stream), _p(out), B, chw, _stream()),
+        "mdm_sampler_jump",
+    )
+    return out
+
+
 def noise_images(images, g, eps=None, rng=None, rng_stream=0, inv_scale=1.0):
     """x_t = sqrt(g) * images * inv_scale + sqrt(1 - g) * eps (reference samplers.py:244-246).  ``eps=None`` draws the
     noise inside the kernel from ``rng``.  -> (x_t, eps)"""

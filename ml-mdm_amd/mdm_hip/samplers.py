@@ -16,7 +16,11 @@ tensors, broadcast, instead of being materialised at full image size (:196-199).
 
 Beyond the reference: ``sample(..., solver="dpmpp_2m")`` replaces the first-order update by
 DPM-Solver++(2M) (Lu et al. 2022; ``get_prediction_xt_last_2m`` -> ``ops.sampler_step_2m``),
-same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.
+same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.  So does image conditioning:
+``sample(..., known_images=, known_mask=, resample=, known_seed=)`` holds a region of every trajectory on a given image
+(the replacement method of RePaint, Lugmayr et al. 2022, with its resampling jumps; ``KnownRegion`` ->
+``ops.sampler_known_blend`` / ``ops.sampler_jump``), and ``Diffusion.partial_diffusion`` starts a trajectory late from a
+noised image (SDEdit, Meng et al. 2022).
 """
 import math
 from dataclasses import dataclass
@@ -113,6 +117,133 @@ def _check_solver(solver, ddim_eta):
         raise ValueError("unknown solver %r (known: %s; None = DDPM / DDIM)" % (solver, ", ".join(SOLVERS)))
     if ddim_eta is not None:
         raise ValueError("solver=%r is deterministic and takes no ddim_eta (got %r)" % (solver, ddim_eta))
+
+
+def _check_known(known_images, resample, solver):
+    if int(resample) != resample or resample < 1:
+        raise ValueError("resample must be an integer >= 1 (got %r)" % (resample,))
+    if resample > 1 and known_images is None:
+        raise ValueError("resample=%d repeats the steps around a known region: it needs known_images" % resample)
+    if resample > 1 and solver is not None:
+        raise ValueError("resample=%d with solver=%r: the multistep history is void after a jump" % (resample, solver))
+
+
+def known_blend(x, known, mask, g, inv_scale=1.0, noise=None):
+    """torch ops of ``ops.sampler_known_blend`` (for CPU tensors; not in place):  k = sqrt(g) known inv_scale +
+    sqrt(1 - g) n;  x where mask == 0, k where mask == 1, m k + (1 - m) x in between.  ``g`` broadcasts as [B, 1, 1, 1]."""
+    g = _b(g)
+    k = g.sqrt() * (known * inv_scale) + (1 - g).sqrt() * noise
+    return torch.where(mask == 0, x, torch.where(mask == 1, k, mask * k + (1 - mask) * x))
+
+
+def jump(x_s, g_t, g_s, noise):
+    """torch ops of ``ops.sampler_jump``: the forward transition from level g_s back to the noisier g_t"""
+    a = _b(g_t) / _b(g_s)
+    return a.sqrt() * x_s + (1 - a).clamp(min=0).sqrt() * noise
+
+
+def known_pyramid(known, mask, ratios):
+    """One top-scale image and mask -> hi->lo lists for the scales ``ratios`` (top side / side of the scale; ratios[0] == 1).
+    Images are average-pooled.  A lower-scale pixel is known only where EVERY pixel of its block is (mask == 1 there),
+    stored as 0 / 1 floats; the top scale keeps the mask it was given, fractions included."""
+    hip = known.is_cuda
+    pool = (lambda x, r: ops.avgpool(x.float().contiguous(), r)) if hip else F.avg_pool2d
+    ks, ms = [known], [mask]
+    full = (mask == 1).to(known.dtype)
+    for r in ratios[1:]:
+        ks.append(pool(known, r))
+        # the block mean of a 0 / 1 image is 1 only where all r * r are 1: the next value below is 1 - 1 / r^2
+        ms.append((pool(full, r) > 1 - 0.5 / (r * r)).to(known.dtype))
+    return ks, ms
+
+
+class KnownRegion:
+    """The known images of one ``sample()`` call: per scale (hi -> lo) an image [B, C, H, W] in output units ([-1, 1]), a mask
+    [B, 1, H, W] in [0, 1] and 1 / image_scale of that scale, or None where the scale is free; plus the source of the
+    known-region noise.  GPU tensors: one ``ops.DeviceRng(seed)`` of its own, drawn in the kernels on stream 1 and advanced
+    by ``numel`` after every launch -- it never touches the ancestral-noise generator or torch's global one.  CPU tensors:
+    ``noise_fn(x)`` if given (called once per blend / jump, in launch order), else a private ``torch.Generator`` seeded
+    with ``seed``.  Within one iteration: blends hi -> lo, then jumps hi -> lo."""
+
+    def __init__(self, images, masks, inv_scales, seed=0, noise_fn=None):
+        self.images, self.masks, self.inv_scales = images, masks, inv_scales
+        self.noise_fn = noise_fn
+        first = next(k for k in images if k is not None)
+        self.hip = first.is_cuda
+        if self.hip:
+            self.rng = ops.DeviceRng(seed, first.device)
+        elif noise_fn is None:
+            gen = torch.Generator().manual_seed(int(seed) & (2**63 - 1))
+            self.noise_fn = lambda x: torch.randn(x.shape, generator=gen, dtype=x.dtype)
+
+    @staticmethod
+    def build(x_shapes, device, dtype, known_images, known_mask, ratios, image_scales, seed=0, noise_fn=None):
+        """Normalise what ``sample()`` was given.  ``known_images`` / ``known_mask``: one top-scale tensor each (the lower
+        scales come from ``known_pyramid``), or hi -> lo lists with None where a scale is free (a None mask beside a given
+        image means all ones)."""
+        n = len(x_shapes)
+        if isinstance(known_images, (list, tuple)):
+            if len(known_images) != n:
+                raise ValueError("known_images has %d entries, the model %d scales" % (len(known_images), n))
+            if known_mask is not None and (not isinstance(known_mask, (list, tuple)) or len(known_mask) != n):
+                raise ValueError("known_mask must be a list of %d entries (or None) beside a list of known_images" % n)
+            ks, ms = list(known_images), list(known_mask) if known_mask is not None else [None] * n
+            if all(k is None for k in ks):
+                raise ValueError("known_images holds no image")
+        else:
+            if isinstance(known_mask, (list, tuple)):
+                raise ValueError("known_mask is a list but known_images one tensor")
+            k = known_images.to(device=device, dtype=dtype)
+            m = torch.ones(k.shape[0], 1, *k.shape[2:], device=device, dtype=dtype) if known_mask is None else known_mask
+            KnownRegion._check(k, m, x_shapes[0])
+            ks, ms = known_pyramid(k, m.to(device=device, dtype=dtype), ratios)
+        for i, (k, shape) in enumerate(zip(ks, x_shapes)):
+            if k is None:
+                if ms[i] is not None:
+                    raise ValueError("known_mask[%d] without known_images[%d]" % (i, i))
+                continue
+            k = k.to(device=device, dtype=dtype).contiguous()
+            m = ms[i]
+            m = torch.ones(k.shape[0], 1, *k.shape[2:], device=device, dtype=dtype) if m is None else m
+            KnownRegion._check(k, m, shape)
+            ks[i], ms[i] = k, m.to(device=device, dtype=dtype).contiguous()
+        inv = [1.0 / s if s else 1.0 for s in image_scales]
+        return KnownRegion(ks, ms, inv, seed, noise_fn)
+
+    @staticmethod
+    def _check(k, m, shape):
+        shape = tuple(shape)
+        if tuple(k.shape) != shape:
+            raise ValueError("known image %s vs the sampled image %s" % (tuple(k.shape), shape))
+        if tuple(m.shape) != (shape[0], 1, shape[2], shape[3]):
+            raise ValueError("known mask must be %s (got %s)" % ((shape[0], 1, shape[2], shape[3]), tuple(m.shape)))
+        if (shape[2] * shape[3]) % 4:
+            raise ValueError("known-region sampling needs H * W to be a multiple of 4 (got %d x %d)" % (shape[2], shape[3]))
+
+    def blend(self, xs, gs):
+        """every scale's x_s (at its own gamma ``gs[i]``) with its known image; -> the list (GPU tensors: in place)"""
+        out = list(xs)
+        for i, (x, g) in enumerate(zip(xs, gs)):
+            k, m, inv = self.images[i], self.masks[i], self.inv_scales[i]
+            if k is None:
+                continue
+            if self.hip:
+                out[i] = ops.sampler_known_blend(x, k, m, g, inv_scale=inv, rng=self.rng, rng_stream=1)
+                self.rng.advance(x.numel())
+            else:
+                out[i] = known_blend(x, k, m, g, inv, self.noise_fn(x))
+        return out
+
+    def jump(self, xs, g_t, g_s):
+        """every scale back from its level g_s[i] to g_t[i]"""
+        out = []
+        for x, gt, gs in zip(xs, g_t, g_s):
+            if self.hip:
+                out.append(ops.sampler_jump(x, gt, gs, rng=self.rng, rng_stream=1, out=x))
+                self.rng.advance(x.numel())
+            else:
+                out.append(jump(x, gt, gs, self.noise_fn(x)))
+        return out
 
 
 class Sampler(nn.Module):
@@ -382,19 +513,52 @@ class Sampler(nn.Module):
         DPM-Solver++(2M), deterministic, second order, one denoiser call per step -- made for few steps
         (``resample_steps=True, num_inference_steps=20..50``)."""
         _check_solver(kwargs.get("solver"), kwargs.get("ddim_eta"))   # here, not at the generator's first next()
+        _check_known(kwargs.get("known_images"), kwargs.get("resample", 1), kwargs.get("solver"))
         gen = self._sample(*args, **kwargs)
         return gen if kwargs.get("yield_output", False) else next(gen)
 
+    def _scale_info(self, model):
+        """-> (top side / side, image_scale) of every scale, hi -> lo: what the step kernel of that scale gets"""
+        return [1], [self._config.rescale_signal or 1]
+
+    def _scale_gammas(self, model, time, B):
+        """gamma of every scale (hi -> lo) at schedule time ``time``, [B, 1, 1, 1] each"""
+        return [self.read_gamma(torch.ones(B, dtype=torch.long, device=self.gammas.device) * time)]
+
+    def _known_region(self, model, x_t, known_images, known_mask, known_seed, known_noise_fn):
+        ratios, image_scales = self._scale_info(model)
+        top = x_t[0] if isinstance(x_t, (list, tuple)) else x_t
+        B, C, H, W = top.shape
+        if H % ratios[-1] or W % ratios[-1]:
+            raise ValueError("image side %d x %d is not a multiple of the nesting ratio %d" % (H, W, ratios[-1]))
+        shapes = [(B, C, H // r, W // r) for r in ratios]
+        return KnownRegion.build(shapes, top.device, top.dtype if top.is_floating_point() else torch.float32, known_images,
+                                 known_mask, ratios, image_scales, known_seed, known_noise_fn)
+
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
-                yield_output=False, solver=None, **post_args):
+                yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
+                known_noise_fn=None, **post_args):
+        """``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
+        whichever update made it, every scale's x_s is replaced where the mask is 1 by the known image diffused to that
+        scale's target gamma (``known_blend``; the last step goes to gamma = 1: the known region of the result IS the known
+        image).  ``resample = r > 1`` (RePaint's jumps of length 1): every step but the last is taken r times, with the
+        forward transition s -> t (``jump``) in between, so that the free region can follow the known one --
+        (n - 1) r + 1 denoiser calls.  The noise of both comes from ``known_seed`` (see ``KnownRegion``).  One top-scale
+        tensor each, or hi -> lo lists for a nested model (``[None, low]``: super-resolution of a given image)."""
         assert not (yield_output and return_sequence)
         _check_solver(solver, ddim_eta)
+        _check_known(known_images, resample, solver)
+        if known_mask is not None and known_images is None:
+            raise ValueError("known_mask without known_images")
         if not resample_steps:
             num_inference_steps = self.n_steps
         steps = torch.from_numpy(self.set_timesteps(num_inference_steps)).to(self.gammas.device)
         if t > -1:
             steps = steps[steps <= t]
+        known = None
+        if known_images is not None:
+            known = self._known_region(model, x_t, known_images, known_mask, known_seed, known_noise_fn)
         seq = [x_t] if return_sequence else []
         x0 = extra = None
         history = {}   # dpmpp_2m: x0 and gamma of the step before, per scale
@@ -403,9 +567,20 @@ class Sampler(nn.Module):
             # step in log-SNR (not on the last one: it goes to gamma = 1)
             order = dict(solver=solver, solver_state=history, second_order=bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)) \
                 if solver is not None else {}
-            x0, x_t, extra = self.get_xt_minus_1(
-                model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
-                guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, **order)
+            reps = resample if i < len(steps) - 2 else 1
+            for rep in range(reps):
+                x0, x_t, extra = self.get_xt_minus_1(
+                    model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
+                    guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, **order)
+                if known is not None:
+                    is_list = isinstance(x_t, (list, tuple))
+                    xs = list(x_t) if is_list else [x_t]
+                    B = xs[0].shape[0]
+                    g_s = self._scale_gammas(model, steps[i + 1], B)
+                    xs = known.blend(xs, g_s)
+                    if rep < reps - 1:
+                        xs = known.jump(xs, self._scale_gammas(model, ts, B), g_s)
+                    x_t = xs if is_list else xs[0]
             if yield_output:
                 yield self._postprocess(x_t, x0, extra, **post_args)
             if return_sequence:
@@ -436,6 +611,14 @@ class NestedSampler(Sampler):
 
     def _signal(self, x, s):
         return x if self._config.schedule_shifted else self.get_image_rescaled(x, s)
+
+    def _scale_info(self, model):
+        scales = model.vision_model.nest_ratio + [1]
+        return [scales[0] // s for s in scales], [1 if self._config.schedule_shifted else s for s in scales]
+
+    def _scale_gammas(self, model, time, B):
+        g = self.read_gamma(torch.ones(B, dtype=torch.long, device=self.gammas.device) * time)
+        return self.get_gammas(g, model.vision_model.nest_ratio + [1])
 
     def get_xt(self, x0, eps, g, scales):
         return [Sampler.get_xt(self, self._signal(x, s), e, gi) for x, s, e, gi in zip(x0, scales, eps, g)]

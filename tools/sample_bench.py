@@ -8,7 +8,13 @@ and DPM-Solver++(2M), alternated call by call in ONE process (device events arou
 ``steps`` iterations, ``--warmup`` calls first, ``--calls`` timed): ms per iteration as median, min, max and p10-p90.  Then
 the wall time of one ``--few``-step (25) 2M ``sample()`` next to one ``--many``-step (250) ancestral DDPM ``sample()``.
    python tools/sample_bench.py nested1024 4 8 --solver dpmpp_2m [--calls 20] [--warmup 3] [--out FILE]
-   rocprofv3 --kernel-trace --stats -d DIR -- python tools/sample_bench.py unet64 4 8 --solver dpmpp_2m --calls 3 --many 0"""
+   rocprofv3 --kernel-trace --stats -d DIR -- python tools/sample_bench.py unet64 4 8 --solver dpmpp_2m --calls 3 --many 0
+
+With ``--known``: known-region sampling against the path it sits beside.  Two graphed legs of ancestral DDPM, without known
+images (the captured graph of before: no launch more) and with a half-image mask (one ``mdm_sampler_known_blend`` launch per
+scale and iteration more), alternated call by call in ONE process, timed like the solver legs.  ``--free-only`` times the
+first leg alone through keywords that older revisions of the package know too: the same figure from another checkout.
+   python tools/sample_bench.py nested1024 4 8 --known [--calls 20] [--warmup 3] [--out FILE]"""
 import argparse
 import json
 import os
@@ -65,12 +71,49 @@ def solver_legs(pipe, smp, batch, side, dev, n_it, a):
     return res
 
 
+def _stats(ts):
+    pct = lambda q: sorted(ts)[min(len(ts) - 1, int(round(q * (len(ts) - 1))))]
+    return {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4),
+            "p10_p90": [round(pct(0.1), 4), round(pct(0.9), 4)]}
+
+
+def known_legs(pipe, smp, batch, side, dev, n_it, a):
+    """graphed DDPM without known images and with the left half of the image known, alternated"""
+    gs = GraphedSampler(pipe, seed=7)
+    g = torch.Generator().manual_seed(3)
+    known = (torch.rand(batch, 3, side, side, generator=g) * 2 - 1).to(dev)
+    mask = torch.zeros(batch, 1, side, side, device=dev)
+    mask[..., : side // 2] = 1
+    legs = {"free": {}}
+    if not a.free_only:
+        legs["known_half"] = dict(known_images=known, known_mask=mask)
+    times, finite = {k: [] for k in legs}, True
+    for it in range(a.warmup + a.calls):
+        for k, kw in legs.items():
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = gs.sample(batch, smp, side, dev, num_inference_steps=n_it, **kw)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= a.warmup:
+                times[k].append(e0.elapsed_time(e1) / n_it)
+            finite = finite and bool(torch.isfinite(out).all())
+    res = {"ms_per_iteration": {k: _stats(ts) for k, ts in times.items()}, "finite": finite}
+    if not a.free_only:
+        res["known_minus_free_median_ms"] = round(res["ms_per_iteration"]["known_half"]["median"] - res["ms_per_iteration"]["free"]["median"], 4)
+        res["known_half_is_kept"] = bool((out[..., : side // 2] - known[..., : side // 2]).abs().max() < 1e-5)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("which", nargs="?", default="nested1024", choices=["unet64", "nested256", "nested1024"])
     ap.add_argument("batch", nargs="?", type=int, default=4)
     ap.add_argument("steps", nargs="?", type=int, default=8)
     ap.add_argument("--solver", default=None, choices=list(samplers.SOLVERS))
+    ap.add_argument("--known", action="store_true", help="graphed DDPM with and without a half-image mask, alternated")
+    ap.add_argument("--free-only", action="store_true", help="with --known: the leg without known images alone")
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--few", type=int, default=25)
@@ -95,6 +138,14 @@ def main():
     pipe = pipe.to(dev)
     g = torch.Generator().manual_seed(1)
     smp = {"lm_outputs": torch.randn(batch, 32, 2048, generator=g).to(dev), "lm_mask": torch.ones(batch, 32).to(dev)}
+    if a.known:
+        res = {"model": which, "batch": batch, "steps_per_call": n_it, "calls": a.calls, "warmup": a.warmup,
+               "sampler": "GraphedSampler, ancestral DDPM, CFG off, bf16, random weights"}
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+            res.update(known_legs(pipe, smp, batch, side, dev, n_it, a))
+        res["max_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2**30, 2)
+        emit(res, a.out)
+        return
     if a.solver is not None:
         res = {"model": which, "batch": batch, "steps_per_call": n_it, "calls": a.calls, "warmup": a.warmup,
                "sampler": "GraphedSampler, CFG off, bf16, random weights"}
