@@ -381,6 +381,29 @@ int mdm_t5_gated_gelu(const void* u, void* y, int T, int F, int dtype, void* str
 int mdm_t5_attn_fwd(const void* qkv, const int* seq_start, const int* pos, const float* bias_table, void* out, int B,
                     int T, int S, int max_len, int H, int d, int dtype, void* stream);
 
+/* ---- low-rank adapters (LoRA) on the attention projections (pure additions: no exported signature changed) -----------
+ * The reference has no counterpart: y = W x + b + s B (A x) with A [r, Cin], B [Cout, r] trainable beside a frozen W, b
+ * (mdm_hip/lora.py).  The base term stays the ordinary mdm_conv_fwd launch; these entries are the rank-r arithmetic.
+ * `dtype` (MDM_F32 | MDM_BF16) is the type of EVERY matrix of a call, the small ones included (the caller keeps copies of
+ * A, B and their transposes in the activation dtype); products on the MFMA pipe, accumulation in fp32.
+ * r in {4, 8, ..., 64} (a multiple of 4; padded to the MFMA shape inside the kernels), C and N multiples of 8, M >= 1.
+ *   mdm_lora_down     t [M, r] = x [M, C] a^T, a row-major [r, C].  x is read once, t written once.
+ *                     forward: T = X A^T;  backward: G = dY B (pass B^T [r, N] as a)
+ *   mdm_lora_up_add   y [M, N] (+)= s t [M, r] b^T, b row-major [N, r]; accumulate != 0 adds in place (one read-modify-write
+ *                     pass over y; b == 0 leaves y bit-identical), accumulate == 0 overwrites y without reading it.
+ *                     forward: Y += s T B^T;  backward: dX = s G A (pass A^T [C, r] as b);  merge / unmerge on fp32
+ *                     masters: W [Cout, Cin] += (+-s) B A (t = B, b = A^T, MDM_F32)
+ *   mdm_lora_wgrad    d [r, C] fp32 (+)= s p [M, r]^T q [M, C]: p and q are read once, split over M into *splits_out fp32
+ *                     slabs [r, C] in ws (*ws_bytes, both from mdm_lora_wgrad_plan, host-only) that a second kernel of
+ *                     the same call sums in slab order -- no float atomics, two runs are bit-identical.
+ *                     dA = s G^T X (p = G, q = X);  dB^T [r, N] = s T^T dY (p = T, q = dY) */
+int mdm_lora_down(const void* x, const void* a, void* t, int M, int C, int r, int dtype, void* stream);
+int mdm_lora_up_add(void* y, const void* t, const void* b, int M, int N, int r, float s, int accumulate, int dtype,
+                    void* stream);
+int mdm_lora_wgrad_plan(int M, int r, int C, int dtype, int* splits_out, size_t* ws_bytes);
+int mdm_lora_wgrad(const void* p, const void* q, float* d, float* ws, int M, int r, int C, float s, int accumulate,
+                   int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

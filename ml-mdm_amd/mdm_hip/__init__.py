@@ -12,6 +12,7 @@ Layout of the package
   registry.py     plug into the reference's ml_mdm.config registries when present
   text_encoder.py T5Encoder / LanguageModel: the frozen flan-T5 text encoder on packed tokens (mirror of
                   ml_mdm.language_models.factory)
+  lora.py         LoRA adapters on the attention projections: attach / merge / unmerge / detach
 """
 import os as _os
 
@@ -33,6 +34,7 @@ from .nested_unet import (  # noqa: E402  # noqa: F401
 )
 from .text_encoder import LanguageModel, T5Encoder, T5EncoderConfig  # noqa: F401,E402
 from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
+from . import lora  # noqa: F401,E402
 
 __all__ = [
     "UNet",
@@ -46,4 +48,5 @@ __all__ = [
     "T5Encoder",
     "T5EncoderConfig",
     "LanguageModel",
+    "lora",
 ]

@@ -12,7 +12,9 @@ batch the ~1500 kernel launches of one call are host-bound (Python + launch, wha
                       between.  All per-step values live in device tables indexed by a device-side counter.
 
 Inference only (no autograd through a replay); parameters must not change between replays -- call ``reset()`` after
-loading a checkpoint (the packed kernel-layout weights baked into the graph would be stale otherwise).
+loading a checkpoint (the packed kernel-layout weights baked into the graph would be stale otherwise).  Attaching, detaching,
+merging or unmerging LoRA adapters (``mdm_hip.lora``) changes what a forward launches: both classes
+drop their graphs when ``ops.adapter_epoch()`` has moved, so the next call captures anew instead of replaying a stale one.
 """
 import numpy as np
 import torch
@@ -28,6 +30,7 @@ class GraphedDenoiser(nn.Module):
         self.model = model
         self._warmup = warmup
         self._graphs = {}
+        self._adapter_epoch = ops.adapter_epoch()
 
     # attributes the diffusion / sampler code reads from the vision model
     def __getattr__(self, name):
@@ -49,6 +52,9 @@ class GraphedDenoiser(nn.Module):
     def forward(self, x_t, times, conditioning=None, cond_mask=None, micros={}):
         if torch.is_grad_enabled() or self.model.training or micros:
             return self.model(x_t, times, conditioning, cond_mask, micros)
+        if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
+            self._graphs.clear()
+            self._adapter_epoch = ops.adapter_epoch()
         key = self._sig(x_t, times, conditioning, cond_mask)
         ent = self._graphs.get(key)
         is_list = isinstance(x_t, (list, tuple))
@@ -108,6 +114,7 @@ class GraphedSampler:
         self._warmup = warmup
         self._seed = seed
         self._graphs = {}
+        self._adapter_epoch = ops.adapter_epoch()
         fn = self.sampler._config.threshold_function
         if fn not in (ThresholdType.CLIP, ThresholdType.NONE, ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF):
             raise NotImplementedError("GraphedSampler: unknown threshold function %r" % (fn,))
@@ -274,6 +281,11 @@ class GraphedSampler:
             raise ValueError("known_mask without known_images")
         if start_step is not None and start_noise is None:
             raise ValueError("start_step needs start_noise: the image noised to that step")
+        if ops.adapter_epoch() != self._adapter_epoch:
+            # LoRA adapters were attached / detached / merged / unmerged since the graphs were captured: what a forward
+            # launches, or the weights it reads, changed -- stale like after a checkpoint load, so capture anew
+            self._graphs.clear()
+            self._adapter_epoch = ops.adapter_epoch()
         self.pipe.eval()
         smp = self.sampler
         nested = isinstance(smp, NestedSampler)

@@ -989,12 +989,16 @@ class FFNFn(torch.autograd.Function):
             dbt = torch.empty(cout_, dtype=torch.float32, device=xin.device)
             return _wgrad_launch(xin, g, N, H, W, cin_, H, W, cout_, 1, 1, dbias=dbt).view(w.shape), dbt
 
-        dw2, db2 = wb_grads(a, dy, w2, b2, c_hid, c_out)
+        # a frozen layer (neither the weight nor its bias wants a gradient) launches no weight-gradient GEMM
+        dw1 = db1 = dw2 = db2 = None
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            dw2, db2 = wb_grads(a, dy, w2, b2, c_hid, c_out)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             _conv_launch(dpre, wd1, None, None, None, dx, None, N, H, W, c_hid, H, W, c_in, 1, 1, 0, 0)
-        dw1, db1 = wb_grads(x, dpre, w1, b1, c_in, c_hid)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw1, db1 = wb_grads(x, dpre, w1, b1, c_in, c_hid)
         dres = dy if (ctx.has_res and ctx.needs_input_grad[5]) else None
         return dx, dw1, db1, dw2, db2, dres, None
 
@@ -1002,6 +1006,144 @@ class FFNFn(torch.autograd.Function):
 def ffn(x, w1, b1, w2, b2, residual):
     # autograd.Function.forward runs with grad mode off, so the "will there be a backward" decision is taken here
     return FFNFn.apply(x, w1, b1, w2, b2, residual, torch.is_grad_enabled())
+
+
+# --------------------------------------------------------------------------------------
+# low-rank adapters (mdm_hip/lora.py): y = W x + b + s B (A x) beside a frozen W, b
+# --------------------------------------------------------------------------------------
+_adapter_epoch = 0   # moves whenever adapters are attached / detached / merged / unmerged: captured graphs are keyed on it
+
+
+def adapter_epoch() -> int:
+    return _adapter_epoch
+
+
+def bump_adapter_epoch():
+    global _adapter_epoch
+    _adapter_epoch += 1
+
+
+def _lora_mats(big, small, what):
+    """checks shared by the three kernels: ``big`` [M, C] and ``small`` [*, *] contiguous GPU tensors of one dtype"""
+    _require_gpu(big)
+    _require_gpu(small)
+    if big.dtype != small.dtype or not big.is_contiguous() or not small.is_contiguous():
+        raise _lib.MdmHipError("%s: operands must be contiguous tensors of one dtype (%s, %s)" % (what, big.dtype, small.dtype))
+
+
+def lora_down(x, a):
+    """t [M, r] = x [M, C] a^T  (a [r, C], both of x's dtype)"""
+    _lora_mats(x, a, "lora_down")
+    M, C = x.shape
+    r = a.shape[0]
+    if a.shape[1] != C:
+        raise _lib.MdmHipError("lora_down: x has %d columns, a has %d" % (C, a.shape[1]))
+    t = torch.empty((M, r), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().mdm_lora_down(_p(x), _p(a), _p(t), M, C, r, _dt(x), _stream()), "mdm_lora_down")
+    return t
+
+
+def lora_up_add(y, t, b, s, accumulate=True):
+    """y [M, N] (+)= s t [M, r] b^T in place  (b [N, r]); ``accumulate=False`` overwrites y without reading it"""
+    _lora_mats(y, b, "lora_up_add")
+    _lora_mats(y, t, "lora_up_add")
+    M, N = y.shape
+    r = t.shape[1]
+    if t.shape[0] != M or tuple(b.shape) != (N, r):
+        raise _lib.MdmHipError("lora_up_add: y %s, t %s, b %s do not fit" % (tuple(y.shape), tuple(t.shape), tuple(b.shape)))
+    _lib.check(_lib.lib().mdm_lora_up_add(_p(y), _p(t), _p(b), M, N, r, float(s), 1 if accumulate else 0, _dt(y), _stream()),
+               "mdm_lora_up_add")
+    return y
+
+
+def lora_wgrad(p, q, s, out=None):
+    """d [r, C] fp32 = s p [M, r]^T q [M, C]; with ``out`` the result is ADDED into it.  Deterministic (no atomics)."""
+    _lora_mats(q, p, "lora_wgrad")
+    M, C = q.shape
+    r = p.shape[1]
+    if p.shape[0] != M:
+        raise _lib.MdmHipError("lora_wgrad: p has %d rows, q has %d" % (p.shape[0], M))
+    L = _lib.lib()
+    splits, wsb = ctypes.c_int(0), ctypes.c_size_t(0)
+    _lib.check(L.mdm_lora_wgrad_plan(M, r, C, _dt(q), ctypes.byref(splits), ctypes.byref(wsb)), "mdm_lora_wgrad_plan")
+    ws = _f32_ws(wsb.value, q.device)
+    d = torch.empty((r, C), dtype=torch.float32, device=q.device) if out is None else out
+    if d.dtype != torch.float32 or not d.is_contiguous() or tuple(d.shape) != (r, C):
+        raise _lib.MdmHipError("lora_wgrad: out must be a contiguous fp32 [%d, %d] tensor" % (r, C))
+    _lib.check(L.mdm_lora_wgrad(_p(p), _p(q), _p(d), _p(ws), M, r, C, float(s), 0 if out is None else 1, _dt(q), _stream()),
+               "mdm_lora_wgrad")
+    return d
+
+
+def _lora_packs(A, B, dtype):
+    """(A [r, C], A^T [C, r], B [N, r], B^T [r, N]) of the activation dtype for the fp32 adapter parameters; cached per
+    parameter version and re-made INTO THE SAME BUFFERS (a captured graph holds their addresses)"""
+    ent = _cache_slot(A)
+    key = ("lora", dtype)
+    ver = (A._version, B._version, A.data_ptr(), B.data_ptr(), _pack_epoch)
+    if key in ent and ent[key][0] == ver:
+        return ent[key][1]
+    _require_gpu(A)
+    _require_gpu(B)
+    prev = ent[key][1] if key in ent else None
+    if prev is None or prev[0].shape != A.shape or prev[2].shape != B.shape or prev[0].device != A.device:
+        r, C = A.shape
+        N = B.shape[0]
+        prev = tuple(torch.empty(shp, dtype=dtype, device=A.device) for shp in ((r, C), (C, r), (N, r), (r, N)))
+    with torch.no_grad():
+        prev[0].copy_(A)
+        prev[1].copy_(A.t())
+        prev[2].copy_(B)
+        prev[3].copy_(B.t())
+    ent[key] = (ver, prev)
+    return prev
+
+
+class LoraFn(torch.autograd.Function):
+    """y += s (x A^T) B^T, IN PLACE on y = the base projection's fresh output (its producer, ConvFn, saves its inputs
+    only).  x [..., C] is that projection's input; A [r, C], B [N, r] are the fp32 adapter parameters."""
+
+    @staticmethod
+    def forward(ctx, y, x, A, B, s):
+        _require_gpu(x)
+        _require_gpu(y)
+        r, C = A.shape
+        N = B.shape[0]
+        if not y.is_contiguous() or y.dtype != x.dtype or y.shape[-1] != N or x.shape[-1] != C or B.shape[1] != r:
+            raise _lib.MdmHipError("lora: y %s / x %s / A %s / B %s do not fit (y must be contiguous, of x's dtype)"
+                                   % (tuple(y.shape), tuple(x.shape), tuple(A.shape), tuple(B.shape)))
+        x2 = _c(x).reshape(-1, C)
+        M = x2.shape[0]
+        a_c, _, b_c, _ = _lora_packs(A, B, x.dtype)
+        t = lora_down(x2, a_c)
+        lora_up_add(y.view(M, N), t, b_c, s)
+        ctx.mark_dirty(y)
+        ctx.save_for_backward(x2, t, A, B)
+        ctx.s, ctx.xshape = s, x.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, t, A, B = ctx.saved_tensors
+        M, C = x2.shape
+        N = B.shape[0]
+        dy2 = _c(dy).reshape(M, N)
+        _, at_c, _, bt_c = _lora_packs(A, B, x2.dtype)
+        dx = dA = dB = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            g = lora_down(dy2, bt_c)                                    # G = dY B
+            if ctx.needs_input_grad[1]:                                 # the low-rank part of dX = s G A
+                dx = lora_up_add(torch.empty_like(x2), g, at_c, ctx.s, accumulate=False).view(ctx.xshape)
+            if ctx.needs_input_grad[2]:
+                dA = lora_wgrad(g, x2, ctx.s)                           # s G^T X
+        if ctx.needs_input_grad[3]:
+            dB = lora_wgrad(t, dy2, ctx.s).t()                          # (s T^T dY)^T
+        return dy, dx, dA, dB, None
+
+
+def lora(y, x, A, B, s):
+    """the adapter term of one projection, added into its output y (returned): see LoraFn"""
+    return LoraFn.apply(y, x, A, B, float(s))
 
 
 # --------------------------------------------------------------------------------------

@@ -164,7 +164,9 @@ def _adopt(model, optimizer, ema_model):
     if not isinstance(net, UNet):
         return no("vision model is not an mdm_hip UNet")
     params = [p for p in net.parameters() if p.requires_grad]
-    if not params or not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+    if not params:
+        return no("vision model has no trainable parameters")
+    if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
         return no("parameters are not fp32 tensors on the GPU")
     if type(optimizer) not in (torch.optim.AdamW, torch.optim.Adam) or len(optimizer.param_groups) != 1:
         return no("optimizer is not a single-group torch Adam / AdamW")
@@ -242,6 +244,20 @@ def _loss_of(losses, weights):
     return losses.mean() if weights is None else (losses * weights).sum() / weights.sum()
 
 
+def _clip_parameters(model, optimizer):
+    """what the plain path clips: the model's parameters (the reference's set, trainer.py:52-58) and, behind them, every
+    parameter the optimizer holds that is not among them (LoRA adapters live outside the model) -- one norm over the union"""
+    mine = list(model.model.parameters())
+    seen = {id(p) for p in mine}
+    extra = []
+    for grp in optimizer.param_groups:
+        for p in grp["params"]:
+            if id(p) not in seen:
+                seen.add(id(p))
+                extra.append(p)
+    return mine + extra if extra else model.model.parameters()
+
+
 def train_batch(model, sample, optimizer, scheduler, logger, args, grad_scaler=None, accumulate_gradient=False,
                 num_grad_accumulations=1, ema_model=None, loss_factor=1.0):
     """One micro-step of ``ml_mdm.trainer.train_batch`` (reference trainer.py:13-96): same arguments, same return value
@@ -293,11 +309,11 @@ def train_batch(model, sample, optimizer, scheduler, logger, args, grad_scaler=N
         core = getattr(model.model, "module", model.model)
         if fp16 and grad_scaler is not None:
             grad_scaler.unscale_(optimizer)
-            torch.nn.utils.clip_grad_norm_(model.model.parameters(), clip)
+            optimizer._mdm_grad_norm = torch.nn.utils.clip_grad_norm_(_clip_parameters(model, optimizer), clip)
             grad_scaler.step(optimizer)
             grad_scaler.update()
         else:
-            torch.nn.utils.clip_grad_norm_(model.model.parameters(), clip)
+            optimizer._mdm_grad_norm = torch.nn.utils.clip_grad_norm_(_clip_parameters(model, optimizer), clip)
             optimizer.step()
         ops.invalidate_packed_weights()
         if ema_model is not None:

@@ -210,21 +210,42 @@ class SelfAttention(nn.Module):
         else:
             self.ffn = None
 
+    # low-rank adapters of this layer's projections (mdm_hip.lora.attach): a plain handle, not a submodule -- the state
+    # dict keeps the reference's keys.  None: no line below launches anything it did not launch before.
+    _lora = None
+
     def forward(self, x, cond=None, cond_mask=None):
         N, H, W, C = x.shape
+        lora = self._lora
         hn, x = ops.group_norm(x, self.norm.weight, self.norm.bias, 32, self.norm.eps, passthrough=True)
         qkv = ops.conv(hn, self.qkv.weight, self.qkv.bias)
+        if lora is not None:
+            qkv = lora.apply("qkv", qkv, hn)
         kvc = None
         if self.cond_dim is not None and self.cond_dim > 0:
             if isinstance(cond, TextStates) and id(self) in cond.kv:
                 kvc = cond.kv[id(self)]          # projected up front with all the other layers (ops.text_kv)
+                if lora is not None and lora.active("kv_cond"):
+                    # the base term stays the grouped projection, so B = 0 reproduces the model without adapters bit for
+                    # bit; the adapter term needs this layer's own LayerNorm output and adds into a COPY: a sampling loop
+                    # computes the grouped result once and reads it again in every step
+                    cn = ops.layer_norm(cond.raw, self.norm_cond.weight, self.norm_cond.bias, self.norm_cond.eps)
+                    kvc = lora.apply("kv_cond", kvc.clone(), cn)
             else:
                 raw = cond.raw if isinstance(cond, TextStates) else cond
                 cn = ops.layer_norm(raw, self.norm_cond.weight, self.norm_cond.bias, self.norm_cond.eps)
-                kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
+                if lora is not None and lora.active("kv_cond"):
+                    # the adapter adds into the projection's own output tensor: [rows, D] -> [rows, 2C], reshaped after
+                    cn2 = cn.reshape(-1, cn.shape[-1])
+                    kvc = lora.apply("kv_cond", ops.conv(cn2, self.kv_cond.weight, self.kv_cond.bias), cn2)
+                    kvc = kvc.reshape(*cn.shape[:-1], kvc.shape[-1])
+                else:
+                    kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
         a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
         a = a.reshape(N, H, W, C)
         x = ops.conv(a, self.proj_out.weight, self.proj_out.bias, residual=x)
+        if lora is not None:
+            x = lora.apply("proj_out", x, a)
         if self.ffn is not None:
             fn, x = ops.group_norm(x, self.ffn[0].weight, self.ffn[0].bias, 32, self.ffn[0].eps, passthrough=True)
             x = ops.ffn(fn, self.ffn[1].weight, self.ffn[1].bias, self.ffn[3].weight, self.ffn[3].bias, residual=x)
