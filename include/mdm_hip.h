@@ -404,6 +404,25 @@ int mdm_lora_wgrad_plan(int M, int r, int C, int dtype, int* splits_out, size_t*
 int mdm_lora_wgrad(const void* p, const void* q, float* d, float* ws, int M, int r, int C, float s, int accumulate,
                    int dtype, void* stream);
 
+/* ---- the same for the 3x3 (stride 1, padding 1) convolutions of the ResNet blocks (pure additions) --------------------
+ * y = conv3x3(x, W) + b + s B conv3x3(x, A): A [r, Cin, 3, 3] carries the 3x3, B [Cout, r] is 1x1.  Activations are NHWC
+ * [N, H, W, C]; tap = 3 ky + kx; a tap outside the pixel's own image contributes zeros (never the neighbouring image of
+ * the batch).  Same dtypes, ranks and channel multiples as above; N H W < 2^30.
+ *   mdm_lora_down_conv3x3     t [N,H,W,r] : t[n,y,x,j] = sum_{ky,kx,c} x[n, y+ky-1, x+kx-1, c] a[j][tap][c], a packed
+ *                             [r][9][C] in the activation dtype
+ *   mdm_lora_up_add_conv3x3   y[n,y,x,o] (+)= s sum_{ky,kx,j} t[n, y+ky-1, x+kx-1, j] b[o][tap][j], b packed [Cout][9][r].
+ *                             The adapter's forward up-projection is 1x1 (mdm_lora_up_add); this entry is the backward's
+ *                             transposed convolution: dx = it(g, b[c][tap][j] = A[j][8 - tap][c], accumulate = 0)
+ *   mdm_lora_wgrad_conv3x3    d [r][9][C] fp32 (+)= s sum_{n,y,x} p[n,y,x,j] q[n, y+ky-1, x+kx-1, c]; row slabs in ws
+ *                             (*ws_bytes, *splits_out from the host-only _plan) summed in slab order: deterministic.
+ *                             dA = it(p = g, q = x), then permuted to [r, Cin, 3, 3] by the caller */
+int mdm_lora_down_conv3x3(const void* x, const void* a, void* t, int N, int H, int W, int C, int r, int dtype, void* stream);
+int mdm_lora_up_add_conv3x3(void* y, const void* t, const void* b, int N, int H, int W, int Cout, int r, float s,
+                            int accumulate, int dtype, void* stream);
+int mdm_lora_wgrad_conv3x3_plan(int N, int H, int W, int r, int C, int dtype, int* splits_out, size_t* ws_bytes);
+int mdm_lora_wgrad_conv3x3(const void* p, const void* q, float* d, float* ws, int N, int H, int W, int r, int C, float s,
+                           int accumulate, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -334,6 +334,290 @@ inline void lora_wgrad_split(int M, int C, int dtype, int* rows_per_split, int* 
   *ngroups = groups;
 }
 
+// =====================================================================================================================
+// The same three products for a 3x3 (stride 1, padding 1) adapter on an NHWC activation [N, H, W, C]:
+//   y = conv3x3(x, W) + b + s B conv3x3(x, A),   A [r, Cin, 3, 3] (the 3x3 sits on the down-projection), B [Cout, r]
+//   lora_down_conv3x3_kernel     T[M, r]     = sum_tap X[m + shift(tap)][C] A[:, tap, :]^T        a packed [r][9][C]
+//   lora_up_add_conv3x3_kernel   Y[M, N] (+)= s sum_tap T[m + shift(tap)][r] B[:, tap, :]^T      b packed [N][9][r]
+//   lora_wgrad_conv3x3_kernel    D[r][9][C] (+)= s sum_m P[m][r]^T Q[m + shift(tap)][C]          + the reduce kernel above
+// with M = N H W rows, tap = 3 ky + kx and shift(tap) = (ky - 1) W + (kx - 1) rows.  A pixel's position in its own image
+// is (y, x) = ((m / W) % H, m % W); a tap whose (y + ky - 1, x + kx - 1) lies outside [0, H) x [0, W) contributes zeros --
+// that one test covers the image's four borders AND the neighbouring images of the batch, and whenever it passes the
+// shifted row lies in the same image, hence inside the buffer.  Where it fails the lane reads `safe` (the buffer's first
+// element) and selects zeros: branch-free, and no out-of-range address is formed into a load.  The shifted rows are
+// re-read through L2 (a row is used by 9 taps of 3 neighbouring rows: the working set of a block is 3 image rows) rather
+// than staged as a halo in LDS: the kernels have a few MFMAs per byte and no reuse inside a block beyond those 9 taps.
+// =====================================================================================================================
+
+// the two 4-element halves of a fragment from two addresses of their own (each n-th of a 32-deep step may belong to
+// another tap, hence another row); !ok -> zeros, read from `safe`
+__device__ __forceinline__ void ldg_frag4x2(Frag<bf16>& f, const bf16* p0, bool ok0, const bf16* p1, bool ok1, const bf16* safe) {
+  const u32x2 a = *reinterpret_cast<const u32x2*>(ok0 ? p0 : safe), b = *reinterpret_cast<const u32x2*>(ok1 ? p1 : safe);
+  uint4 u = uint4{ok0 ? a.x : 0u, ok0 ? a.y : 0u, ok1 ? b.x : 0u, ok1 ? b.y : 0u};
+  f.v = *reinterpret_cast<bf16x8*>(&u);
+}
+__device__ __forceinline__ void ldg_frag4x2(Frag<float>& f, const float* p0, bool ok0, const float* p1, bool ok1, const float* safe) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(ok0 ? p0 : safe), b = *reinterpret_cast<const f32x4*>(ok1 ? p1 : safe);
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f.lo = ok0 ? a : z;
+  f.hi = ok1 ? b : z;
+}
+
+// Blocks b and b + 8 share an XCD and its L2 (observed dealing, for speed only): the blocks of one XCD get a contiguous range
+// of tiles, so that the rows a tile re-reads from its neighbours (+-(W + 1) rows) sit in the L2 that fetched them.
+// Bijective for any number of blocks n.
+__device__ __forceinline__ int xcd_tile(int b, int n) {
+  const int q = n >> 3, rem = n & 7, x = b & 7;
+  return (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + (b >> 3);
+}
+
+// T[M, r] = sum_tap X[m + shift(tap)] A[:, tap, :]^T: lora_down_kernel with the k-steps running over 9 x ceil(C / 32)
+// (tap-major), dealt to the four waves in turn.  X comes from HBM once and 8 more times from L2; A [r][9][C] per block
+// through L2.
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void lora_down_conv3x3_kernel(const T* __restrict__ X, const T* __restrict__ A, T* __restrict__ Tout,
+                                                                int M, int H, int W, int C, int r) {
+  __shared__ f32x4 part[4][DOWN_RT * NT][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int l15 = lane & 15, quad = lane >> 4;
+  const int m0 = xcd_tile(blockIdx.x, gridDim.x) * (16 * DOWN_RT);
+  int px[DOWN_RT], py[DOWN_RT];
+#pragma unroll
+  for (int rt = 0; rt < DOWN_RT; ++rt) {
+    const int m = m0 + rt * 16 + l15;
+    px[rt] = m % W;
+    py[rt] = (m / W) % H;
+  }
+  f32x4 acc[DOWN_RT][NT];
+#pragma unroll
+  for (int rt = 0; rt < DOWN_RT; ++rt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int kpt = (C + 31) / 32;   // k-steps per tap
+  const int ksteps = 9 * kpt;
+  for (int ks = w; ks < ksteps; ks += 4) {
+    const int tap = ks / kpt;
+    const int k = (ks - tap * kpt) * 32 + quad * 8;
+    const int ky = tap / 3, dy = ky - 1, dx = tap - 3 * ky - 1;
+    const bool kok = k < C;   // C % 8 == 0: a chunk is inside or outside as a whole
+    Frag<T> xf[DOWN_RT], af[NT];
+#pragma unroll
+    for (int rt = 0; rt < DOWN_RT; ++rt) {
+      const int m = m0 + rt * 16 + l15;
+      const bool ok = kok && m < M && (unsigned)(py[rt] + dy) < (unsigned)H && (unsigned)(px[rt] + dx) < (unsigned)W;
+      const size_t row = ok ? (size_t)(m + dy * W + dx) : 0;
+      ldg_frag8(xf[rt], X + row * C + k, ok, X);
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int n = t * 16 + l15;
+      ldg_frag8(af[t], A + ((size_t)n * 9 + tap) * C + k, kok && n < r, A);
+    }
+#pragma unroll
+    for (int rt = 0; rt < DOWN_RT; ++rt)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) mma16(acc[rt][t], af[t], xf[rt]);   // [rank n][row m]
+  }
+#pragma unroll
+  for (int rt = 0; rt < DOWN_RT; ++rt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) part[w][rt * NT + t][lane] = acc[rt][t];
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < DOWN_RT * NT * 64; idx += 256) {
+    const int tile = idx >> 6, ln = idx & 63;
+    const f32x4 s = ((part[0][tile][ln] + part[1][tile][ln]) + part[2][tile][ln]) + part[3][tile][ln];
+    const int m = m0 + (tile / NT) * 16 + (ln & 15);
+    const int n = (tile % NT) * 16 + (ln >> 4) * 4;
+    if (m < M && n < r) st4(Tout + (size_t)m * r + n, s);
+  }
+}
+
+// Y[M, N] (+)= s sum_tap T[m + shift(tap)] B[:, tap, :]^T.  The reduction index is k = tap r + j, 9 r long and
+// contiguous in the packed B [N][9][r]; it is cut into 32-deep MFMA steps WITHOUT padding each tap: a lane's fragment is
+// two runs of 4 (r % 4 == 0: a run never straddles two taps), each with the tap, hence the shifted row of T, of its own.
+// r = 4 takes 2 steps (36 of 64 slots used), not 9.  The wave tile is lora_up_add_kernel's (32 rows x 128 columns, the
+// same dealing of B's rows so that a lane owns 8 consecutive columns); the k-steps are a loop of loads and MFMAs only,
+// and Y is read (ACC), added to and stored once behind it.
+template <typename T, bool ACC>
+__global__ __launch_bounds__(256) void lora_up_add_conv3x3_kernel(T* __restrict__ Y, const T* __restrict__ Tm, const T* __restrict__ B,
+                                                                  int M, int H, int W, int N, int r, float s, int ncol, int ntiles) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int l15 = lane & 15, quad = lane >> 4;
+  const int wid = xcd_tile(blockIdx.x, gridDim.x) * 4 + w;
+  if (wid >= ntiles) return;   // wave-uniform; the kernel has no barrier
+  const int m0 = (wid / ncol) * (16 * UP_RT), n0 = (wid % ncol) * (32 * UP_U);
+  int px[UP_RT], py[UP_RT];
+#pragma unroll
+  for (int rt = 0; rt < UP_RT; ++rt) {
+    const int m = m0 + rt * 16 + l15;
+    px[rt] = m % W;
+    py[rt] = (m / W) % H;
+  }
+  f32x4 acc[UP_RT][UP_U][2];
+#pragma unroll
+  for (int rt = 0; rt < UP_RT; ++rt)
+#pragma unroll
+    for (int u = 0; u < UP_U; ++u) acc[rt][u][0] = acc[rt][u][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int rpt = r >> 2;       // runs of 4 per tap
+  const int K = 9 * r;
+  const int ksteps = (K + 31) / 32;
+  for (int ks = 0; ks < ksteps; ++ks) {
+    const int k = ks * 32 + quad * 8;
+    const T* tp[2];
+    int tdy[2], tdx[2];
+    bool tin[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int run = (k >> 2) + h;
+      tin[h] = run < 9 * rpt;
+      const int tap = tin[h] ? run / rpt : 0;
+      const int ky = tap / 3;
+      tdy[h] = ky - 1;
+      tdx[h] = tap - 3 * ky - 1;
+      tp[h] = Tm + (run - tap * rpt) * 4;
+    }
+    Frag<T> tf[UP_RT];
+#pragma unroll
+    for (int rt = 0; rt < UP_RT; ++rt) {
+      const int m = m0 + rt * 16 + l15;
+      bool ok[2];
+      size_t row[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        ok[h] = tin[h] && m < M && (unsigned)(py[rt] + tdy[h]) < (unsigned)H && (unsigned)(px[rt] + tdx[h]) < (unsigned)W;
+        row[h] = ok[h] ? (size_t)(m + tdy[h] * W + tdx[h]) : 0;
+      }
+      ldg_frag4x2(tf[rt], tp[0] + row[0] * r, ok[0], tp[1] + row[1] * r, ok[1], Tm);
+    }
+#pragma unroll
+    for (int u = 0; u < UP_U; ++u) {
+      if (n0 + u * 32 >= N) continue;   // wave-uniform: a column group past N has nothing to form
+      Frag<T> bf[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int n = n0 + u * 32 + (l15 >> 2) * 8 + h * 4 + (l15 & 3);
+        ldg_frag44(bf[h], B + (size_t)n * K + k, n < N ? K - k : 0, B);
+      }
+#pragma unroll
+      for (int rt = 0; rt < UP_RT; ++rt)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) mma16(acc[rt][u][h], bf[h], tf[rt]);   // [column 8 quad + 4 h + i][row l15]
+    }
+  }
+#pragma unroll
+  for (int rt = 0; rt < UP_RT; ++rt)
+#pragma unroll
+    for (int u = 0; u < UP_U; ++u) {
+      const int m = m0 + rt * 16 + l15, n = n0 + u * 32 + quad * 8;
+      const bool yok = m < M && n < N;   // N % 8 == 0
+      float y[8];
+      if (ACC) {
+        ld8(y, yok ? Y + (size_t)m * N + n : Y);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) y[i] = 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        y[i] += s * acc[rt][u][0][i];
+        y[4 + i] += s * acc[rt][u][1][i];
+      }
+      if (yok) st8(Y + (size_t)m * N + n, y);
+    }
+}
+
+// D[r][9][C] (+)= s sum_m P[m]^T Q[m + shift(tap)]: lora_wgrad_kernel with the tap as one more dimension of the grid.  A
+// wave owns a slab of rows, one tap and 16 chunks of columns; the 9 waves of a (slab, column group) sit side by side in
+// the grid and read the same rows of Q, shifted by at most W + 1 rows: Q comes from HBM once and from L2 for the rest.
+// (y, x) of the lane's first row takes two divisions per 32 rows; the 7 rows behind it are counted up.
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void lora_wgrad_conv3x3_kernel(const T* __restrict__ P, const T* __restrict__ Q, float* __restrict__ ws,
+                                                                 int M, int H, int W, int r, int C, int rows_per_split, int ngroups,
+                                                                 int ntiles) {
+  constexpr int EPV = Tr<T>::EPV;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int l15 = lane & 15, quad = lane >> 4;
+  const int wid = xcd_tile(blockIdx.x, gridDim.x) * 4 + w;
+  if (wid >= ntiles) return;   // wave-uniform; no barrier below
+  const int sp = wid / (9 * ngroups), rem = wid - sp * (9 * ngroups);
+  const int tap = rem % 9;
+  const int c0 = (rem / 9) * (16 * EPV) + l15 * EPV;
+  const bool cok = c0 < C;     // C % 8 == 0
+  const int ky = tap / 3, dy = ky - 1, dx = tap - 3 * ky - 1;
+  const int mb = sp * rows_per_split;
+  const int me = mb + rows_per_split < M ? mb + rows_per_split : M;
+  f32x4 acc[NT][EPV];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int c = 0; c < EPV; ++c) acc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int m = mb; m < me; m += 32) {
+    QBlk<T> qb;
+    T pe[NT][8];
+    int x = (m + quad * 8) % W, y = ((m + quad * 8) / W) % H;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int mm = m + quad * 8 + j;
+      const bool ok = cok && mm < me && (unsigned)(y + dy) < (unsigned)H && (unsigned)(x + dx) < (unsigned)W;
+      qb.load(j, ok ? Q + (size_t)(mm + dy * W + dx) * C + c0 : Q, ok);
+      if (++x == W) {
+        x = 0;
+        if (++y == H) y = 0;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int mm = m + quad * 8 + j, n = t * 16 + l15;
+        const bool ok = mm < me && n < r;
+        const T v = *(ok ? P + (size_t)mm * r + n : P);
+        pe[t][j] = ok ? v : (T)0.f;
+      }
+    Frag<T> pf[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) frag_of(pf[t], pe[t]);
+#pragma unroll
+    for (int c = 0; c < EPV; ++c) {
+      Frag<T> qf;
+      qb.frag(qf, c);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) mma16(acc[t][c], pf[t], qf);   // [rank 16 t + 4 quad + i][column c0 + c]
+    }
+  }
+  if (!cok) return;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int n = t * 16 + quad * 4 + i;
+      if (n < r) {
+        float* o = ws + (((size_t)sp * r + n) * 9 + tap) * C + c0;
+#pragma unroll
+        for (int c = 0; c < EPV; c += 4)
+          *reinterpret_cast<f32x4*>(o + c) = f32x4{acc[t][c][i], acc[t][c + 1][i], acc[t][c + 2][i], acc[t][c + 3][i]};
+      }
+    }
+}
+
+// the 3x3 form's split: the same rule with 9 waves (one per tap) for every (slab, column group)
+inline void lora_wgrad_conv3x3_split(int M, int C, int dtype, int* rows_per_split, int* nsplit, int* ngroups) {
+  const int cw = 16 * (dtype == DT_F32 ? 4 : 8);
+  const int groups = (C + cw - 1) / cw;
+  int rps = 128;
+  while ((long long)((M + rps - 1) / rps) * groups * 9 > 4096 || (M + rps - 1) / rps > 256) rps *= 2;
+  *rows_per_split = rps;
+  *nsplit = (M + rps - 1) / rps;
+  *ngroups = groups;
+}
+
+// N H W rows of an NHWC activation as an int (the kernels index rows with 32 bits), or 0 if the geometry is not valid
+inline int lora_conv_rows(int N, int H, int W) {
+  if (N < 1 || H < 1 || W < 1) return 0;
+  const long long m = (long long)N * H * W;
+  return m < (1ll << 30) ? (int)m : 0;   // row + shift and 32-row tile arithmetic stay far inside int
+}
+
 }  // namespace
 }  // namespace mdm
 
@@ -418,6 +702,92 @@ extern "C" int mdm_lora_wgrad(const void* p, const void* q, float* d, float* ws,
   }
 #undef MDM_LORA_WG
   const size_t n4 = (size_t)r * C / 4;
+  hipLaunchKernelGGL(lora_wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, ws, d, n4, nsplit, s, accumulate);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_lora_down_conv3x3(const void* x, const void* a, void* t, int N, int H, int W, int C, int r, int dtype,
+                                     void* stream) {
+  MDM_CHECK_ARG(x && a && t);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
+  const int M = lora_conv_rows(N, H, W);
+  MDM_CHECK_ARG(M >= 1 && C >= 8 && C % 8 == 0);
+  MDM_CHECK_ARG(lora_rank_ok(r));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((M + 16 * DOWN_RT - 1) / (16 * DOWN_RT));
+  const int nt = (r + 15) / 16;
+#define MDM_LORA_DOWN3(TT, NT) \
+  hipLaunchKernelGGL((lora_down_conv3x3_kernel<TT, NT>), grid, dim3(256), 0, st, (const TT*)x, (const TT*)a, (TT*)t, M, H, W, C, r)
+  if (dtype == DT_F32) {
+    if (nt == 1) MDM_LORA_DOWN3(float, 1); else if (nt == 2) MDM_LORA_DOWN3(float, 2); else MDM_LORA_DOWN3(float, 4);
+  } else {
+    if (nt == 1) MDM_LORA_DOWN3(bf16, 1); else if (nt == 2) MDM_LORA_DOWN3(bf16, 2); else MDM_LORA_DOWN3(bf16, 4);
+  }
+#undef MDM_LORA_DOWN3
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_lora_up_add_conv3x3(void* y, const void* t, const void* b, int N, int H, int W, int Cout, int r, float s,
+                                       int accumulate, int dtype, void* stream) {
+  MDM_CHECK_ARG(y && t && b);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
+  const int M = lora_conv_rows(N, H, W);
+  MDM_CHECK_ARG(M >= 1 && Cout >= 8 && Cout % 8 == 0);
+  MDM_CHECK_ARG(lora_rank_ok(r));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int ncol = (Cout + 32 * UP_U - 1) / (32 * UP_U);
+  const long long tiles = (long long)((M + 16 * UP_RT - 1) / (16 * UP_RT)) * ncol;
+  MDM_CHECK_ARG(tiles < (1ll << 31));
+  const int ntiles = (int)tiles;
+  const dim3 grid((ntiles + 3) / 4);
+#define MDM_LORA_UP3(TT, ACC)                                                                                          \
+  hipLaunchKernelGGL((lora_up_add_conv3x3_kernel<TT, ACC>), grid, dim3(256), 0, st, (TT*)y, (const TT*)t, (const TT*)b, M, H, \
+                     W, Cout, r, s, ncol, ntiles)
+  if (dtype == DT_F32) {
+    if (accumulate) MDM_LORA_UP3(float, true); else MDM_LORA_UP3(float, false);
+  } else {
+    if (accumulate) MDM_LORA_UP3(bf16, true); else MDM_LORA_UP3(bf16, false);
+  }
+#undef MDM_LORA_UP3
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_lora_wgrad_conv3x3_plan(int N, int H, int W, int r, int C, int dtype, int* splits_out, size_t* ws_bytes) {
+  MDM_CHECK_ARG(splits_out && ws_bytes);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
+  const int M = lora_conv_rows(N, H, W);
+  MDM_CHECK_ARG(M >= 1 && C >= 8 && C % 8 == 0);
+  MDM_CHECK_ARG(lora_rank_ok(r));
+  int rps, nsplit, groups;
+  lora_wgrad_conv3x3_split(M, C, dtype, &rps, &nsplit, &groups);
+  *splits_out = nsplit;
+  *ws_bytes = (size_t)nsplit * r * 9 * C * sizeof(float);
+  return 0;
+}
+
+extern "C" int mdm_lora_wgrad_conv3x3(const void* p, const void* q, float* d, float* ws, int N, int H, int W, int r, int C,
+                                      float s, int accumulate, int dtype, void* stream) {
+  MDM_CHECK_ARG(p && q && d && ws);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
+  const int M = lora_conv_rows(N, H, W);
+  MDM_CHECK_ARG(M >= 1 && C >= 8 && C % 8 == 0);
+  MDM_CHECK_ARG(lora_rank_ok(r));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int rps, nsplit, groups;
+  lora_wgrad_conv3x3_split(M, C, dtype, &rps, &nsplit, &groups);
+  const int ntiles = nsplit * groups * 9;
+  const dim3 grid((ntiles + 3) / 4);
+  const int nt = (r + 15) / 16;
+#define MDM_LORA_WG3(TT, NT)                                                                                           \
+  hipLaunchKernelGGL((lora_wgrad_conv3x3_kernel<TT, NT>), grid, dim3(256), 0, st, (const TT*)p, (const TT*)q, ws, M, H, W, r, \
+                     C, rps, groups, ntiles)
+  if (dtype == DT_F32) {
+    if (nt == 1) MDM_LORA_WG3(float, 1); else if (nt == 2) MDM_LORA_WG3(float, 2); else MDM_LORA_WG3(float, 4);
+  } else {
+    if (nt == 1) MDM_LORA_WG3(bf16, 1); else if (nt == 2) MDM_LORA_WG3(bf16, 2); else MDM_LORA_WG3(bf16, 4);
+  }
+#undef MDM_LORA_WG3
+  const size_t n4 = (size_t)r * 9 * C / 4;
   hipLaunchKernelGGL(lora_wgrad_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, ws, d, n4, nsplit, s, accumulate);
   MDM_LAUNCH_STATUS();
 }

@@ -1146,6 +1146,129 @@ def lora(y, x, A, B, s):
     return LoraFn.apply(y, x, A, B, float(s))
 
 
+# ---- the 3x3 form: y = conv3x3(x, W) + b + s B conv3x3(x, A), A [r, Cin, 3, 3], on NHWC activations ----------------------
+def _lora_nhwc(act, small, what, c_dim):
+    """``act`` [N, H, W, C] and the packed ``small`` [*, 9, *] (its dimension ``c_dim`` is C): contiguous GPU tensors of one dtype"""
+    _lora_mats(act, small, what)
+    if act.dim() != 4 or small.dim() != 3 or small.shape[1] != 9 or small.shape[c_dim] != act.shape[3]:
+        raise _lib.MdmHipError("%s: activation %s (NHWC) and packed matrix %s do not fit" % (what, tuple(act.shape), tuple(small.shape)))
+
+
+def lora_down_conv3x3(x, a):
+    """t [N, H, W, r]: t[n, y, x] = sum over the 9 taps of x[n, y + ky - 1, x + kx - 1] a[:, 3 ky + kx, :]^T  (x NHWC,
+    a packed [r, 9, C]; pixels outside the image count as zeros)"""
+    _lora_nhwc(x, a, "lora_down_conv3x3", 2)
+    N, H, W, C = x.shape
+    r = a.shape[0]
+    t = torch.empty((N, H, W, r), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().mdm_lora_down_conv3x3(_p(x), _p(a), _p(t), N, H, W, C, r, _dt(x), _stream()), "mdm_lora_down_conv3x3")
+    return t
+
+
+def lora_up_add_conv3x3(y, t, b, s, accumulate=True):
+    """y [N, H, W, Cout] (+)= s sum over the taps of t[n, y + ky - 1, x + kx - 1] b[:, 3 ky + kx, :]^T in place  (t
+    [N, H, W, r], b packed [Cout, 9, r]); ``accumulate=False`` overwrites y without reading it"""
+    _lora_nhwc(y, b, "lora_up_add_conv3x3", 0)
+    _lora_mats(y, t, "lora_up_add_conv3x3")
+    N, H, W, Cout = y.shape
+    r = b.shape[2]
+    if tuple(t.shape) != (N, H, W, r):
+        raise _lib.MdmHipError("lora_up_add_conv3x3: y %s, t %s, b %s do not fit" % (tuple(y.shape), tuple(t.shape), tuple(b.shape)))
+    _lib.check(_lib.lib().mdm_lora_up_add_conv3x3(_p(y), _p(t), _p(b), N, H, W, Cout, r, float(s), 1 if accumulate else 0, _dt(y),
+                                                  _stream()), "mdm_lora_up_add_conv3x3")
+    return y
+
+
+def lora_wgrad_conv3x3(p, q, s, out=None):
+    """d [r, 9, C] fp32: d[:, 3 ky + kx, :] = s sum over the pixels of p[n, y, x]^T q[n, y + ky - 1, x + kx - 1]  (p
+    [N, H, W, r], q [N, H, W, C]); with ``out`` the result is ADDED into it.  Deterministic (no atomics)."""
+    _lora_mats(q, p, "lora_wgrad_conv3x3")
+    if q.dim() != 4 or p.dim() != 4 or p.shape[:3] != q.shape[:3]:
+        raise _lib.MdmHipError("lora_wgrad_conv3x3: p %s and q %s must be NHWC tensors over the same pixels" % (tuple(p.shape), tuple(q.shape)))
+    N, H, W, C = q.shape
+    r = p.shape[3]
+    L = _lib.lib()
+    splits, wsb = ctypes.c_int(0), ctypes.c_size_t(0)
+    _lib.check(L.mdm_lora_wgrad_conv3x3_plan(N, H, W, r, C, _dt(q), ctypes.byref(splits), ctypes.byref(wsb)), "mdm_lora_wgrad_conv3x3_plan")
+    ws = _f32_ws(wsb.value, q.device)
+    d = torch.empty((r, 9, C), dtype=torch.float32, device=q.device) if out is None else out
+    if d.dtype != torch.float32 or not d.is_contiguous() or tuple(d.shape) != (r, 9, C):
+        raise _lib.MdmHipError("lora_wgrad_conv3x3: out must be a contiguous fp32 [%d, 9, %d] tensor" % (r, C))
+    _lib.check(L.mdm_lora_wgrad_conv3x3(_p(p), _p(q), _p(d), _p(ws), N, H, W, r, C, float(s), 0 if out is None else 1, _dt(q),
+                                        _stream()), "mdm_lora_wgrad_conv3x3")
+    return d
+
+
+def _lora_conv_packs(A, B, dtype):
+    """(A as [r, 9, C], its flipped transpose [C, 9, r] with [c][tap][j] = A[j][8 - tap][c], B [N, r], B^T [r, N]) of the
+    activation dtype for A [r, C, 3, 3], B [N, r]; cached and re-made into the same buffers as _lora_packs does"""
+    ent = _cache_slot(A)
+    key = ("lora3x3", dtype)
+    ver = (A._version, B._version, A.data_ptr(), B.data_ptr(), _pack_epoch)
+    if key in ent and ent[key][0] == ver:
+        return ent[key][1]
+    _require_gpu(A)
+    _require_gpu(B)
+    r, C = A.shape[0], A.shape[1]
+    N = B.shape[0]
+    prev = ent[key][1] if key in ent else None
+    if prev is None or prev[0].shape != (r, 9, C) or prev[2].shape != B.shape or prev[0].device != A.device:
+        prev = tuple(torch.empty(shp, dtype=dtype, device=A.device) for shp in ((r, 9, C), (C, 9, r), (N, r), (r, N)))
+    with torch.no_grad():
+        prev[0].view(r, 3, 3, C).copy_(A.permute(0, 2, 3, 1))
+        prev[1].view(C, 3, 3, r).copy_(A.flip(2, 3).permute(1, 2, 3, 0))
+        prev[2].copy_(B)
+        prev[3].copy_(B.t())
+    ent[key] = (ver, prev)
+    return prev
+
+
+class LoraConvFn(torch.autograd.Function):
+    """y += s conv3x3(x, A) B^T, IN PLACE on y = the base 3x3 convolution's fresh output (as LoraFn).  x [N, H, W, C] is
+    that convolution's input; A [r, C, 3, 3], B [N, r] are the fp32 adapter parameters."""
+
+    @staticmethod
+    def forward(ctx, y, x, A, B, s):
+        _require_gpu(x)
+        _require_gpu(y)
+        if A.dim() != 4 or tuple(A.shape[2:]) != (3, 3) or B.dim() != 2 or x.dim() != 4 or not y.is_contiguous() or y.dtype != x.dtype \
+                or tuple(y.shape) != tuple(x.shape[:3]) + (B.shape[0],) or x.shape[3] != A.shape[1] or B.shape[1] != A.shape[0]:
+            raise _lib.MdmHipError("lora_conv: y %s / x %s / A %s / B %s do not fit (x, y NHWC; y contiguous, of x's dtype)"
+                                   % (tuple(y.shape), tuple(x.shape), tuple(A.shape), tuple(B.shape)))
+        x = _c(x)
+        r, N = A.shape[0], B.shape[0]
+        a_p, _, b_c, _ = _lora_conv_packs(A, B, x.dtype)
+        t = lora_down_conv3x3(x, a_p)
+        lora_up_add(y.view(-1, N), t.view(-1, r), b_c, s)
+        ctx.mark_dirty(y)
+        ctx.save_for_backward(x, t, A, B)
+        ctx.s = s
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, t, A, B = ctx.saved_tensors
+        r, C = A.shape[0], A.shape[1]
+        N = B.shape[0]
+        dy2 = _c(dy).reshape(-1, N)
+        _, af_c, _, bt_c = _lora_conv_packs(A, B, x.dtype)
+        dx = dA = dB = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            g = lora_down(dy2, bt_c).view(x.shape[:3] + (r,))             # G = dY B
+            if ctx.needs_input_grad[1]:                                   # the low-rank part of dX: the transposed 3x3 of G
+                dx = lora_up_add_conv3x3(torch.empty_like(x), g, af_c, ctx.s, accumulate=False)
+            if ctx.needs_input_grad[2]:                                   # [r, 9, C] -> A's [r, C, 3, 3]
+                dA = lora_wgrad_conv3x3(g, x, ctx.s).view(r, 3, 3, C).permute(0, 3, 1, 2).contiguous()
+        if ctx.needs_input_grad[3]:
+            dB = lora_wgrad(t.view(-1, r), dy2, ctx.s).t()                # (s T^T dY)^T
+        return dy, dx, dA, dB, None
+
+
+def lora_conv(y, x, A, B, s):
+    """the adapter term of one 3x3 convolution, added into its output y (returned): see LoraConvFn"""
+    return LoraConvFn.apply(y, x, A, B, float(s))
+
+
 # --------------------------------------------------------------------------------------
 # normalisation
 # --------------------------------------------------------------------------------------

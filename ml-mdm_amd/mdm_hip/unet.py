@@ -108,6 +108,8 @@ def compute_dtype() -> torch.dtype:
 class ResNet(nn.Module):
     """GN+SiLU -> 3x3 -> GN*(1+ta)+tb -> SiLU -> 3x3 (zero-init) + shortcut   (reference unet.py:193-238)."""
 
+    _lora = None   # low-rank adapters on conv1 / conv2 / conv3 (mdm_hip/lora.py); not a submodule: the state dict stays the reference's
+
     def __init__(self, time_emb_channels, config: ResNetConfig):
         super().__init__()
         self.config = config
@@ -131,7 +133,11 @@ class ResNet(nn.Module):
             h, x, tap[0][tap[1]] = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=2)
         else:
             h, x = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=True)
-        h = ops.conv(h, self.conv1.weight, self.conv1.bias)
+        lo = self._lora
+        if lo is None:
+            h = ops.conv(h, self.conv1.weight, self.conv1.bias)
+        else:
+            h = lo.apply("conv1", ops.conv(h, self.conv1.weight, self.conv1.bias), h)
         if isinstance(temb_act, TimeStates):
             film = temb_act.film.get(id(self))
             if film is None:
@@ -146,7 +152,11 @@ class ResNet(nn.Module):
         shortcut = x
         if self.config.output_channels != self.config.num_channels:
             shortcut = ops.conv(x, self.conv3.weight, self.conv3.bias)
-        return ops.conv(h, self.conv2.weight, self.conv2.bias, residual=shortcut)
+            if lo is not None:
+                shortcut = lo.apply("conv3", shortcut, x)
+        out = ops.conv(h, self.conv2.weight, self.conv2.bias, residual=shortcut)
+        # the residual went in with the base convolution's epilogue; the adapter term adds behind it (linear: exact)
+        return out if lo is None else lo.apply("conv2", out, h)
 
 
 class TimeStates:

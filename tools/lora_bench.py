@@ -10,7 +10,11 @@ median [p10-p90].
   leg 2  step time: ``trainer.train_batch`` on its plain path with every weight trainable (AdamW over the model), against
          the LoRA step (frozen base, AdamW over the adapters only)
   leg 3  the three kernels alone at M = 16 384, C = 768, N in {768, 1536, 2304}: achieved GB/s over the bytes each must
-         move (24 launches on rotating operands, larger together than the last-level cache, replayed as one hipGraph)"""
+         move (24 launches on rotating operands, larger together than the last-level cache, replayed as one hipGraph)
+  --conv the same for adapters on the ResNet convolutions (``conv_targets``, rank ``--conv-rank``) INSTEAD of legs 1-3:
+         forward + backward with the base frozen, without against with conv adapters, on UNet-64 at ``--batch`` and on
+         nested-256 at ``--nested-batch`` with adapters on the OUTER net's ResNets only; then the three 3x3 kernels alone
+         at the outer net's first level (256 x 256 x 64) and at UNet-64's (64 x 64 x 256)"""
 import argparse
 import json
 import os
@@ -164,6 +168,95 @@ def kernel_legs(a, base):
     return res
 
 
+def conv_overhead_legs(a, base):
+    out = []
+    for model, batch, sides in (("unet64", a.batch, [64]), ("nested256 (adapters on the outer net only)", a.nested_batch, [256, 64])):
+        nested = len(sides) > 1
+
+        def build():
+            torch.manual_seed(0)
+            net = mdm_hip.NestedUNet(3, 3, configs.nested256_config(2048)) if nested else mdm_hip.UNet(3, 3, configs.unet64_config(2048))
+            net.load_state_dict(randomize_zero_params(net.state_dict(), seed=1))
+            return net.to(DEV)
+
+        net_f, net_l = build(), build()
+        for p in net_f.parameters():
+            p.requires_grad = False
+        ad = lora.attach(net_l, targets=(), conv_targets=lora.CONV_TARGETS, conv_rank=a.conv_rank)
+        _seeded_b(ad)
+        active = 0
+        for name, m in net_l.named_modules():
+            if getattr(m, "_lora", None) is not None:
+                if nested and name.startswith("inner_unet."):
+                    m._lora = None            # the outer net's cost alone: the inner net runs as in the other leg
+                else:
+                    active += len(m._lora.pairs)
+        for net in (net_f, net_l):           # one cheap trainable tensor at the very start: backward walks the whole net
+            net.conv_in.bias.requires_grad = True
+        g = torch.Generator().manual_seed(2)
+        xs = [torch.randn(batch, 3, sd, sd, generator=g).to(DEV) for sd in sides]
+        t = torch.randint(0, 1000, (batch,), generator=g).to(DEV)
+        cond, mask = torch.randn(batch, 32, 2048, generator=g).to(DEV), torch.ones(batch, 32).to(DEV)
+
+        def run(vm):
+            def go():
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    outs = vm(xs if nested else xs[0], t, cond, mask, {})
+                sum(o.float().square().mean() for o in (outs if isinstance(outs, (list, tuple)) else [outs])).backward()
+            return go
+
+        res = dict(base, model=model, batch=batch, rank=a.conv_rank, leg="conv adapter overhead: forward + backward, frozen base",
+                   unit="ms per call", adapters=active)
+        res["ms"] = _alternate({"frozen_no_adapters": run(net_f), "frozen_with_conv_adapters": run(net_l)}, a)
+        res["adapters_minus_none_median_ms"] = round(res["ms"]["frozen_with_conv_adapters"]["median"] - res["ms"]["frozen_no_adapters"]["median"], 4)
+        out.append(res)
+        del net_f, net_l, ad
+        torch.cuda.empty_cache()
+    return out
+
+
+def conv_kernel_legs(a, base):
+    bf, r, out = torch.bfloat16, a.conv_rank, []
+    g = torch.Generator().manual_seed(4)
+    for (N, H, W, C, nbuf) in ((4, 256, 256, 64, 16), (64, 64, 64, 256, 16)):
+        M = N * H * W
+        res = dict(base, leg="3x3 kernel rates", unit="GB/s over the bytes the kernel must move from / to HBM", N=N, H=H, W=W, C=C, r=r,
+                   rank=r, rotating_buffers=nbuf, streaming_yardstick="concat_kernel 6.1 TB/s (profiles/)", kernels={})
+        xs = [torch.randn(N, H, W, C, generator=g).to(bf).to(DEV) for _ in range(nbuf)]
+        am = (torch.randn(r, 9, C, generator=g) / (9 * C) ** 0.5).to(bf).to(DEV)
+        bm = (torch.randn(C, 9, r, generator=g) * 0.02).to(bf).to(DEV)
+        ts = [ops.lora_down_conv3x3(x, am) for x in xs]
+
+        def rate(launch, nbytes):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                launch(0)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for k in range(nbuf):
+                    launch(k)
+            t = []
+            for it in range(a.warmup + a.calls):
+                ms = _timed(graph.replay) / nbuf
+                if it >= a.warmup:
+                    t.append(ms)
+            st = _stats(t)
+            return {"us": round(st["median"] * 1e3, 2), "us_p10_p90": [round(v * 1e3, 2) for v in st["p10_p90"]], "bytes": nbytes,
+                    "GBps": round(nbytes / (st["median"] * 1e-3) / 1e9, 1)}
+
+        res["kernels"]["lora_down_conv3x3"] = rate(lambda k: ops.lora_down_conv3x3(xs[k], am), M * C * 2 + M * r * 2 + r * 9 * C * 2)
+        res["kernels"]["lora_up_add_conv3x3 (overwrite: the backward's dX)"] = rate(
+            lambda k: ops.lora_up_add_conv3x3(xs[k], ts[k], bm, 1e-3, accumulate=False), M * C * 2 + M * r * 2 + C * 9 * r * 2)
+        res["kernels"]["lora_wgrad_conv3x3 (slabs + reduce)"] = rate(lambda k: ops.lora_wgrad_conv3x3(ts[k], xs[k], 1.0),
+                                                                     M * C * 2 + M * r * 2 + r * 9 * C * 4)
+        out.append(res)
+        del xs, ts
+        torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -171,13 +264,21 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--legs", default="1,2,3")
+    ap.add_argument("--conv", action="store_true", help="the conv-adapter legs instead of legs 1-3")
+    ap.add_argument("--conv-rank", type=int, default=8)
+    ap.add_argument("--nested-batch", type=int, default=16)
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     a = ap.parse_args()
     base = {"model": "unet64", "batch": a.batch, "rank": a.rank, "calls": a.calls, "warmup": a.warmup,
             "setup": "bf16 autocast, random weights, legs alternated call by call in one process, device events"}
-    for leg, fn in (("1", overhead_legs), ("2", step_legs), ("3", kernel_legs)):
-        if leg in a.legs.split(","):
-            res = fn(a, base)
+
+    def one(fn):
+        return lambda a, base: [fn(a, base)]
+
+    legs = [("conv", conv_overhead_legs), ("conv", conv_kernel_legs)] if a.conv else \
+        [(leg, one(fn)) for leg, fn in (("1", overhead_legs), ("2", step_legs), ("3", kernel_legs)) if leg in a.legs.split(",")]
+    for _, fn in legs:
+        for res in fn(a, base):
             res["max_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2**30, 2)
             print(json.dumps(res), flush=True)
             if a.out:
