@@ -423,6 +423,25 @@ int mdm_lora_wgrad_conv3x3_plan(int N, int H, int W, int r, int C, int dtype, in
 int mdm_lora_wgrad_conv3x3(const void* p, const void* q, float* d, float* ws, int N, int H, int W, int r, int C, float s,
                            int accumulate, int dtype, void* stream);
 
+/* ---- MXFP8 sampling path for the plain-GEMM layers of SelfAttention (pure additions; inference only) ------------------
+ * OCP MX "MXFP8 E4M3": a block is 32 consecutive K elements of one row and carries one E8M0 scale byte s (2^(s - 127)) and
+ * 32 e4m3fn codes.  amax = the block's largest magnitude: e = clamp(floor(log2 amax) - 8, -127, 127), s = e + 127
+ * (amax == 0: s = 127), code = RNE_e4m3fn(clamp(x 2^-e, -448, 448)).  Rows are padded to Kp = K rounded up to 128 with
+ * code 0 / scale 127; codes [rows, Kp] and scales [rows, Kp / 32] are both row-major.  Activations [M, K] and weights
+ * [N, K] (the logical (Cout, Cin) of a 1x1 weight) use the same form.  Non-finite input is not handled.
+ *   mdm_mx8_quant   x [M, K] (MDM_F32 | MDM_BF16, K % 8 == 0) -> q_out [M, Kp], s_out [M, Kp / 32].  One pass; serves the
+ *                   activations of models/unet.py:296-313 on every call and their weights once per parameter version
+ *                   (from the fp32 masters).
+ *   mdm_mx8_gemm    Y [M, N] = A W^T (+ bias, fp32 [N]) (+ GELU when act == MDM_ACT_GELU) (+ residual, bf16 [M, N]), in this
+ *                   order and with the activation applied to the bf16-rounded value as in mdm_conv_fwd, on
+ *                   v_mfma_scale_f32_16x16x128_f8f6f4 with fp32 accumulation: the projections qkv (models/unet.py:298),
+ *                   proj_out (:310) and the FFN pair (:311-312).  Either y (bf16 [M, N]) or q_out / s_out is given:
+ *                   the latter receive mdm_mx8_quant of the bf16 result ([M, Np], [M, Np / 32], Np = N rounded up to
+ *                   128), bit for bit.  N % 32 == 0, Kp % 128 == 0, M >= 1; no split-K, two runs are bit-identical. */
+int mdm_mx8_quant(const void* x, int dtype, int M, int K, int Kp, void* q_out, void* s_out, void* stream);
+int mdm_mx8_gemm(const void* qa, const void* sa, const void* qw, const void* sw, const float* bias, const void* residual,
+                 void* y, void* q_out, void* s_out, int M, int N, int Kp, int act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

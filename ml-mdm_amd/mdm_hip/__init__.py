@@ -13,6 +13,7 @@ Layout of the package
   text_encoder.py T5Encoder / LanguageModel: the frozen flan-T5 text encoder on packed tokens (mirror of
                   ml_mdm.language_models.factory)
   lora.py         LoRA adapters on the attention projections: attach / merge / unmerge / detach
+  fp8.py          opt-in MXFP8 (weights and activations) sampling path of the attention-layer 1x1 GEMMs: attach / detach
 """
 import os as _os
 
@@ -35,6 +36,7 @@ from .nested_unet import (  # noqa: E402  # noqa: F401
 from .text_encoder import LanguageModel, T5Encoder, T5EncoderConfig  # noqa: F401,E402
 from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
 from . import lora  # noqa: F401,E402
+from . import fp8  # noqa: F401,E402
 
 __all__ = [
     "UNet",
@@ -49,4 +51,5 @@ __all__ = [
     "T5EncoderConfig",
     "LanguageModel",
     "lora",
+    "fp8",
 ]

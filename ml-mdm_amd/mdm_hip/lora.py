@@ -183,6 +183,8 @@ class LoraAdapters(nn.Module):
         if not self.merged:
             raise RuntimeError("the adapters are not merged")
         self._attached()
+        if any(getattr(layer, "_fp8", None) is not None for _, layer, _, _, _, _ in self._entries):
+            raise RuntimeError("the model's attention layers run in MXFP8 (mdm_hip.fp8): detach() the fp8 handle before unmerge()")
         self._fold(-1.0)
         self.merged = False
 
@@ -244,5 +246,8 @@ def attach(vision_model, rank=16, alpha=None, targets=TARGETS, freeze_base=True,
         raise ValueError("the model has no ResNet block to adapt")
     if any(m._lora is not None for m in layers + resnets):
         raise RuntimeError("the model already has adapters attached: detach() them first")
+    if targets and any(m._fp8 is not None for m in layers):
+        raise RuntimeError("the model's attention layers run in MXFP8 (mdm_hip.fp8): detach() the fp8 handle first, then attach "
+                           "and merge() the adapters, then attach fp8 again")
     return LoraAdapters(vision_model, rank, rank if alpha is None else alpha, targets, seed, freeze_base, conv_targets, conv_rank,
                         conv_alpha)

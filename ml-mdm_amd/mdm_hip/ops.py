@@ -1270,6 +1270,109 @@ def lora_conv(y, x, A, B, s):
 
 
 # --------------------------------------------------------------------------------------
+# MXFP8 sampling path (mdm_hip/fp8.py, csrc/fp8.hip): E4M3 codes + one E8M0 scale byte per 32 K elements.  No autograd.
+# --------------------------------------------------------------------------------------
+class Mx8:
+    """rows [M, K] in MXFP8: ``q`` uint8 [M, Kp] (e4m3fn codes), ``s`` uint8 [M, Kp / 32] (E8M0 scale bytes), Kp = K
+    rounded up to 128 (padding: code 0, scale 127)"""
+
+    __slots__ = ("q", "s", "K")
+
+    def __init__(self, q, s, K):
+        self.q, self.s, self.K = q, s, K
+
+    @property
+    def rows(self):
+        return self.q.shape[0]
+
+    @property
+    def Kp(self):
+        return self.q.shape[1]
+
+
+def _mx8_inference_only(*tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise _lib.MdmHipError("the MXFP8 layers are inference-only (no backward): run them under torch.no_grad()")
+
+
+def mx8_quant(x, out=None):
+    """x [..., K] (bf16 or fp32, K % 8 == 0) -> Mx8 of the rows [M, K].  ``out``: an Mx8 of the same shape to write into."""
+    _require_gpu(x)
+    _mx8_inference_only(x)
+    x = _c(x.detach())
+    K = x.shape[-1]
+    M = x.numel() // K
+    if K % 8 or M < 1:
+        raise _lib.MdmHipError("mx8_quant: %d rows of %d elements; the row length must be a multiple of 8" % (M, K))
+    Kp = _round_up(K, 128)
+    if out is None:
+        out = Mx8(torch.empty((M, Kp), dtype=torch.uint8, device=x.device),
+                  torch.empty((M, Kp // 32), dtype=torch.uint8, device=x.device), K)
+    _lib.check(_lib.lib().mdm_mx8_quant(_p(x), _dt(x), M, K, Kp, _p(out.q), _p(out.s), _stream()), "mdm_mx8_quant")
+    return out
+
+
+def mx8_gemm(a, w, bias=None, residual=None, gelu=False, emit=False):
+    """Y [M, N] = a w^T (+ bias) (+ GELU) (+ residual) for Mx8 operands a [M, K], w [N, K]: a bf16 tensor, or with
+    ``emit`` the Mx8 of that bf16 tensor (bit-equal to ``mx8_quant`` of it) for a GEMM that consumes it directly.
+    bias fp32 [N]; residual bf16 with M N elements."""
+    M, N = a.rows, w.rows
+    if a.Kp != w.Kp or a.K != w.K:
+        raise _lib.MdmHipError("mx8_gemm: the operands have %d and %d columns" % (a.K, w.K))
+    if N % 32:
+        raise _lib.MdmHipError("mx8_gemm: %d output channels; the MXFP8 GEMM needs a multiple of 32" % N)
+    _mx8_inference_only(bias, residual)
+    dev = a.q.device
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+        raise _lib.MdmHipError("mx8_gemm: the bias must be a contiguous fp32 vector of %d elements" % N)
+    if residual is not None:
+        _require_gpu(residual)
+        if residual.dtype != torch.bfloat16 or residual.numel() != M * N:
+            raise _lib.MdmHipError("mx8_gemm: the residual must be a bf16 tensor of %d x %d elements (got %s, %d)"
+                                   % (M, N, residual.dtype, residual.numel()))
+        residual = _c(residual.detach())
+    act = 1 if gelu else 0
+    L = _lib.lib()
+    if emit:
+        Np = _round_up(N, 128)
+        out = Mx8(torch.empty((M, Np), dtype=torch.uint8, device=dev), torch.empty((M, Np // 32), dtype=torch.uint8, device=dev), N)
+        _lib.check(L.mdm_mx8_gemm(_p(a.q), _p(a.s), _p(w.q), _p(w.s), _p(bias), _p(residual), None, _p(out.q), _p(out.s),
+                                  M, N, a.Kp, act, _stream()), "mdm_mx8_gemm")
+        return out
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+    _lib.check(L.mdm_mx8_gemm(_p(a.q), _p(a.s), _p(w.q), _p(w.s), _p(bias), _p(residual), _p(y), None, None,
+                              M, N, a.Kp, act, _stream()), "mdm_mx8_gemm")
+    return y
+
+
+def packed_weight_mx8(weight: torch.Tensor, bias):
+    """(Mx8 of the weight as [Cout, Cin], fp32 bias or None) for a reference-layout 1x1 weight ``(Cout, Cin[, 1, 1])``,
+    quantised from the fp32 master and cached per parameter version exactly like ``packed_weight``: a ``load_state_dict``,
+    an EMA swap or a LoRA ``merge()`` re-quantises on the next use (into the same buffers)."""
+    ent = _cache_slot(weight)
+    ver = (weight._version, None if bias is None else bias._version, weight.data_ptr(), _pack_epoch)
+    if "mx8" in ent and ent["mx8"][0] == ver:
+        return ent["mx8"][1]
+    _require_gpu(weight)
+    if weight.dim() not in (2, 4) or (weight.dim() == 4 and tuple(weight.shape[2:]) != (1, 1)):
+        raise _lib.MdmHipError("packed_weight_mx8: only 1x1 / linear weights have an MXFP8 form (got %s)" % (tuple(weight.shape),))
+    cout, cin = weight.shape[0], weight.shape[1]
+    prev, bp = ent["mx8"][1] if "mx8" in ent else (None, None)
+    if prev is not None and (tuple(prev.q.shape) != (cout, _round_up(cin, 128)) or prev.q.device != weight.device):
+        prev = bp = None
+    with torch.no_grad():
+        wq = mx8_quant(weight.detach().float().reshape(cout, cin), out=prev)
+        if bias is None:
+            bp = None
+        elif bp is not None and bp.shape == bias.shape and bp.device == bias.device:
+            bp.copy_(bias.detach())     # the fp32 copy keeps its buffer too
+        else:
+            bp = bias.detach().float().contiguous().clone()
+    ent["mx8"] = (ver, (wq, bp))
+    return ent["mx8"][1]
+
+
+# --------------------------------------------------------------------------------------
 # normalisation
 # --------------------------------------------------------------------------------------
 def _gn_ws(N, HW, C, G, device):

@@ -223,12 +223,18 @@ class SelfAttention(nn.Module):
     # low-rank adapters of this layer's projections (mdm_hip.lora.attach): a plain handle, not a submodule -- the state
     # dict keeps the reference's keys.  None: no line below launches anything it did not launch before.
     _lora = None
+    # MXFP8 sampling path of the plain-GEMM projections (mdm_hip.fp8.attach): the same kind of handle.  None: as above.
+    _fp8 = None
 
     def forward(self, x, cond=None, cond_mask=None):
         N, H, W, C = x.shape
         lora = self._lora
+        fp8 = self._fp8
         hn, x = ops.group_norm(x, self.norm.weight, self.norm.bias, 32, self.norm.eps, passthrough=True)
-        qkv = ops.conv(hn, self.qkv.weight, self.qkv.bias)
+        if fp8 is not None and fp8.on("qkv"):
+            qkv = fp8.conv(hn, self.qkv)
+        else:
+            qkv = ops.conv(hn, self.qkv.weight, self.qkv.bias)
         if lora is not None:
             qkv = lora.apply("qkv", qkv, hn)
         kvc = None
@@ -253,12 +259,18 @@ class SelfAttention(nn.Module):
                     kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
         a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
         a = a.reshape(N, H, W, C)
-        x = ops.conv(a, self.proj_out.weight, self.proj_out.bias, residual=x)
+        if fp8 is not None and fp8.on("proj_out"):
+            x = fp8.conv(a, self.proj_out, residual=x)
+        else:
+            x = ops.conv(a, self.proj_out.weight, self.proj_out.bias, residual=x)
         if lora is not None:
             x = lora.apply("proj_out", x, a)
         if self.ffn is not None:
             fn, x = ops.group_norm(x, self.ffn[0].weight, self.ffn[0].bias, 32, self.ffn[0].eps, passthrough=True)
-            x = ops.ffn(fn, self.ffn[1].weight, self.ffn[1].bias, self.ffn[3].weight, self.ffn[3].bias, residual=x)
+            if fp8 is not None and fp8.on("ffn"):
+                x = fp8.ffn(fn, self.ffn[1], self.ffn[3], residual=x)
+            else:
+                x = ops.ffn(fn, self.ffn[1].weight, self.ffn[1].bias, self.ffn[3].weight, self.ffn[3].bias, residual=x)
         return x
 
 

@@ -4,7 +4,8 @@ LDS / global store) with too few wait states when the read sits on the TAKEN edg
 recognizer covered the fall-through path only (conv3x3_direct_kernel<64, 64, 8, 32, 4>, HISTORY.md section 4.1e).
 Walks every path of up to 10 wait states after each v_mfma (following branches) and reports reads of its destination
 registers that come earlier than `MIN_WS` (the compiler itself leaves 11 in straight-line code).  CPU-only:
-   python tools/mfma_hazard_scan.py            # compiles csrc/gemm_conv.hip and attention.hip to ISA, exits 1 on a finding
+   python tools/mfma_hazard_scan.py            # csrc/gemm_conv.hip, attention.hip and fp8.hip to ISA; exits 1 on a finding
+   python tools/mfma_hazard_scan.py fp8.hip    # one source only
 Also checks, on the same ISA, that no kernel spills more than SPILL_CAP vector registers, and that the bias-gradient dot
 products of conv_wgrad_bl_kernel still sit behind scalar branches (round 5: as plain code hipcc if-converted them into every
 wave's instruction stream -- all 64 v_dot2c + a v_cndmask per row -- which is what made one block in nine the tail of the
@@ -104,8 +105,8 @@ def unguarded_dot2(path):
 
 
 def loads_between_wide_stores(path):
-    """Round 6: the chunked store loops of the GEMM epilogues (conv_gemm_bl_kernel / conv_gemm_kernel) and of the slab form of
-    conv_wgrad_bl_kernel must not LOAD between their 8 / 16-byte stores.  gfx950 counts loads and stores in one in-order
+    """Round 6: the chunked store loops of the GEMM epilogues (conv_gemm_bl_kernel / conv_gemm_kernel, and mx8_gemm_kernel of
+    fp8.hip) and of the slab form of conv_wgrad_bl_kernel must not LOAD between their 8 / 16-byte stores.  gfx950 counts loads and stores in one in-order
     counter (vmcnt), so the wait for a load that follows a store is a wait for that store's acknowledgement -- rounds 3-5 had
     a vector load (a development knob read from a __device__ variable) and a join-point wait in front of every chunk, and the
     "additive store phase" they produced cost 2.1 ms per train step.  A parity test cannot see this.  Flags every vector load
@@ -113,7 +114,7 @@ def loads_between_wide_stores(path):
     not looked at; the arena form of the weight gradient loads one row AHEAD of its stores by design and is exempt)."""
     txt = open(path).read()
     out = []
-    for km in re.finditer(r"^(\S*(?:conv_gemm_bl_kernel|conv_gemm_kernel)\S*):\s*; @\1\n", txt, re.M):
+    for km in re.finditer(r"^(\S*(?:conv_gemm_bl_kernel|conv_gemm_kernel|mx8_gemm_kernel)\S*):\s*; @\1\n", txt, re.M):
         name, i = km.group(1), km.end()
         code = [ln.strip() for ln in txt[i:txt.find(".Lfunc_end", i)].split("\n")]
         code = [ln for ln in code if ln and not ln.startswith(";") and not ln.startswith(".")]
@@ -131,7 +132,7 @@ def loads_between_wide_stores(path):
 
 
 def main():
-    srcs = sys.argv[1:] or ["gemm_conv.hip", "attention.hip"]
+    srcs = sys.argv[1:] or ["gemm_conv.hip", "attention.hip", "fp8.hip"]
     bad = 0
     with tempfile.TemporaryDirectory() as td:
         for s in srcs:
@@ -162,6 +163,7 @@ def main():
                 for name, ln in ung[:4]:
                     print("      %s: %s" % (name[:60], ln))
                 bad += len(ung)
+            if os.path.basename(src) in ("gemm_conv.hip", "fp8.hip"):
                 lw = loads_between_wide_stores(out)
                 print("   GEMM epilogues: %d vector loads between two wide stores of a chunked store loop" % len(lw))
                 for name, ln in lw[:4]:
