@@ -442,6 +442,22 @@ int mdm_mx8_quant(const void* x, int dtype, int M, int K, int Kp, void* q_out, v
 int mdm_mx8_gemm(const void* qa, const void* sa, const void* qw, const void* sw, const float* bias, const void* residual,
                  void* y, void* q_out, void* s_out, int M, int N, int Kp, int act, void* stream);
 
+/* ---- MXFP8 for the 3x3 convolutions of ResNet (pure additions; inference only) -----------------------------------------
+ * conv1 and conv2 of models/unet.py:223-238 (stride 1, zero padding 1, NHWC) as an implicit GEMM over the SAME operand
+ * format: the activation is mdm_mx8_quant of the NHWC tensor seen as [M = N H W, Cin] -- a block is 32 channels of one
+ * pixel, so one quantisation serves all nine taps -- and the weight (Cout, Cin, 3, 3) is quantised as [Cout 9, Cin] with
+ * row o 9 + ky 3 + kx (a block is 32 input channels of one (o, tap)).
+ *   mdm_mx8_quant_zrow  mdm_mx8_quant that writes M + 1 rows: q_out [M + 1, Kp], s_out [M + 1, Kp / 32]; row M is the zero
+ *                       row (codes 0, scales 127) that the taps outside the image read.  One launch, as mdm_mx8_quant.
+ *   mdm_mx8_conv3x3     Y [N, H, W, Cout] = bf16(conv3x3(A, W) + bias, fp32 [Cout]) (+ residual, bf16 [N, H, W, Cout]), the
+ *                       order and rounding of mdm_mx8_gemm, fp32 accumulation over 9 taps x Kp / 128 k-tiles (tap outer).
+ *                       qa / sa: the M + 1 rows of mdm_mx8_quant_zrow; qw / sw: [Cout 9, Kp], [Cout 9, Kp / 32].  A tap is
+ *                       valid by (y + dy, x + dx), never by the flat row index.  Cin % 32 == 0, Cout % 32 == 0, any
+ *                       N, H, W >= 1 with N H W below 2^31 - W - 130; no split-K, two runs are bit-identical. */
+int mdm_mx8_quant_zrow(const void* x, int dtype, int M, int K, int Kp, void* q_out, void* s_out, void* stream);
+int mdm_mx8_conv3x3(const void* qa, const void* sa, const void* qw, const void* sw, const float* bias, const void* residual,
+                    void* y, int N, int H, int W, int Cin, int Cout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,15 @@
 // Structure: 128 x 128 x 128 tile, 4 waves (2 x 2, 64 x 64 each), two LDS stages filled by global_load_lds (16-byte copies
 // for the codes, 4-byte copies for the tile's 128 + 128 scale dwords), one barrier per k-tile.  The XOR swizzle of the
 // 128-byte LDS rows sits on the SOURCE address (the DMA writes lane-linear).  Deterministic: no split-K.
+//
+// The 3x3 convolutions of ResNet (reference models/unet.py:223-238) run on the same kernel as an implicit GEMM (CONV): the
+// k-loop walks 9 taps x Kp / 128 tiles, tap outer, and for tap (dy, dx) tile row m = (b, y, x) takes its 128-byte code row and
+// its scale dword from row m + dy W + dx of the SAME quantised activation (blocks run along the channels of one pixel, so one
+// quantisation serves all nine taps) -- a row gather on the per-lane DMA source address, nothing else changes.  A tap outside
+// the image, tested on (y, x) and never on the flat index, reads the ZERO ROW: row M of the activation, codes 0 / scale 127,
+// written by the quantiser itself (mdm_mx8_quant_zrow).  The weight is [Cout 9, Kp] with row o 9 + ky 3 + kx.
+#include <climits>
+
 #include "common.hpp"
 
 #include "../../include/mdm_hip.h"
@@ -63,7 +72,7 @@ __device__ __forceinline__ unsigned mx8_gather_scales(unsigned sbyte) {
 
 template <typename T>
 __global__ __launch_bounds__(256) void mx8_quant_kernel(const T* __restrict__ x, unsigned char* __restrict__ q,
-                                                        unsigned char* __restrict__ s, int M, int K, int Kp) {
+                                                        unsigned char* __restrict__ s, int M, int Msrc, int K, int Kp) {
   const int cpr = Kp >> 3;                                   // 8-element pieces per padded row: a multiple of 16
   const size_t total = (size_t)M * cpr;
   const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -73,7 +82,8 @@ __global__ __launch_bounds__(256) void mx8_quant_kernel(const T* __restrict__ x,
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = 0.f;
-  if (valid && k < K) {                                      // K % 8 == 0: a piece is inside the row or in the padding
+  if (valid && k < K && row < (size_t)Msrc) {                // K % 8 == 0: a piece is inside the row or in the padding; rows
+                                                             // Msrc .. M - 1 have no source: code 0, scale 127 (the zero row)
     const T* src = x + row * K + k;
     if constexpr (sizeof(T) == 2) {
       Chunk<bf16> c;
@@ -103,6 +113,7 @@ struct Mx8GemmArgs {
   bf16* y;
   unsigned char *q_out, *s_out;
   int M, N, Kp, act;
+  int H, W;   // CONV: the image; M = batch H W pixels, qa / sa hold M + 1 rows (the zero row last), qw / sw 9 N rows
 };
 
 constexpr int MX_BM = 128, MX_BN = 128;
@@ -113,8 +124,9 @@ constexpr int MX_SMEM = 2 * MX_STAGE;
 constexpr int MX_PITCH = MX_BN * 2 + 16;     // staged bf16 output rows, padded by one chunk
 static_assert(MX_BM * MX_PITCH <= MX_SMEM, "the staged output tile must fit the k-loop's LDS");
 
-template <bool EMIT>
+template <bool EMIT, bool CONV>
 __global__ __launch_bounds__(256) void mx8_gemm_kernel(const Mx8GemmArgs p) {
+  static_assert(!(EMIT && CONV), "the 3x3 form has no emitting epilogue");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -136,9 +148,43 @@ __global__ __launch_bounds__(256) void mx8_gemm_kernel(const Mx8GemmArgs p) {
     a_src[j] = p.qa + (size_t)m * p.Kp + lchunk * 16;
     b_src[j] = p.qw + (size_t)n * p.Kp + lchunk * 16;
   }
+  // CONV: the pixel (y, x) of this thread's four code rows and of its scale row; a row past M gets y = -2, so that no tap of
+  // it is ever inside the image and it reads the zero row (it is never stored)
+  int ry[4], rx[4], sy = -2, sx = 0;
+  if constexpr (CONV) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int m = m0 + lrow + 32 * j, q = m / p.W;
+      rx[j] = m - q * p.W;
+      ry[j] = m < p.M ? q % p.H : -2;
+    }
+    if (tid < MX_BM && m0 + tid < p.M) {
+      const int q = (m0 + tid) / p.W;
+      sx = m0 + tid - q * p.W;
+      sy = q % p.H;
+    }
+  }
   // the tile's scales: one dword (4 blocks = 128 k) per row; threads 0..127 the A rows, 128..255 the W rows
   const unsigned char* sc_src = tid < MX_BM ? p.sa + (size_t)min(m0 + tid, p.M - 1) * sb_row
                                             : p.sw + (size_t)min(n0 + tid - MX_BM, p.N - 1) * sb_row;
+  // CONV: the sources of tap ky 3 + kx -- row m + dy W + dx where (y + dy, x + dx) is inside the image, else the zero row M
+#define MDM_SET_TAP(tap)                                                                                  \
+  {                                                                                                       \
+    const int dy = (tap) / 3 - 1, dx = (tap) - ((tap) / 3) * 3 - 1;                                       \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                       \
+      const bool in = (unsigned)(ry[j] + dy) < (unsigned)p.H && (unsigned)(rx[j] + dx) < (unsigned)p.W;   \
+      const int m = in ? m0 + lrow + 32 * j + dy * p.W + dx : p.M;                                        \
+      const int n = min(n0 + lrow + 32 * j, p.N - 1);                                                     \
+      a_src[j] = p.qa + (size_t)m * p.Kp + lchunk * 16;                                                   \
+      b_src[j] = p.qw + ((size_t)n * 9 + (tap)) * p.Kp + lchunk * 16;                                     \
+    }                                                                                                     \
+    if (tid < MX_BM) {                                                                                    \
+      const bool in = (unsigned)(sy + dy) < (unsigned)p.H && (unsigned)(sx + dx) < (unsigned)p.W;         \
+      sc_src = p.sa + (size_t)(in ? m0 + tid + dy * p.W + dx : p.M) * sb_row;                             \
+    } else {                                                                                              \
+      sc_src = p.sw + ((size_t)min(n0 + tid - MX_BM, p.N - 1) * 9 + (tap)) * sb_row;                      \
+    }                                                                                                     \
+  }
   const int wave_lds = __builtin_amdgcn_readfirstlane(wave * 1024);
   const int wave_sc = __builtin_amdgcn_readfirstlane(wave * 256);
 #define MDM_GLDS(src, lds_ptr, bytes)                                                                     \
@@ -158,13 +204,27 @@ __global__ __launch_bounds__(256) void mx8_gemm_kernel(const Mx8GemmArgs p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int ntiles = p.Kp >> 7;
+  const int ktiles = p.Kp >> 7;
+  const int ntiles = CONV ? 9 * ktiles : ktiles;
+  int tap_n = 0, kk_n = 0;                           // CONV: the tap and the k-tile within it of the tile being staged
+  if constexpr (CONV) MDM_SET_TAP(0);
   MDM_STAGE_TILE(smem, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the LDS-DMA of tile 0 has landed before any wave reads it
   __syncthreads();
   for (int kt = 0; kt < ntiles; ++kt) {
     const char* cur = smem + (kt & 1) * MX_STAGE;
-    if (kt + 1 < ntiles) MDM_STAGE_TILE(smem + ((kt + 1) & 1) * MX_STAGE, kt + 1);
+    if (kt + 1 < ntiles) {
+      if constexpr (CONV) {
+        if (++kk_n == ktiles) {
+          kk_n = 0;
+          ++tap_n;
+          MDM_SET_TAP(tap_n);
+        }
+        MDM_STAGE_TILE(smem + ((kt + 1) & 1) * MX_STAGE, kk_n);
+      } else {
+        MDM_STAGE_TILE(smem + ((kt + 1) & 1) * MX_STAGE, kt + 1);
+      }
+    }
     const char* As = cur;
     const char* Bs = cur + MX_A_BYTES;
     const unsigned* sc = reinterpret_cast<const unsigned*>(cur + MX_A_BYTES + MX_B_BYTES);
@@ -194,6 +254,7 @@ __global__ __launch_bounds__(256) void mx8_gemm_kernel(const Mx8GemmArgs p) {
     __syncthreads();
   }
 #undef MDM_STAGE_TILE
+#undef MDM_SET_TAP
 #undef MDM_GLDS
 
   // ---- epilogue: bf16(acc + bias) staged through LDS as rows of the output tile (a lane owns 4 consecutive channels of
@@ -264,21 +325,33 @@ __global__ __launch_bounds__(256) void mx8_gemm_kernel(const Mx8GemmArgs p) {
 using namespace mdm;
 
 // (models/unet.py:296-313: the operands of the qkv / proj_out / FFN projections in MXFP8)
-extern "C" int mdm_mx8_quant(const void* x, int dtype, int M, int K, int Kp, void* q_out, void* s_out, void* stream) {
+// rows 0 .. Msrc - 1 from x, rows Msrc .. Mout - 1 zero (code 0, scale 127)
+static int mx8_quant_launch(const void* x, int dtype, int Msrc, int Mout, int K, int Kp, void* q_out, void* s_out, void* stream) {
   MDM_CHECK_ARG(x != nullptr && q_out != nullptr && s_out != nullptr);
   MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
-  MDM_CHECK_ARG(M >= 1 && K >= 8 && K % 8 == 0 && Kp == (K + 127) / 128 * 128);
+  MDM_CHECK_ARG(Msrc >= 1 && Mout >= Msrc && K >= 8 && K % 8 == 0 && Kp == (K + 127) / 128 * 128);
+  const int M = Mout;
   const size_t total = (size_t)M * (size_t)(Kp / 8);
   const size_t nb = (total + 255) / 256;
   MDM_CHECK_ARG(nb < (size_t)1 << 31);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(mx8_quant_kernel<bf16>, dim3((unsigned)nb), dim3(256), 0, st, (const bf16*)x, (unsigned char*)q_out,
-                       (unsigned char*)s_out, M, K, Kp);
+                       (unsigned char*)s_out, M, Msrc, K, Kp);
   else
     hipLaunchKernelGGL(mx8_quant_kernel<float>, dim3((unsigned)nb), dim3(256), 0, st, (const float*)x, (unsigned char*)q_out,
-                       (unsigned char*)s_out, M, K, Kp);
+                       (unsigned char*)s_out, M, Msrc, K, Kp);
   MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_mx8_quant(const void* x, int dtype, int M, int K, int Kp, void* q_out, void* s_out, void* stream) {
+  return mx8_quant_launch(x, dtype, M, M, K, Kp, q_out, s_out, stream);
+}
+
+// (models/unet.py:223-238: the activation of conv1 / conv2 with the zero row its out-of-image taps read, in the same launch)
+extern "C" int mdm_mx8_quant_zrow(const void* x, int dtype, int M, int K, int Kp, void* q_out, void* s_out, void* stream) {
+  MDM_CHECK_ARG(M >= 1 && M < INT_MAX);
+  return mx8_quant_launch(x, dtype, M, M + 1, K, Kp, q_out, s_out, stream);
 }
 
 // (models/unet.py:296-313: qkv :298, proj_out :310, the FFN pair :311-312)
@@ -297,14 +370,36 @@ extern "C" int mdm_mx8_gemm(const void* qa, const void* sa, const void* qw, cons
   p.qw = (const unsigned char*)qw; p.sw = (const unsigned char*)sw;
   p.bias = bias; p.res = (const bf16*)residual; p.y = (bf16*)y;
   p.q_out = (unsigned char*)q_out; p.s_out = (unsigned char*)s_out;
-  p.M = M; p.N = N; p.Kp = Kp; p.act = act;
+  p.M = M; p.N = N; p.Kp = Kp; p.act = act; p.H = p.W = 0;
   hipStream_t st = (hipStream_t)stream;
   if (emit) {
-    ensure_dynamic_lds(mx8_gemm_kernel<true>, MX_SMEM);
-    hipLaunchKernelGGL(mx8_gemm_kernel<true>, dim3((unsigned)tiles), dim3(256), MX_SMEM, st, p);
+    ensure_dynamic_lds(mx8_gemm_kernel<true, false>, MX_SMEM);
+    hipLaunchKernelGGL((mx8_gemm_kernel<true, false>), dim3((unsigned)tiles), dim3(256), MX_SMEM, st, p);
   } else {
-    ensure_dynamic_lds(mx8_gemm_kernel<false>, MX_SMEM);
-    hipLaunchKernelGGL(mx8_gemm_kernel<false>, dim3((unsigned)tiles), dim3(256), MX_SMEM, st, p);
+    ensure_dynamic_lds(mx8_gemm_kernel<false, false>, MX_SMEM);
+    hipLaunchKernelGGL((mx8_gemm_kernel<false, false>), dim3((unsigned)tiles), dim3(256), MX_SMEM, st, p);
   }
+  MDM_LAUNCH_STATUS();
+}
+
+// (models/unet.py:223-238: conv1 :225 and conv2 :236 of ResNet, stride 1, zero padding 1)
+extern "C" int mdm_mx8_conv3x3(const void* qa, const void* sa, const void* qw, const void* sw, const float* bias,
+                               const void* residual, void* y, int N, int H, int W, int Cin, int Cout, void* stream) {
+  MDM_CHECK_ARG(qa != nullptr && sa != nullptr && qw != nullptr && sw != nullptr && y != nullptr);
+  MDM_CHECK_ARG(N >= 1 && H >= 1 && W >= 1 && Cin >= 32 && Cin % 32 == 0 && Cout >= 32 && Cout % 32 == 0);
+  const size_t pixels = (size_t)N * (size_t)H * (size_t)W;
+  // a shifted row index m + dy W + dx and the zero row M are formed in int
+  MDM_CHECK_ARG(pixels + (size_t)W + MX_BM + 1 < (size_t)INT_MAX && (size_t)Cout * 9 < (size_t)INT_MAX);
+  const int M = (int)pixels;
+  const size_t tiles = (size_t)((M + MX_BM - 1) / MX_BM) * (size_t)((Cout + MX_BN - 1) / MX_BN);
+  MDM_CHECK_ARG(tiles < (size_t)1 << 31);
+  Mx8GemmArgs p;
+  p.qa = (const unsigned char*)qa; p.sa = (const unsigned char*)sa;
+  p.qw = (const unsigned char*)qw; p.sw = (const unsigned char*)sw;
+  p.bias = bias; p.res = (const bf16*)residual; p.y = (bf16*)y;
+  p.q_out = nullptr; p.s_out = nullptr;
+  p.M = M; p.N = Cout; p.Kp = (Cin + 127) / 128 * 128; p.act = MDM_ACT_NONE; p.H = H; p.W = W;
+  ensure_dynamic_lds(mx8_gemm_kernel<false, true>, MX_SMEM);
+  hipLaunchKernelGGL((mx8_gemm_kernel<false, true>), dim3((unsigned)tiles), dim3(256), MX_SMEM, (hipStream_t)stream, p);
   MDM_LAUNCH_STATUS();
 }

@@ -13,7 +13,8 @@ Layout of the package
   text_encoder.py T5Encoder / LanguageModel: the frozen flan-T5 text encoder on packed tokens (mirror of
                   ml_mdm.language_models.factory)
   lora.py         LoRA adapters on the attention projections: attach / merge / unmerge / detach
-  fp8.py          opt-in MXFP8 (weights and activations) sampling path of the attention-layer 1x1 GEMMs: attach / detach
+  fp8.py          opt-in MXFP8 (weights and activations) sampling path of the attention-layer 1x1 GEMMs and, with
+                  conv_targets, of the ResNet convolutions (3x3 implicit GEMM): attach / detach
 """
 import os as _os
 

@@ -184,7 +184,7 @@ class LoraAdapters(nn.Module):
             raise RuntimeError("the adapters are not merged")
         self._attached()
         if any(getattr(layer, "_fp8", None) is not None for _, layer, _, _, _, _ in self._entries):
-            raise RuntimeError("the model's attention layers run in MXFP8 (mdm_hip.fp8): detach() the fp8 handle before unmerge()")
+            raise RuntimeError("the model's adapted layers run in MXFP8 (mdm_hip.fp8): detach() the fp8 handle before unmerge()")
         self._fold(-1.0)
         self.merged = False
 
@@ -248,6 +248,9 @@ def attach(vision_model, rank=16, alpha=None, targets=TARGETS, freeze_base=True,
         raise RuntimeError("the model already has adapters attached: detach() them first")
     if targets and any(m._fp8 is not None for m in layers):
         raise RuntimeError("the model's attention layers run in MXFP8 (mdm_hip.fp8): detach() the fp8 handle first, then attach "
+                           "and merge() the adapters, then attach fp8 again")
+    if any(m._fp8 is not None for m in resnets):
+        raise RuntimeError("the model's ResNet convolutions run in MXFP8 (mdm_hip.fp8): detach() the fp8 handle first, then attach "
                            "and merge() the adapters, then attach fp8 again")
     return LoraAdapters(vision_model, rank, rank if alpha is None else alpha, targets, seed, freeze_base, conv_targets, conv_rank,
                         conv_alpha)

@@ -1372,6 +1372,82 @@ def packed_weight_mx8(weight: torch.Tensor, bias):
     return ent["mx8"][1]
 
 
+def mx8_quant_zrow(x):
+    """the activation of a 3x3 MXFP8 convolution: x [..., K] (bf16, K % 8 == 0) -> Mx8 of M + 1 rows -- ``mx8_quant`` of the
+    rows [M, K] plus the zero row (codes 0, scales 127) that taps outside the image read, written by the same launch"""
+    _require_gpu(x)
+    _mx8_inference_only(x)
+    if x.dtype != torch.bfloat16:
+        raise _lib.MdmHipError("mx8_quant_zrow: the MXFP8 convolutions take bf16 activations (got %s)" % x.dtype)
+    x = _c(x.detach())
+    K = x.shape[-1]
+    M = x.numel() // K
+    if K % 8 or M < 1:
+        raise _lib.MdmHipError("mx8_quant_zrow: %d rows of %d elements; the row length must be a multiple of 8" % (M, K))
+    Kp = _round_up(K, 128)
+    out = Mx8(torch.empty((M + 1, Kp), dtype=torch.uint8, device=x.device),
+              torch.empty((M + 1, Kp // 32), dtype=torch.uint8, device=x.device), K)
+    _lib.check(_lib.lib().mdm_mx8_quant_zrow(_p(x), _dt(x), M, K, Kp, _p(out.q), _p(out.s), _stream()), "mdm_mx8_quant_zrow")
+    return out
+
+
+def mx8_conv3x3(a, w, shape, bias=None, residual=None):
+    """Y [N, H, W, Cout] (bf16) = conv3x3(a, w) (+ bias) (+ residual), stride 1, zero padding 1: ``a`` the Mx8 of
+    ``mx8_quant_zrow`` (N H W + 1 rows of Cin), ``w`` the Mx8 of ``packed_weight_mx8_3x3`` ([Cout 9, Cin]), ``shape`` =
+    (N, H, W); bias fp32 [Cout]; residual bf16 with N H W Cout elements."""
+    _require_gpu(a.q)
+    N, H, W = (int(v) for v in shape)
+    if min(N, H, W) < 1 or a.rows != N * H * W + 1:
+        raise _lib.MdmHipError("mx8_conv3x3: the activation has %d rows, %d x %d x %d pixels need %d (the zero row last: "
+                               "mx8_quant_zrow)" % (a.rows, N, H, W, N * H * W + 1))
+    if w.rows % 9 or a.Kp != w.Kp or a.K != w.K:
+        raise _lib.MdmHipError("mx8_conv3x3: the activation has %d channels, the weight %d rows of %d" % (a.K, w.rows, w.K))
+    cin, cout = a.K, w.rows // 9
+    if cin % 32 or cout % 32:
+        raise _lib.MdmHipError("mx8_conv3x3: %d -> %d channels; the MXFP8 convolution needs multiples of 32" % (cin, cout))
+    _mx8_inference_only(bias, residual)
+    dev = a.q.device
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout or not bias.is_contiguous()):
+        raise _lib.MdmHipError("mx8_conv3x3: the bias must be a contiguous fp32 vector of %d elements" % cout)
+    if residual is not None:
+        _require_gpu(residual)
+        if residual.dtype != torch.bfloat16 or residual.numel() != N * H * W * cout:
+            raise _lib.MdmHipError("mx8_conv3x3: the residual must be a bf16 tensor of %d x %d elements (got %s, %d)"
+                                   % (N * H * W, cout, residual.dtype, residual.numel()))
+        residual = _c(residual.detach())
+    y = torch.empty((N, H, W, cout), dtype=torch.bfloat16, device=dev)
+    _lib.check(_lib.lib().mdm_mx8_conv3x3(_p(a.q), _p(a.s), _p(w.q), _p(w.s), _p(bias), _p(residual), _p(y), N, H, W, cin, cout,
+                                          _stream()), "mdm_mx8_conv3x3")
+    return y
+
+
+def packed_weight_mx8_3x3(weight: torch.Tensor, bias):
+    """(Mx8 of the weight as [Cout 9, Cin], row o 9 + ky 3 + kx, fp32 bias or None) for a reference-layout 3x3 weight
+    ``(Cout, Cin, 3, 3)``: a block is 32 input channels of one (o, tap).  Quantised from the fp32 master and cached per
+    parameter version under a key of its own, exactly like ``packed_weight_mx8``."""
+    ent = _cache_slot(weight)
+    ver = (weight._version, None if bias is None else bias._version, weight.data_ptr(), _pack_epoch)
+    if "mx8_3x3" in ent and ent["mx8_3x3"][0] == ver:
+        return ent["mx8_3x3"][1]
+    _require_gpu(weight)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise _lib.MdmHipError("packed_weight_mx8_3x3: only 3x3 weights (got %s)" % (tuple(weight.shape),))
+    cout, cin = weight.shape[0], weight.shape[1]
+    prev, bp = ent["mx8_3x3"][1] if "mx8_3x3" in ent else (None, None)
+    if prev is not None and (tuple(prev.q.shape) != (cout * 9, _round_up(cin, 128)) or prev.q.device != weight.device):
+        prev = bp = None
+    with torch.no_grad():
+        wq = mx8_quant(weight.detach().float().permute(0, 2, 3, 1).reshape(cout * 9, cin), out=prev)
+        if bias is None:
+            bp = None
+        elif bp is not None and bp.shape == bias.shape and bp.device == bias.device:
+            bp.copy_(bias.detach())
+        else:
+            bp = bias.detach().float().contiguous().clone()
+    ent["mx8_3x3"] = (ver, (wq, bp))
+    return ent["mx8_3x3"][1]
+
+
 # --------------------------------------------------------------------------------------
 # normalisation
 # --------------------------------------------------------------------------------------

@@ -109,6 +109,7 @@ class ResNet(nn.Module):
     """GN+SiLU -> 3x3 -> GN*(1+ta)+tb -> SiLU -> 3x3 (zero-init) + shortcut   (reference unet.py:193-238)."""
 
     _lora = None   # low-rank adapters on conv1 / conv2 / conv3 (mdm_hip/lora.py); not a submodule: the state dict stays the reference's
+    _fp8 = None    # MXFP8 sampling path of conv1 / conv2 / conv3 (mdm_hip.fp8.attach(conv_targets=...)): the same kind of handle
 
     def __init__(self, time_emb_channels, config: ResNetConfig):
         super().__init__()
@@ -134,7 +135,10 @@ class ResNet(nn.Module):
         else:
             h, x = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=True)
         lo = self._lora
-        if lo is None:
+        fp8 = self._fp8    # only beside merged adapters (fp8.attach refuses unmerged ones): lo.apply then adds nothing
+        if fp8 is not None and fp8.on("conv1"):
+            h = fp8.conv3x3(h, self.conv1)
+        elif lo is None:
             h = ops.conv(h, self.conv1.weight, self.conv1.bias)
         else:
             h = lo.apply("conv1", ops.conv(h, self.conv1.weight, self.conv1.bias), h)
@@ -151,9 +155,14 @@ class ResNet(nn.Module):
             h = ops.dropout(h, self.config.dropout, True)
         shortcut = x
         if self.config.output_channels != self.config.num_channels:
-            shortcut = ops.conv(x, self.conv3.weight, self.conv3.bias)
-            if lo is not None:
-                shortcut = lo.apply("conv3", shortcut, x)
+            if fp8 is not None and fp8.on("conv3"):
+                shortcut = fp8.conv(x, self.conv3)
+            else:
+                shortcut = ops.conv(x, self.conv3.weight, self.conv3.bias)
+                if lo is not None:
+                    shortcut = lo.apply("conv3", shortcut, x)
+        if fp8 is not None and fp8.on("conv2"):
+            return fp8.conv3x3(h, self.conv2, residual=shortcut)
         out = ops.conv(h, self.conv2.weight, self.conv2.bias, residual=shortcut)
         # the residual went in with the base convolution's epilogue; the adapter term adds behind it (linear: exact)
         return out if lo is None else lo.apply("conv2", out, h)

@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""What the opt-in MXFP8 path of the attention-layer 1x1 GEMMs (mdm_hip/fp8.py, csrc/fp8.hip) costs and saves, bf16 autocast,
-random weights.  Development / reporting tool in the method of tools/sample_bench.py: the two legs of a comparison are
+"""What the opt-in MXFP8 path of the attention-layer 1x1 GEMMs and (``--conv``) of the ResNet convolutions (mdm_hip/fp8.py,
+csrc/fp8.hip) costs and saves, bf16 autocast, random weights.  Development / reporting tool in the method of tools/sample_bench.py: the two legs of a comparison are
 alternated call by call in ONE process, ``--warmup`` calls first, ``--calls`` timed, device events around every call,
 median [p10-p90].
    python tools/fp8_bench.py [--models unet64:64,unet64:4,nested1024:4] [--steps 8] [--calls 10] [--warmup 2]
-                             [--legs sampling,kernels,error] [--out profiles/fp8_sampling.jsonl]
+                             [--legs sampling,kernels,error] [--conv] [--out profiles/fp8_sampling.jsonl]
 
   sampling  graphed DDIM (eta = 0) ms per iteration: the plain bf16 model against a second copy of it with the fp8 handle
             attached (two GraphedSamplers, the same start noise and conditioning)
@@ -13,6 +13,10 @@ median [p10-p90].
             over the bytes it must move; the whole FFN (quantise + two GEMMs against ops.ffn).  8 launches on rotating
             operands replayed as one hipGraph
   error     rel-L2 between the bf16 and the fp8 model's outputs on the same inputs at a few timesteps
+  --conv    adds to ``sampling`` and ``error`` a third copy of the model with the attention layers AND conv1 / conv2 / conv3
+            of every ResNet in fp8 ("fp8+conv"; on a nested model a fourth, "fp8+conv>=128": the same with min_channels=128,
+            the width study), and to ``kernels`` mx8_conv3x3 (+ its mx8_quant_zrow) against the bf16 3x3 convolution
+            (conv_gemm_bl_kernel) at the shipped ResNet shapes, TFLOP/s over 2 M 9 Cin Cout
 With random weights image quality is not judged."""
 import argparse
 import json
@@ -90,6 +94,13 @@ def model_legs(which, batch, a, base, legs):
     pipe_b, side = _pipe(which)
     pipe_f, _ = _pipe(which)
     handle = fp8.attach(pipe_f.model.vision_model)
+    extra = {}   # --conv: leg name -> (pipe, handle)
+    if a.conv:
+        widths = (0, 128) if which != "unet64" else (0,)
+        for mc in widths:
+            p, _ = _pipe(which)
+            extra["fp8+conv" if mc == 0 else "fp8+conv>=%d" % mc] = (
+                p, fp8.attach(p.model.vision_model, conv_targets=fp8.CONV_TARGETS, min_channels=mc))
     g = torch.Generator().manual_seed(1)
     smp = {"lm_outputs": torch.randn(batch, 32, 2048, generator=g).to(DEV), "lm_mask": torch.ones(batch, 32).to(DEV)}
     vm_b, vm_f = pipe_b.model.vision_model, pipe_f.model.vision_model
@@ -98,7 +109,7 @@ def model_legs(which, batch, a, base, legs):
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         if "error" in legs:
             res = dict(base, model=which, batch=batch, leg="rel-L2 between the bf16 and the fp8 model's outputs, same inputs",
-                       fp8_layers=len(handle.layers), rel_l2={})
+                       fp8_layers=len(handle.layers), rel_l2={}, **{"rel_l2 " + k: {} for k in extra})
             for t in (50, 500, 950):
                 xs = [torch.randn(batch, 3, sd, sd, generator=g).to(DEV) for sd in sides]
                 tt = torch.full((batch,), t, dtype=torch.int64, device=DEV)
@@ -106,20 +117,32 @@ def model_legs(which, batch, a, base, legs):
                 ob, of = vm_b(*args), vm_f(*args)
                 ob, of = (list(ob), list(of)) if isinstance(ob, (list, tuple)) else ([ob], [of])
                 res["rel_l2"]["t=%d" % t] = [round(float((f.float() - b.float()).norm() / b.float().norm()), 5) for b, f in zip(ob, of)]
+                for k, (p, _) in extra.items():
+                    oc = p.model.vision_model(*args)
+                    oc = list(oc) if isinstance(oc, (list, tuple)) else [oc]
+                    res["rel_l2 " + k]["t=%d" % t] = [round(float((f.float() - b.float()).norm() / b.float().norm()), 5) for b, f in zip(ob, oc)]
             out.append(res)
         if "sampling" in legs:
             noise = [torch.randn(batch, 3, sd, sd, generator=g).to(DEV) for sd in sides]
             gb, gf = GraphedSampler(pipe_b, seed=7), GraphedSampler(pipe_f, seed=7)
+            gx = {k: GraphedSampler(p, seed=7) for k, (p, _) in extra.items()}
             run = lambda gs: lambda: gs.sample(batch, smp, side, DEV, num_inference_steps=a.steps, start_noise=noise, ddim_eta=0)
             res = dict(base, model=which, batch=batch, steps_per_call=a.steps, leg="graphed DDIM, bf16 against fp8", unit="ms per call",
                        fp8_layers=len(handle.layers))
-            res["ms"] = _alternate({"bf16": run(gb), "fp8": run(gf)}, a)
+            for k, (_, hx) in extra.items():
+                res["fp8_convs " + k] = len(hx.convs)
+            res["ms"] = _alternate(dict({"bf16": run(gb), "fp8": run(gf)}, **{k: run(gs) for k, gs in gx.items()}), a)
             res["sclk_after"] = _sclk()
             res["ms_per_iteration"] = {k: round(v["median"] / a.steps, 4) for k, v in res["ms"].items()}
             res["fp8_over_bf16_median"] = round(res["ms"]["fp8"]["median"] / res["ms"]["bf16"]["median"], 4)
+            for k in gx:
+                res[k + "_over_bf16_median"] = round(res["ms"][k]["median"] / res["ms"]["bf16"]["median"], 4)
             ib, i_f = run(gb)(), run(gf)()
             res["finite"] = bool(torch.isfinite(ib).all() and torch.isfinite(i_f).all())
+            ib = ib.clone()      # a GraphedSampler returns its static output buffer
             res["images_rel_l2_fp8_vs_bf16"] = round(float((i_f.float() - ib.float()).norm() / ib.float().norm()), 5)
+            for k, gs in gx.items():
+                res["images_rel_l2_%s_vs_bf16" % k] = round(float((run(gs)().float() - ib.float()).norm() / ib.float().norm()), 5)
             out.append(res)
     return out
 
@@ -197,6 +220,57 @@ def kernel_legs(a, base):
     return [res]
 
 
+# the shipped ResNet 3x3 shapes (N, H, W, Cin, Cout): UNet-64 B=64 at its three levels and a skip-concat input, then the
+# nets of nested-1024 B=4 from the 1024 x 1024 outer net inwards
+CONV_SHAPES = [(64, 64, 64, 256, 256), (64, 32, 32, 512, 512), (64, 16, 16, 768, 768), (64, 16, 16, 1536, 768),
+               (4, 1024, 1024, 32, 32), (4, 512, 512, 64, 64), (4, 256, 256, 128, 128), (4, 128, 128, 256, 256)]
+
+
+def conv_kernel_legs(a, base):
+    nbuf, bf = 4, torch.bfloat16
+    g = torch.Generator().manual_seed(5)
+    res = dict(base, leg="3x3 kernel rates", rotating_buffers=nbuf, unit="TFLOP/s over 2 M 9 Cin Cout; the quantiser in us", kernels={})
+
+    def rate(launch):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            launch(0)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for k in range(nbuf):
+                launch(k)
+        t = []
+        for it in range(a.warmup + a.calls):
+            ms = _timed(graph.replay) / nbuf
+            if it >= a.warmup:
+                t.append(ms)
+        return _stats(t)
+
+    with torch.no_grad():
+        for N, H, W, cin, cout in CONV_SHAPES:
+            flops = 2.0 * N * H * W * 9 * cin * cout
+            one = torch.randn(N, H, W, cin, generator=g).to(bf).to(DEV)
+            xs = [one] + [one.roll(k, 0).contiguous() for k in range(1, nbuf)]
+            w = torch.nn.Parameter((torch.randn(cout, cin, 3, 3, generator=g) / (9 * cin) ** 0.5).to(DEV))
+            b = torch.nn.Parameter(torch.randn(cout, generator=g).to(DEV) * 0.1)
+            wq, bq = ops.packed_weight_mx8_3x3(w, b)
+            aq = [ops.mx8_quant_zrow(x) for x in xs]
+            entry = {}
+            for name, fn in (("mx8_conv3x3", lambda k: ops.mx8_conv3x3(aq[k], wq, (N, H, W), bq)),
+                             ("mx8_quant_zrow + mx8_conv3x3", lambda k: ops.mx8_conv3x3(ops.mx8_quant_zrow(xs[k]), wq, (N, H, W), bq)),
+                             ("conv_gemm_bl bf16", lambda k: ops.conv(xs[k], w, b))):
+                st = rate(fn)
+                entry[name] = {"us": round(st["median"] * 1e3, 2), "us_p10_p90": [round(v * 1e3, 2) for v in st["p10_p90"]],
+                               "TFLOPs": round(flops / (st["median"] * 1e-3) / 1e12, 1)}
+            res["kernels"]["%d x %d x %d, %d -> %d" % (N, H, W, cin, cout)] = entry
+            del xs, aq, one
+            torch.cuda.empty_cache()
+    res["sclk_after"] = _sclk()
+    return [res]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="unet64:64,unet64:4,nested1024:4")
@@ -204,6 +278,7 @@ def main():
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--legs", default="sampling,kernels,error")
+    ap.add_argument("--conv", action="store_true", help="also the ResNet convolutions in fp8 (see above)")
     ap.add_argument("--out", default=None, help="append the result lines to this file")
     a = ap.parse_args()
     legs = a.legs.split(",")
@@ -224,6 +299,8 @@ def main():
 
     if "kernels" in legs:
         emit(kernel_legs(a, base))
+        if a.conv:
+            emit(conv_kernel_legs(a, base))
     if "sampling" in legs or "error" in legs:
         for spec in a.models.split(","):
             which, batch = spec.split(":")
