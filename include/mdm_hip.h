@@ -187,6 +187,18 @@ int mdm_gn_bwd(const void* dy, const void* x, const float* gamma, const float* b
                float* dbeta, void* dfilm, float* ws, int N, int HW, int C, int G, int act, int accumulate, int dtype,
                void* stream);
 int mdm_gn_param_reduce_multi(const void* table, int n, int total_blocks, void* stream);
+/* mdm_gn_reapply (a pure addition: no exported signature changed): the output of the normalisations that feed the two
+ * 3x3 convolutions of a ResNet block -- silu(norm1(x)), and dropout(silu(norm2(h) * (1 + ta) + tb)) (unet.py:224, 233-234)
+ * -- once more, from x and the coef [N][C][2] that mdm_gn_fwd saved, so that training need not keep it for the
+ * convolution's weight gradient:
+ *   y = dropout(act(coef[n][c][0] * x + coef[n][c][1]))   x, y [N][HW][C] of `dtype` (MDM_F32 | MDM_BF16), act: 0 none, 1 SiLU
+ * Bit-equal to what mdm_gn_fwd wrote for the same x (either of its kernel families, with or without FiLM: FiLM is folded
+ * into coef), and with p > 0 to mdm_dropout of that output under the same (p, seed, offset); p == 0: no dropout (seed and
+ * offset are ignored).  No statistics and no workspace: one read of x, one write of y.  C a multiple of the 16-byte chunk
+ * (4 fp32 / 8 bf16 elements), N <= 65535, 0 <= p < 1, and N HW C % 8 == 0 when p > 0 (mdm_dropout's rule).  Consumes no
+ * counter blocks of its own: the forward's mdm_dropout call did. */
+int mdm_gn_reapply(const void* x, const float* coef, void* y, int N, int HW, int C, int act, float p,
+                   unsigned long long seed, unsigned long long offset, int dtype, void* stream);
 int mdm_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* stats, int R, int D, float eps,
                int dtype, void* stream);
 /* ws: fp32 [ceil(R/64)][D][2] */

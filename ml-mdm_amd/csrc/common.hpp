@@ -372,6 +372,26 @@ template <typename T, int N> __device__ __forceinline__ void mul_dgelu_vec(float
   for (int e = 0; e < N; ++e) v[e] *= dgelu_t<T>(a[e]);
 }
 
+// Philox4x32-10 (Salmon et al., SC'11): the counter-based generator behind the device RNG of diffusion_ops.hip and the
+// dropout mask, which mdm_dropout draws and mdm_gn_reapply (norm.hip) replays.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+
+// the four mask words of the elements 4 * (blk - offset) ... + 3 of a dropout draw: element i is kept when its word
+// (lane i & 3 of counter block offset + i / 4) is >= p * 2^32
+__device__ __forceinline__ void dropout_words(uint32_t (&c)[4], unsigned long long seed, unsigned long long blk) {
+  c[0] = (uint32_t)blk; c[1] = (uint32_t)(blk >> 32); c[2] = 0x44524f50u /* "DROP" */; c[3] = 0u;
+  philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
 // XCD-aware, bijective remap of a 1-D block id: consecutive logical ids land on
 // the same XCD (hardware places block b on XCD b % 8) so neighbouring tiles that
 // share operand panels hit the same L2. Speed only, never correctness.
@@ -402,6 +422,14 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   } while (0)
 
 extern "C" void mdm_set_error(const char* file, int line, const char* what);
+
+// threshold and scale of a dropout draw with probability p in [0, 1): shared by mdm_dropout and mdm_gn_reapply, which must
+// agree in every bit
+inline void dropout_params(float p, unsigned* thresh, float* scale) {
+  const double t = (double)p * 4294967296.0;
+  *thresh = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+  *scale = 1.f / (1.f - p);
+}
 
 // ---- host-side per-device state ----------------------------------------------------------------------------------
 // Kernel attributes (dynamic LDS above 64 KB) and the CU count belong to a DEVICE, and a process may touch several

@@ -23,17 +23,7 @@ namespace mdm {
 // ---------------------------------------------------------------------------------------------------------
 struct RngState { unsigned long long seed, offset; };
 
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-
+// (philox4x32_10 itself: common.hpp -- the GroupNorm re-apply kernel of norm.hip replays the dropout mask with it)
 // four standard normals of block `blk` of stream `stream`
 __device__ __forceinline__ void normal4(const RngState& st, unsigned long long blk, uint32_t stream, float (&out)[4]) {
   const unsigned long long ctr = st.offset + blk;
@@ -682,9 +672,8 @@ __global__ __launch_bounds__(256) void dropout_kernel(const T* __restrict__ x, T
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const unsigned long long ctr = offset + 2 * i + h;
-      uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x44524f50u /* "DROP" */, 0u};
-      philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+      uint32_t c[4];
+      dropout_words(c, seed, offset + 2 * i + h);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[4 * h + e] = c[e] >= thresh ? v[4 * h + e] * scale : 0.f;
     }
@@ -708,9 +697,9 @@ extern "C" int mdm_dropout(const void* x, void* y, size_t n, float p, unsigned l
   MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
   if (n == 0) return 0;
   const size_t n8 = n / 8;
-  const double t = (double)p * 4294967296.0;
-  const unsigned thresh = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-  const float scale = 1.f / (1.f - p);
+  unsigned thresh;
+  float scale;
+  dropout_params(p, &thresh, &scale);
   const unsigned blocks = (unsigned)((n8 + 255) / 256 > 8192 ? 8192 : (n8 + 255) / 256);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == DT_F32) hipLaunchKernelGGL(dropout_kernel<float>, dim3(blocks), dim3(256), 0, st, (const float*)x, (float*)y, n8, thresh, scale, seed, offset);

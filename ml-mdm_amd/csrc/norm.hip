@@ -29,6 +29,15 @@ namespace mdm {
 
 template <int N> struct GnInt { static constexpr int value = N; };   // compile-time operand counts / flags of the store loops
 
+// y = act(a * x + b): the ONE expression every kernel that produces a GroupNorm output ends in -- gn_apply_kernel,
+// gn_fused_fwd_kernel and gn_reapply_kernel, which must reproduce the other two bit for bit from the a, b they stored.
+// (a * x + b is contracted into one FMA; through this helper all three get the same contraction and the same silu_f.)
+template <int ACT>
+__device__ __forceinline__ float gn_affine_act(float a, float x, float b) {
+  const float z = a * x + b;
+  return ACT ? silu_f(z) : z;
+}
+
 
 // ---- stage 1: per (n, slab) per-channel shifted sums -------------------------
 // part[n][slab][c] = (s1, s2) with s1 = sum(x - K_c), s2 = sum((x - K_c)^2), K_c = x[n, 0, c]
@@ -208,11 +217,66 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
         Chunk<T> ch;
         ch.load(reinterpret_cast<const T*>(&raw[u]));
 #pragma unroll
-        for (int e = 0; e < EPV; ++e) {
-          const float z = a[e] * ch.v[e] + b[e];
-          ch.v[e] = ACT ? silu_f(z) : z;
-        }
+        for (int e = 0; e < EPV; ++e) ch.v[e] = gn_affine_act<ACT>(a[e], ch.v[e], b[e]);
         ch.store(y + base + (size_t)pu * C);
+      }
+    }
+  }
+}
+
+// ---- re-apply: y = dropout?(act(a * x + b)) from the coefficients a forward pass saved ---------------------------------
+// What activation recomputation runs in backward instead of keeping y (ops.py: GnConvFn).  grid (pixel splits, channel
+// slices, N); a block owns `lanes` 16-byte chunk columns (<= 32: row pieces of up to 512 bytes) of sample n and the pixels
+// [px0, px1); the store loop is gn_apply_kernel's -- four rows requested before the first dependent store -- and the
+// arithmetic is gn_affine_act, which both forward kernels end in, on the very a, b they stored: the result is theirs bit for bit.
+// DROP: the mask of mdm_dropout under the same (seed, offset), applied to the value ROUNDED to T (mdm_dropout read the
+// stored y), then rounded again -- bit-equal to mdm_dropout(mdm_gn_fwd(x)).
+template <typename T, int ACT, bool DROP>
+__global__ __launch_bounds__(256) void gn_reapply_kernel(const T* __restrict__ x, const float* __restrict__ coef,
+                                                         T* __restrict__ y, int HW, int C, int lanes, int pix_per_block,
+                                                         unsigned thresh, float scale, unsigned long long seed,
+                                                         unsigned long long offset) {
+  constexpr int EPV = Tr<T>::EPV;
+  const int n = blockIdx.z, tid = threadIdx.x;
+  const int rows_par = 256 / lanes;
+  const int cl = tid % lanes, rl = tid / lanes;
+  if (rl >= rows_par) return;
+  const int c0 = ((int)blockIdx.y * lanes + cl) * EPV;
+  const float* cf = coef + ((size_t)n * C + c0) * 2;
+  float a[EPV], b[EPV];
+#pragma unroll
+  for (int e = 0; e < EPV; ++e) { a[e] = cf[2 * e]; b[e] = cf[2 * e + 1]; }
+  const int px0 = blockIdx.x * pix_per_block, px1 = min(HW, px0 + pix_per_block);
+  const size_t base = (size_t)n * HW * C + c0;
+  for (int p = px0 + rl; p < px1; p += 4 * rows_par) {
+    uint4 raw[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int pu = p + u * rows_par;
+      if (pu < px1) raw[u] = *reinterpret_cast<const uint4*>(x + base + (size_t)pu * C);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int pu = p + u * rows_par;
+      if (pu < px1) {
+        const size_t off = base + (size_t)pu * C;   // flat element index of the chunk: a multiple of EPV
+        Chunk<T> ch;
+        ch.load(reinterpret_cast<const T*>(&raw[u]));
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) ch.v[e] = gn_affine_act<ACT>(a[e], ch.v[e], b[e]);
+        if constexpr (DROP) {
+#pragma unroll
+          for (int h = 0; h < EPV / 4; ++h) {
+            uint32_t w[4];
+            dropout_words(w, seed, offset + off / 4 + h);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float v = to_f32(from_f32<T>(ch.v[4 * h + e]));
+              ch.v[4 * h + e] = w[e] >= thresh ? v * scale : 0.f;
+            }
+          }
+        }
+        ch.store(y + off);
       }
     }
   }
@@ -525,10 +589,7 @@ __global__ __launch_bounds__(NTHR) void gn_fused_fwd_kernel(const T* __restrict_
       Chunk<T> v;
       v.load(reinterpret_cast<const T*>(&raw[it]));
 #pragma unroll
-      for (int e = 0; e < EPV; ++e) {
-        const float z = a[e] * v.v[e] + b[e];
-        v.v[e] = ACT ? silu_f(z) : z;
-      }
+      for (int e = 0; e < EPV; ++e) v.v[e] = gn_affine_act<ACT>(a[e], v.v[e], b[e]);
       v.store(yn + (size_t)p * C);
     }
   }
@@ -1059,6 +1120,49 @@ extern "C" int mdm_gn_fwd(const void* x, const float* gamma, const float* beta, 
   if (dtype == DT_F32) { if (act) { MDM_GN_FWD(float, 1) } else { MDM_GN_FWD(float, 0) } }
   else { if (act) { MDM_GN_FWD(bf16, 1) } else { MDM_GN_FWD(bf16, 0) } }
 #undef MDM_GN_FWD
+  MDM_LAUNCH_STATUS();
+}
+
+// y = dropout?(act(coef[n][c][0] * x + coef[n][c][1])): the output of mdm_gn_fwd (and of mdm_dropout behind it, p > 0, same
+// seed / offset) once more, from x and the coefficients mdm_gn_fwd saved -- one read of x, one write of y, no statistics.
+extern "C" int mdm_gn_reapply(const void* x, const float* coef, void* y, int N, int HW, int C, int act, float p,
+                              unsigned long long seed, unsigned long long offset, int dtype, void* stream) {
+  MDM_CHECK_ARG(x && coef && y);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16);
+  const int epv = dtype == DT_F32 ? 4 : 8;
+  MDM_CHECK_ARG(N > 0 && N <= 65535 && HW > 0 && C > 0 && C % epv == 0);
+  MDM_CHECK_ARG(act == 0 || act == 1);
+  MDM_CHECK_ARG(p >= 0.f && p < 1.f);
+  MDM_CHECK_ARG(p == 0.f || ((size_t)N * HW * C) % 8 == 0);   // mdm_dropout's rule: whole pairs of counter blocks
+  unsigned thresh = 0;
+  float scale = 1.f;
+  if (p > 0.f) dropout_params(p, &thresh, &scale);
+  // chunk columns per block: the largest divisor of C / epv up to 32; pixel splits: about 2048 blocks, every block at
+  // least one full trip of the store loop (4 x 256 / lanes rows).  Every shipped width gives 4 ... 32 columns (64 ... 512
+  // byte row pieces).  A chunk count without a small divisor is correct but slow -- C = 8 x 37 in bf16: one column, a
+  // 16-byte piece per thread at stride C -- there is no ragged last slice here.
+  const int nchunks = C / epv;
+  int lanes = nchunks < 32 ? nchunks : 32;
+  while (nchunks % lanes != 0) --lanes;
+  const int cslices = nchunks / lanes;
+  MDM_CHECK_ARG(cslices <= 65535);   // gridDim.y
+  const int trip = 4 * (256 / lanes);
+  int sp = (int)((2048 + (size_t)N * cslices - 1) / ((size_t)N * cslices));
+  const int max_sp = (HW + trip - 1) / trip;
+  if (sp > max_sp) sp = max_sp;
+  if (sp < 1) sp = 1;
+  const int ppb = (HW + sp - 1) / sp;
+  const dim3 grid(sp, cslices, N);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define MDM_GN_REAPPLY(TT, ACT, DROP)                                                                                \
+  hipLaunchKernelGGL((gn_reapply_kernel<TT, ACT, DROP>), grid, dim3(256), 0, st, (const TT*)x, coef, (TT*)y, HW, C, lanes, \
+                     ppb, thresh, scale, seed, offset)
+#define MDM_GN_REAPPLY_T(TT)                                                                                         \
+  if (p > 0.f) { if (act) MDM_GN_REAPPLY(TT, 1, true); else MDM_GN_REAPPLY(TT, 0, true); }                           \
+  else { if (act) MDM_GN_REAPPLY(TT, 1, false); else MDM_GN_REAPPLY(TT, 0, false); }
+  if (dtype == DT_F32) { MDM_GN_REAPPLY_T(float) } else { MDM_GN_REAPPLY_T(bf16) }
+#undef MDM_GN_REAPPLY_T
+#undef MDM_GN_REAPPLY
   MDM_LAUNCH_STATUS();
 }
 

@@ -38,6 +38,7 @@ from .text_encoder import LanguageModel, T5Encoder, T5EncoderConfig  # noqa: F40
 from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
 from . import lora  # noqa: F401,E402
 from . import fp8  # noqa: F401,E402
+from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
 
 __all__ = [
     "UNet",
@@ -53,4 +54,6 @@ __all__ = [
     "LanguageModel",
     "lora",
     "fp8",
+    "enable_activation_recompute",
+    "activation_recompute_enabled",
 ]

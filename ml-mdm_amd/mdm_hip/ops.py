@@ -724,6 +724,18 @@ def _out_shape(x, Ho, Wo, C):
     return (x.shape[0], C) if x.dim() == 2 else (x.shape[0], Ho, Wo, C)
 
 
+def _conv_forward(x, weight, bias, residual, stride):
+    """the forward launch of y = conv(x, weight) + bias (+ residual) on contiguous operands -> (y, kernel size)"""
+    ks = weight.shape[2] if weight.dim() == 4 else 1
+    wf, wd, bp, cin_pad, cout_pad, kbf, kbd = packed_weight(weight, bias, x.dtype)
+    if x.shape[-1] != cin_pad:
+        raise _lib.MdmHipError("conv input has %d channels, packed weight expects %d" % (x.shape[-1], cin_pad))
+    N, H, W, Ho, Wo = _geom(x, ks, stride)
+    y = torch.empty(_out_shape(x, Ho, Wo, cout_pad), dtype=x.dtype, device=x.device)
+    _conv_launch(x, wf, bp, residual, None, y, None, N, H, W, cin_pad, Ho, Wo, cout_pad, ks, stride, 0, 0, kbf)
+    return y, ks
+
+
 class ConvFn(torch.autograd.Function):
     """y = conv(x, weight) + bias (+ residual).  3x3 (stride 1/2, pad 1), 1x1, or linear ([R, Cin])."""
 
@@ -735,13 +747,7 @@ class ConvFn(torch.autograd.Function):
         _require_gpu(x)
         x = _c(x)
         residual = _c(residual)
-        ks = weight.shape[2] if weight.dim() == 4 else 1
-        wf, wd, bp, cin_pad, cout_pad, kbf, kbd = packed_weight(weight, bias, x.dtype)
-        if x.shape[-1] != cin_pad:
-            raise _lib.MdmHipError("conv input has %d channels, packed weight expects %d" % (x.shape[-1], cin_pad))
-        N, H, W, Ho, Wo = _geom(x, ks, stride)
-        y = torch.empty(_out_shape(x, Ho, Wo, cout_pad), dtype=x.dtype, device=x.device)
-        _conv_launch(x, wf, bp, residual, None, y, None, N, H, W, cin_pad, Ho, Wo, cout_pad, ks, stride, 0, 0, kbf)
+        y, ks = _conv_forward(x, weight, bias, residual, stride)
         ctx.save_for_backward(x, weight, bias)
         ctx.stride, ctx.ks = stride, ks
         ctx.has_res = residual is not None
@@ -1457,6 +1463,23 @@ def _gn_ws(N, HW, C, G, device):
     return _f32_ws(wsb.value, device)
 
 
+def _gn_forward(x, gamma, beta, film, groups, eps, act):
+    """the GroupNorm forward launch on contiguous operands -> (y, stats [N, G, 2], coef [N, C, 2])"""
+    N, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (N * C)
+    g32, b32 = _c(gamma.detach().float()), _c(beta.detach().float())
+    y = torch.empty_like(x)
+    stats = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device)
+    coef = torch.empty((N, C, 2), dtype=torch.float32, device=x.device)
+    ws = _gn_ws(N, HW, C, groups, x.device)
+    _prof_wrap("group_norm fwd (HW=%d)" % HW, 2.0 * x.numel() * x.element_size(), lambda: _lib.check(
+        _lib.lib().mdm_gn_fwd(_p(x), _p(g32), _p(b32), _p(film), _p(y), _p(stats), _p(coef), _p(ws), N, HW, C,
+                              groups, float(eps), act, _dt(x), _stream()),
+        "mdm_gn_fwd",
+    ), kind="hbm")
+    return y, stats, coef
+
+
 class GroupNormFn(torch.autograd.Function):
     """y = act(GroupNorm(x) * (1 + film[:, :C]) + film[:, C:]);  act in {0: none, 1: SiLU}."""
 
@@ -1464,18 +1487,7 @@ class GroupNormFn(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, film, groups, eps, act, passthrough):
         _require_gpu(x)
         x, film = _c(x), _c(film)
-        N, C = x.shape[0], x.shape[-1]
-        HW = x.numel() // (N * C)
-        g32, b32 = _c(gamma.detach().float()), _c(beta.detach().float())
-        y = torch.empty_like(x)
-        stats = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device)
-        coef = torch.empty((N, C, 2), dtype=torch.float32, device=x.device)
-        ws = _gn_ws(N, HW, C, groups, x.device)
-        _prof_wrap("group_norm fwd (HW=%d)" % HW, 2.0 * x.numel() * x.element_size(), lambda: _lib.check(
-            _lib.lib().mdm_gn_fwd(_p(x), _p(g32), _p(b32), _p(film), _p(y), _p(stats), _p(coef), _p(ws), N, HW, C,
-                                  groups, float(eps), act, _dt(x), _stream()),
-            "mdm_gn_fwd",
-        ), kind="hbm")
+        y, stats, coef = _gn_forward(x, gamma, beta, film, groups, eps, act)
         ctx.save_for_backward(x, gamma, beta, film, stats, coef)
         ctx.groups, ctx.act = groups, act
         ctx.passthrough = passthrough
@@ -1547,6 +1559,130 @@ def group_norm(x, gamma, beta, groups, eps=1e-5, film=None, silu=False, passthro
     norm opens, and the residual gradient is folded into the norm's backward kernel.  ``passthrough=2`` returns
     ``(y, x_res, x_skip)``: ``x_skip`` (== x again) is for a second consumer outside the block (a skip connection)."""
     return GroupNormFn.apply(x, gamma, beta, film, groups, eps, 1 if silu else 0, int(passthrough))
+
+
+# --------------------------------------------------------------------------------------
+# activation recomputation: GroupNorm(+FiLM)+SiLU -> (dropout) -> 3x3 convolution as ONE autograd node
+# --------------------------------------------------------------------------------------
+# A ResNet block keeps four full-size activations per call: x (for norm1), h1 = silu(norm1(x)) (for conv1's weight
+# gradient), c1 = conv1(h1) (for norm2) and h2 = dropout(silu(norm2(c1) * (1 + ta) + tb)) (for conv2's).  h1 and h2 are
+# act(a * x + b) of a tensor that is kept anyway, with the a, b that GroupNormFn keeps anyway (coef), under a dropout mask
+# that is a pure function of (p, seed, offset): mdm_gn_reapply reproduces them bit for bit in one elementwise pass.  With
+# the switch on, unet.ResNet routes norm -> (dropout) -> conv through GnConvFn, which issues the stored path's forward
+# launches, saves what GroupNormFn and ConvFn save EXCEPT h, and re-applies h at the top of its backward.  Opt-in: one more
+# read and write of h per ResNet convolution in backward against half of the block's activation memory.
+_act_recompute = False
+
+
+def enable_activation_recompute(flag: bool):
+    """Recompute the normalised input of the ResNet 3x3 convolutions in backward instead of keeping it (default off).
+    Read when a forward pass runs: a step's forward and backward may straddle a change.  Results are bit-identical either
+    way.  Blocks with unmerged conv LoRA adapters (the adapter's backward reads h) or an MXFP8 handle keep the stored
+    path for the convolutions concerned; attention layers, FFN hidden activations, conv3, the resampling convolutions and
+    the queued operands of deferred 1x1 weight gradients are not covered."""
+    global _act_recompute
+    _act_recompute = bool(flag)
+
+
+def activation_recompute_enabled() -> bool:
+    return _act_recompute
+
+
+def gn_reapply(x, coef, silu=True, p=0.0, seed=0, offset=0):
+    """act(coef[..., 0] * x + coef[..., 1]) (+ the dropout mask of (p, seed, offset)): the output of the GroupNorm launch
+    that wrote ``coef`` ([N, C, 2] fp32), and of the dropout launch behind it, bit for bit (C ABI mdm_gn_reapply)"""
+    _require_gpu(x)
+    x = _c(x)
+    N, C = x.shape[0], x.shape[-1]
+    if tuple(coef.shape) != (N, C, 2) or coef.dtype != torch.float32 or coef.device != x.device:
+        raise _lib.MdmHipError("gn_reapply: coef must be fp32 [N=%d, C=%d, 2] on %s, got %s %s on %s" % (
+            N, C, x.device, coef.dtype, tuple(coef.shape), coef.device))
+    coef = _c(coef)
+    HW = x.numel() // (N * C)
+    y = torch.empty_like(x)
+    nbytes = 2.0 * x.numel() * x.element_size()
+    _prof_wrap("group_norm reapply (HW=%d)" % HW, nbytes, lambda: _lib.check(
+        _lib.lib().mdm_gn_reapply(_p(x), _p(coef), _p(y), N, HW, C, 1 if silu else 0, float(p), int(seed), int(offset), _dt(x),
+                                  _stream()), "mdm_gn_reapply"), kind="hbm")
+    return y
+
+
+class _ConvNeeds:
+    """what _conv_backward reads of a ConvFn context"""
+
+    __slots__ = ("ks", "stride", "has_res", "needs_input_grad")
+
+    def __init__(self, ks, stride, has_res, needs):
+        self.ks, self.stride, self.has_res, self.needs_input_grad = ks, stride, has_res, needs
+
+
+class GnConvFn(torch.autograd.Function):
+    """y = conv3x3(dropout_p(act(GroupNorm(x) * (1 + film[:, :C]) + film[:, C:])), weight) + bias (+ residual), with the
+    pass-through outputs of GroupNormFn: the launches of GroupNormFn -> DropoutFn -> ConvFn and their gradients, but the
+    convolution's input is re-applied in backward (mdm_gn_reapply) rather than saved."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, film, groups, eps, act, passthrough, p, weight, bias, residual):
+        _require_gpu(x)
+        x, film, residual = _c(x), _c(film), _c(residual)
+        h, stats, coef = _gn_forward(x, gamma, beta, film, groups, eps, act)
+        seed = off = 0
+        if p > 0.0:
+            h, seed, off = _dropout_forward(h, p)   # the counter moves here, once; backward replays (seed, off)
+        y, ks = _conv_forward(h, weight, bias, residual, 1)
+        del h   # nothing holds it past the convolution's launch
+        ctx.save_for_backward(x, gamma, beta, film, stats, coef, weight, bias)
+        ctx.groups, ctx.act, ctx.ks = groups, act, ks
+        ctx.has_res = residual is not None
+        ctx.drop = (float(p), seed, off)
+        ctx.set_materialize_grads(False)   # an unused pass-through output reaches backward as None (see GroupNormFn)
+        if passthrough == 2:
+            return y, x.view_as(x), x.view_as(x)
+        if passthrough:
+            return y, x.view_as(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy, dres=None, dres2=None):
+        x, gamma, beta, film, stats, coef, weight, bias = ctx.saved_tensors
+        if dy is None:
+            raise _lib.MdmHipError("gn_conv: the convolution's output received no gradient")
+        nig = ctx.needs_input_grad
+        need_dh = nig[0] or nig[1] or nig[2] or nig[3]
+        p, seed, off = ctx.drop
+        if nig[9]:
+            h = gn_reapply(x, coef, bool(ctx.act), p, seed, off)
+        else:
+            h = x   # a frozen weight: nothing reads h, _conv_backward takes only shape and dtype from it
+        # the weight gradient may run on the side stream: _off_critical_path keeps h referenced until that launch has
+        # consumed it, as it keeps a stored x
+        dh, dw, db, dres_conv = _conv_backward(_ConvNeeds(ctx.ks, 1, ctx.has_res, (need_dh, nig[9], nig[10], nig[11])),
+                                               h, weight, bias, dy)
+        del h
+        dx = dgamma = dbeta = dfilm = None
+        if need_dh:
+            if p > 0.0:
+                dhd = torch.empty_like(dh)
+                _lib.check(_lib.lib().mdm_dropout(_p(dh), _p(dhd), dh.numel(), p, seed, off, _dt(dh), _stream()), "mdm_dropout")
+                dh = dhd
+            dx, dgamma, dbeta, dfilm = _gn_backward(dh, x, gamma, beta, film, stats, coef, dres, dres2, ctx.groups, ctx.act)
+        return dx, dgamma, dbeta, dfilm, None, None, None, None, None, dw, db, dres_conv
+
+
+def gn_conv(x, gamma, beta, groups, weight, bias=None, eps=1e-5, film=None, silu=True, passthrough=False, p=0.0,
+            residual=None):
+    """``conv(dropout(group_norm(x, ..., film=film, silu=silu), p), weight, bias, residual)`` for a 3x3 stride-1
+    convolution as one autograd node that does not keep the convolution's input (see enable_activation_recompute);
+    ``passthrough`` as in group_norm: the result is ``y``, ``(y, x_res)`` or ``(y, x_res, x_skip)``.  ``p``: the dropout
+    probability in effect (0: none), 0 <= p < 1, and the element count a multiple of 8 when p > 0."""
+    if weight.dim() != 4 or weight.shape[2] != 3:
+        raise _lib.MdmHipError("gn_conv: a 3x3 convolution weight is expected")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise _lib.MdmHipError("gn_conv: dropout probability %r outside [0, 1)" % p)
+    if p > 0.0 and x.numel() % 8 != 0:
+        raise _lib.MdmHipError("dropout: the element count must be a multiple of 8")
+    return GnConvFn.apply(x, gamma, beta, film, groups, eps, 1 if silu else 0, int(passthrough), p, weight, bias, residual)
 
 
 class LayerNormFn(torch.autograd.Function):
@@ -2428,17 +2564,22 @@ def set_dropout_rng_state(state):
     _dropout_rng[0], _dropout_rng[1] = int(state[0]) & 0xFFFFFFFFFFFFFFFF, int(state[1])
 
 
+def _dropout_forward(x, p):
+    """draw the mask of a contiguous x from the dropout stream (which advances by x's counter blocks) -> (y, seed, offset)"""
+    if _dropout_rng[0] is None:
+        seed_dropout(torch.initial_seed())
+    seed, off = _dropout_rng
+    _dropout_rng[1] = off + (x.numel() + 3) // 4
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().mdm_dropout(_p(x), _p(y), x.numel(), float(p), seed, off, _dt(x), _stream()), "mdm_dropout")
+    return y, seed, off
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):
         _require_gpu(x)
-        x = _c(x)
-        if _dropout_rng[0] is None:
-            seed_dropout(torch.initial_seed())
-        seed, off = _dropout_rng
-        _dropout_rng[1] = off + (x.numel() + 3) // 4
-        y = torch.empty_like(x)
-        _lib.check(_lib.lib().mdm_dropout(_p(x), _p(y), x.numel(), float(p), seed, off, _dt(x), _stream()), "mdm_dropout")
+        y, seed, off = _dropout_forward(_c(x), p)
         ctx.p, ctx.seed, ctx.off = float(p), seed, off
         return y
 

@@ -130,18 +130,32 @@ class ResNet(nn.Module):
         pass-through output of norm1, so that in backward the skip connection's gradient reaches x inside the
         GroupNorm kernel instead of through an accumulation kernel of the autograd engine."""
         g = self.config.num_groups_norm
-        if tap is not None and x.requires_grad and tap[0][tap[1]] is x:
-            h, x, tap[0][tap[1]] = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=2)
-        else:
-            h, x = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=True)
         lo = self._lora
         fp8 = self._fp8    # only beside merged adapters (fp8.attach refuses unmerged ones): lo.apply then adds nothing
-        if fp8 is not None and fp8.on("conv1"):
-            h = fp8.conv3x3(h, self.conv1)
-        elif lo is None:
-            h = ops.conv(h, self.conv1.weight, self.conv1.bias)
+        # activation recomputation (ops.enable_activation_recompute): norm -> (dropout) -> 3x3 conv as one autograd node
+        # that re-applies the convolution's input in backward instead of keeping it.  Only on the plain convolution path:
+        # a block with an MXFP8 handle, and a convolution with an unmerged adapter (whose own backward reads that input),
+        # keep the stored path.
+        recompute = ops.activation_recompute_enabled() and torch.is_grad_enabled() and fp8 is None
+        skip_tap = tap is not None and x.requires_grad and tap[0][tap[1]] is x
+        if recompute and not (lo is not None and lo.active("conv1")):
+            if skip_tap:
+                h, x, tap[0][tap[1]] = ops.gn_conv(x, self.norm1.weight, self.norm1.bias, g, self.conv1.weight, self.conv1.bias,
+                                                   eps=self.norm1.eps, passthrough=2)
+            else:
+                h, x = ops.gn_conv(x, self.norm1.weight, self.norm1.bias, g, self.conv1.weight, self.conv1.bias,
+                                   eps=self.norm1.eps, passthrough=True)
         else:
-            h = lo.apply("conv1", ops.conv(h, self.conv1.weight, self.conv1.bias), h)
+            if skip_tap:
+                h, x, tap[0][tap[1]] = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=2)
+            else:
+                h, x = ops.group_norm(x, self.norm1.weight, self.norm1.bias, g, self.norm1.eps, silu=True, passthrough=True)
+            if fp8 is not None and fp8.on("conv1"):
+                h = fp8.conv3x3(h, self.conv1)
+            elif lo is None:
+                h = ops.conv(h, self.conv1.weight, self.conv1.bias)
+            else:
+                h = lo.apply("conv1", ops.conv(h, self.conv1.weight, self.conv1.bias), h)
         if isinstance(temb_act, TimeStates):
             film = temb_act.film.get(id(self))
             if film is None:
@@ -150,9 +164,12 @@ class ResNet(nn.Module):
             film = ops.linear(temb_act, self.time_layer.weight, self.time_layer.bias)
         if film.shape[0] != h.shape[0]:
             raise NotImplementedError("time-embedding batch repeat (temporal mode) is not implemented")
-        h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, g, self.norm2.eps, film=film, silu=True)
-        if self.config.dropout > 0 and self.training:   # reference :234 (nn.Dropout; the shipped configs use 0.0)
-            h = ops.dropout(h, self.config.dropout, True)
+        p_drop = self.config.dropout if (self.config.dropout > 0 and self.training) else 0.0
+        fuse2 = recompute and not (lo is not None and lo.active("conv2")) and p_drop < 1.0 and (p_drop == 0.0 or h.numel() % 8 == 0)
+        if not fuse2:
+            h = ops.group_norm(h, self.norm2.weight, self.norm2.bias, g, self.norm2.eps, film=film, silu=True)
+            if p_drop > 0:   # reference :234 (nn.Dropout; the shipped configs use 0.0)
+                h = ops.dropout(h, self.config.dropout, True)
         shortcut = x
         if self.config.output_channels != self.config.num_channels:
             if fp8 is not None and fp8.on("conv3"):
@@ -161,6 +178,9 @@ class ResNet(nn.Module):
                 shortcut = ops.conv(x, self.conv3.weight, self.conv3.bias)
                 if lo is not None:
                     shortcut = lo.apply("conv3", shortcut, x)
+        if fuse2:   # (h is still conv1's output here: norm2, the dropout and conv2 are the one node)
+            return ops.gn_conv(h, self.norm2.weight, self.norm2.bias, g, self.conv2.weight, self.conv2.bias, eps=self.norm2.eps,
+                               film=film, p=p_drop, residual=shortcut)
         if fp8 is not None and fp8.on("conv2"):
             return fp8.conv3x3(h, self.conv2, residual=shortcut)
         out = ops.conv(h, self.conv2.weight, self.conv2.bias, residual=shortcut)

@@ -22,6 +22,7 @@ def demangle(names):
     res = []
     for n in out:
         n = re.sub(r"^void ", "", n)
+        n = n.replace("(anonymous namespace)::", "")   # (before the parameter list goes: it would take the whole name along)
         n = re.sub(r"\(.*$", "", n)          # drop the parameter list
         n = n.replace("mdm::", "").replace("__hip_bfloat16", "bf16").replace("__bf16", "bf16").replace("<half", "<bf16")
         res.append(n)
