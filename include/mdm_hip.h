@@ -38,7 +38,9 @@
  *   4  MDM_F32_SPLIT dtype code (mdm_conv_fwd*, mdm_attn_fwd), mdm_dropout (round 4)
  *   3  round 3
  *   5  bf16 tensors: y_pre / aux of mdm_conv_fwd* hold one byte per element, the code of gelu'(pre) (round 6)
- *   6  mdm_conv_fwd_gn / mdm_conv_fwd_gn_ok removed (convolution + GroupNorm in one launch: step-neutral, never the default) */
+ *   6  mdm_conv_fwd_gn / mdm_conv_fwd_gn_ok removed (convolution + GroupNorm in one launch: step-neutral, never the default)
+ * Pure additions do not bump it: 83 entry points at present (the last three: mdm_conv3x3_stem_dgrad, mdm_guide_seed,
+ * mdm_guide_apply). */
 #define MDM_HIP_ABI_VERSION 6
 
 #ifdef __cplusplus
@@ -106,6 +108,19 @@ int mdm_conv_fwd_plan(int M, int Cout, int K, int dtype, int* splits, size_t* ws
 int mdm_conv_fwd_ws(const void* x, const void* w_packed, const float* bias, const void* res, const void* aux, void* y,
                     void* y_pre, int N, int H, int W, int Cin, int Ho, int Wo, int Cout, int ksize, int stride,
                     int transposed, int act, int kblock, int dtype, float* ws, size_t ws_bytes, void* stream);
+/* mdm_conv3x3_stem_dgrad (a pure addition: no exported signature changed): the input gradient of the stem convolution
+ * conv_in (models/unet.py:632, called at :871-880) -- 3x3, stride 1, zero padding 1, 1 <= Cin <= 8 real input channels, which
+ * the forward pass pads to a chunk and for which mdm_pack_weight builds no w_dgrad.
+ *   dx[n, ci, y, x] = sum over taps (ky, kx) and co of  dy[n, y + 1 - ky, x + 1 - kx, co] * w[co, ci, ky, kx]
+ * dy [N, H, W, Cout] of `dtype` (MDM_F32 | MDM_BF16), Cout a multiple of the chunk; w_fwd = the FORWARD pack of
+ * mdm_pack_weight (tap-major, kblock_fwd == 0: [Cout][9][Cin_pad], Cin_pad = Cin rounded up to the chunk), so the
+ * weights are rounded exactly as the forward operator rounds them and the kernel is its exact transpose; fp32
+ * accumulation in a fixed order (no atomics: deterministic).  The result is written DIRECTLY as fp32 NCHW
+ * [N, Cin, H, W], the boundary layout: no padded NHWC tensor of the compute dtype exists and the gradient of x_t is
+ * not rounded to bf16 on its last step.  dy is read once (a halo tile per block in LDS), the filter stays in scalar
+ * registers.  Cin > 8 is an invalid argument. */
+int mdm_conv3x3_stem_dgrad(const void* dy, const void* w_fwd, float* dx_nchw, int N, int H, int W, int Cout, int Cin,
+                           int dtype, void* stream);
 /* Sub-pixel forms of the resampling convolutions (ABI 3; bf16).  A stride-2 3x3 convolution (models/unet.py:514-522) and
  * a 3x3 convolution of a nearest-2x-upsampled image (unet.py:567-569) touch, per 2x2 block of the high-resolution side,
  * 2x2 low-resolution pixels per phase: over 2x2-blocked tensors they are 2x2 correlations -- 16 weight blocks instead of
@@ -346,6 +361,22 @@ int mdm_sampler_jump(const float* x_s, const float* gamma_t, const float* gamma_
 int mdm_noise_images(const float* images, const float* eps, const float* gamma, float inv_scale, float* x_t,
                      float* eps_out, const unsigned long long* rng_state, int rng_stream, int B, size_t chw,
                      void* stream);
+/* Loss-guided sampling (pure additions, no reference line: the reference samples unguided by an image-space loss) --
+ * diffusion posterior sampling, Chung, Kim, Mccann, Klasky, Ye 2023, "Diffusion Posterior Sampling for General Noisy Inverse
+ * Problems": the two per-pixel passes around the caller's autograd call through the denoiser, on [B, chw] images.
+ * mdm_guide_seed: from v = d loss / d x0 (x0 in image units) and the x0 that mdm_sampler_step / _2m returned (after the
+ *   threshold, divided by image_scale), the two terms of the chain rule through x0 = a x_t + b pred (per-sample a[b], b[b]:
+ *   the affine map of get_x0_eps_from_pred, samplers.py:347-367), the image scale and the threshold:
+ *     w = v m image_scale / (clip == 2 ? thr[b] : 1),   m = (clip == 0 || |x0 image_scale| < 1 - 2^-21) ? 1 : 0
+ *     direct = a[b] w,   seed = b[b] w
+ *   The threshold is differentiated as a clamp -- gradient 0 where x0 was clipped, 1 / thr for the dynamic thresholds --
+ *   and thr itself (a per-sample quantile) is a constant.  clip 0 / 1 / 2 as in mdm_sampler_step; x0 may be NULL for clip 0.
+ * mdm_guide_apply: x -= zeta[b] (direct + jt), IN PLACE on x; either of direct / jt may be NULL (a lower scale of a nested
+ *   model receives only jt, the gradient that came back through the denoiser).  zeta is a DEVICE vector [B]; a sample with
+ *   zeta[b] == 0 is neither read nor written. */
+int mdm_guide_seed(const float* v, const float* x0, const float* a, const float* b, const float* thr, float image_scale,
+                   int clip, float* direct, float* seed, int B, size_t chw, void* stream);
+int mdm_guide_apply(float* x, const float* direct, const float* jt, const float* zeta, int B, size_t chw, void* stream);
 int mdm_diffusion_loss_plan(int B, size_t chw, size_t* ws_bytes);
 int mdm_diffusion_loss_fwd(const float* x_t, const float* pred, const float* images, const float* eps,
                            const float* gamma, float inv_scale, float* loss, float* ws, int B, size_t chw,

@@ -462,6 +462,60 @@ __global__ __launch_bounds__(256) void input_stage_kernel(const uint8_t* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Loss-guided sampling (diffusion posterior sampling, Chung et al. 2023): the two per-pixel passes around the
+// autograd call through the denoiser, on [B, chw] fp32 images.
+//   seed:   w = k v m,  k = scale / (clip == 2 ? thr[b] : 1),  m = (clip == 0 || |x0 scale| < 1 - 2^-21) ? 1 : 0
+//           direct = a[b] w (the x_t term of the affine x0),  seed = bcoef[b] w (what goes back through the denoiser)
+//   apply:  x -= zeta[b] (direct + jt); a sample with zeta[b] == 0 keeps its bits (neither read nor written)
+// v is the gradient of the loss in image units; x0 is what the step kernel returned (after its threshold and division by
+// scale): where the clamp acted x0 = +-fl(1 / scale), and fl(fl(1 / scale) scale) is 1 or one ulp below it when scale
+// is no power of two (0.99999994), so "clipped" is |x0 scale| >= 1 - 2^-21 (four ulps): the threshold is differentiated
+// as a clamp.
+// ---------------------------------------------------------------------------------------------------------
+constexpr float kGuideUnclipped = 1.f - 4.76837158203125e-7f;   // 1 - 2^-21
+__global__ __launch_bounds__(256) void guide_seed_kernel(const float* __restrict__ v, const float* __restrict__ x0,
+                                                         const float* __restrict__ a, const float* __restrict__ bcoef,
+                                                         const float* __restrict__ thr, float scale, int clip,
+                                                         float* __restrict__ direct, float* __restrict__ seed, int B,
+                                                         size_t chw4) {
+  for_each_vec4((size_t)B * chw4, [&](size_t i) {
+    const int b = (int)(i / chw4);
+    const float k = clip == 2 ? scale / thr[b] : scale;
+    const float ka = a[b] * k, kb = bcoef[b] * k;
+    const f32x4 g = reinterpret_cast<const f32x4*>(v)[i];
+    f32x4 d, s;
+    if (clip) {
+      const f32x4 x = reinterpret_cast<const f32x4*>(x0)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float w = fabsf(x[e] * scale) < kGuideUnclipped ? g[e] : 0.f;
+        d[e] = ka * w; s[e] = kb * w;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { d[e] = ka * g[e]; s[e] = kb * g[e]; }
+    }
+    reinterpret_cast<f32x4*>(direct)[i] = d;
+    reinterpret_cast<f32x4*>(seed)[i] = s;
+  });
+}
+
+__global__ __launch_bounds__(256) void guide_apply_kernel(float* __restrict__ x, const float* __restrict__ direct,
+                                                          const float* __restrict__ jt, const float* __restrict__ zeta,
+                                                          int B, size_t chw4) {
+  for_each_vec4((size_t)B * chw4, [&](size_t i) {
+    const float z = zeta[i / chw4];
+    if (z == 0.f) return;
+    f32x4 g = direct ? reinterpret_cast<const f32x4*>(direct)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    if (jt) g += reinterpret_cast<const f32x4*>(jt)[i];
+    f32x4 o = reinterpret_cast<const f32x4*>(x)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] -= z * g[e];
+    reinterpret_cast<f32x4*>(x)[i] = o;
+  });
+}
+
 }  // namespace mdm
 
 using namespace mdm;
@@ -553,6 +607,28 @@ extern "C" int mdm_sampler_jump(const float* x_s, const float* gamma_t, const fl
   hipLaunchKernelGGL(jump_kernel, dim3(stream_blocks((size_t)B * (chw / 4))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), x_s, gamma_t, gamma_s, noise, jump_gate,
                      reinterpret_cast<const RngState*>(rng_state), (uint32_t)rng_stream, x_t_out, B, chw / 4);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_guide_seed(const float* v, const float* x0, const float* a, const float* b, const float* thr,
+                              float image_scale, int clip, float* direct, float* seed, int B, size_t chw, void* stream) {
+  MDM_CHECK_ARG(v && a && b && direct && seed && B > 0 && chw > 0 && chw % 4 == 0);
+  MDM_CHECK_ARG(clip >= 0 && clip <= 2);
+  MDM_CHECK_ARG(clip == 0 || x0);
+  MDM_CHECK_ARG(clip != 2 || thr);
+  MDM_CHECK_ARG(image_scale > 0.f);
+  MDM_CHECK_ARG(direct != seed && direct != v && seed != v && direct != x0 && seed != x0);
+  hipLaunchKernelGGL(guide_seed_kernel, dim3(stream_blocks((size_t)B * (chw / 4))), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), v, x0, a, b, thr, image_scale, clip, direct, seed, B, chw / 4);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_guide_apply(float* x, const float* direct, const float* jt, const float* zeta, int B, size_t chw,
+                               void* stream) {
+  MDM_CHECK_ARG(x && zeta && (direct || jt) && B > 0 && chw > 0 && chw % 4 == 0);
+  MDM_CHECK_ARG(x != direct && x != jt);
+  hipLaunchKernelGGL(guide_apply_kernel, dim3(stream_blocks((size_t)B * (chw / 4))), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, direct, jt, zeta, B, chw / 4);
   MDM_LAUNCH_STATUS();
 }
 

@@ -6,7 +6,7 @@ Layout of the package
   unet.py         UNet, config dataclasses (mirror of ml_mdm.models.unet)
   nested_unet.py  NestedUNet (mirror of ml_mdm.models.nested_unet)
   diffusion.py    Diffusion / NestedDiffusion train-step + sampling call surface
-  samplers.py     noise schedules + DDPM/DDIM updates
+  samplers.py     noise schedules + DDPM/DDIM updates; LossGuide: loss-guided (DPS) sampling through the model's input gradient
   configs.py      the three shipped architectures (cc12m 64 / 256 / 1024)
   distributed.py  one-process-per-GPU data parallel gradient reducer over RCCL
   registry.py     plug into the reference's ml_mdm.config registries when present
@@ -39,6 +39,7 @@ from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
 from . import lora  # noqa: F401,E402
 from . import fp8  # noqa: F401,E402
 from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
+from .samplers import LossGuide  # noqa: F401,E402
 
 __all__ = [
     "UNet",
@@ -56,4 +57,5 @@ __all__ = [
     "fp8",
     "enable_activation_recompute",
     "activation_recompute_enabled",
+    "LossGuide",
 ]

@@ -267,7 +267,7 @@ class GraphedSampler:
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None):
+               start_step=None, guide=None):
         """-> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
         guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
         drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on).
@@ -275,6 +275,10 @@ class GraphedSampler:
         known image, and ``resample``, are part of the graph key.  ``start_step=t``: replay only the rows whose time is
         <= t, from ``start_noise`` = the image noised to the first of them (``Diffusion.partial_diffusion(...,
         graphed=self)`` does the noising); the first replayed row of ``dpmpp_2m`` is first order, as in the eager sampler."""
+        if guide is not None:
+            raise NotImplementedError("GraphedSampler does not take guide=: loss-guided sampling calls an arbitrary user "
+                                      "function and an autograd pass through the denoiser every step, and neither can be "
+                                      "captured in a hipGraph; use the eager Sampler.sample(..., guide=...)")
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
         if known_mask is not None and known_images is None:

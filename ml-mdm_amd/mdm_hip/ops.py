@@ -839,6 +839,88 @@ def conv_tap(x, weight, bias=None, stride=1):
 
 
 # --------------------------------------------------------------------------------------
+# the stem (conv_in) as one node whose backward reaches the model's input
+# --------------------------------------------------------------------------------------
+STEM_DGRAD_MAX_CIN = 8
+
+
+def conv3x3_stem_dgrad(dy, weight, bias=None):
+    """dx [N, Cin, H, W] fp32 NCHW of y = conv3x3(pad(x), weight), stride 1, from dy [N, H, W, Cout_pad] of the compute
+    dtype (C ABI mdm_conv3x3_stem_dgrad): reads the FORWARD pack of ``weight``, 1 <= Cin <= 8."""
+    _require_gpu(dy)
+    dy = _c(dy)
+    if weight.dim() != 4 or weight.shape[2] != 3 or weight.shape[3] != 3:
+        raise _lib.MdmHipError("conv3x3_stem_dgrad: a 3x3 convolution weight is expected")
+    cin = weight.shape[1]
+    if not 1 <= cin <= STEM_DGRAD_MAX_CIN:
+        raise _lib.MdmHipError("input gradient of a channel-padded stem convolution is implemented for at most %d input "
+                               "channels (got %d)" % (STEM_DGRAD_MAX_CIN, cin))
+    wf, _, _, cin_pad, cout_pad, kbf, _ = packed_weight(weight, bias, dy.dtype)
+    if dy.dim() != 4 or dy.shape[-1] != cout_pad or kbf:
+        raise _lib.MdmHipError("conv3x3_stem_dgrad: dy %s does not match the packed weight (%d channels)"
+                               % (tuple(dy.shape), cout_pad))
+    N, H, W = dy.shape[0], dy.shape[1], dy.shape[2]
+    dx = torch.empty((N, cin, H, W), dtype=torch.float32, device=dy.device)
+
+    def go():
+        _lib.check(_lib.lib().mdm_conv3x3_stem_dgrad(_p(dy), _p(wf), _p(dx), N, H, W, cout_pad, cin, _dt(dy), _stream()),
+                   "mdm_conv3x3_stem_dgrad")
+
+    if _prof is None:
+        go()
+    else:
+        name = "stem_dgrad_kernel<%s,%d>" % ("f32" if dy.dtype == torch.float32 else "bf16", cin)
+        if _prof_shapes:
+            name += " M=%d N=%d K=%d" % (N * H * W, cin, 9 * cout_pad)
+        _prof_wrap(name, float(dy.numel() * dy.element_size() + dx.numel() * 4), go, kind="hbm")
+    return dx
+
+
+class StemConvFn(torch.autograd.Function):
+    """y = conv3x3(to_nhwc(x), weight) + bias from fp32 NCHW x: the launches of ToNHWCFn -> ConvFn forward (bit-identical
+    output), their weight / bias gradients backward (_conv_backward: gradient sink and side stream included), and the
+    input gradient from mdm_conv3x3_stem_dgrad, straight into fp32 NCHW."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, dtype):
+        _require_gpu(x)
+        x = _c(x.float())
+        N, C, H, W = x.shape
+        epv = 4 if dtype == torch.float32 else 8
+        xh = torch.empty((N, H, W, _round_up(C, epv)), dtype=dtype, device=x.device)
+        _lib.check(_lib.lib().mdm_nchw_to_nhwc(_p(x), _p(xh), N, C, H, W, xh.shape[-1], _dt(xh), _stream()), "mdm_nchw_to_nhwc")
+        y, _ = _conv_forward(xh, weight, bias, None, 1)
+        ctx.save_for_backward(xh, weight, bias)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xh, weight, bias = ctx.saved_tensors
+        nig = ctx.needs_input_grad
+        dy = _c(dy)
+        dx = conv3x3_stem_dgrad(dy, weight, bias) if nig[0] else None
+        _, dw, db, _ = _conv_backward(_ConvNeeds(3, 1, False, (False, nig[1], nig[2], False)), xh, weight, bias, dy)
+        return dx, dw, db, None
+
+
+def stem_conv(x_nchw, weight, bias=None, dtype=torch.float32):
+    """``conv(to_nhwc(x_nchw, dtype), weight, bias)`` for the 3x3 stride-1 stem, differentiable in ``x_nchw``.  A stem whose
+    input channels are NOT padded in ``dtype`` and exceed the kernel's limit takes the generic nodes (they have a dgrad
+    pack); a padded one beyond 8 channels raises."""
+    if weight.dim() != 4 or weight.shape[2] != 3:
+        raise _lib.MdmHipError("stem_conv: a 3x3 convolution weight is expected")
+    cin = weight.shape[1]
+    if x_nchw.dim() != 4 or x_nchw.shape[1] != cin:
+        raise _lib.MdmHipError("stem_conv: input %s vs weight %s" % (tuple(x_nchw.shape), tuple(weight.shape)))
+    if cin > STEM_DGRAD_MAX_CIN:
+        if cin % (4 if dtype == torch.float32 else 8) == 0:
+            return conv(to_nhwc(x_nchw, dtype), weight, bias)
+        raise _lib.MdmHipError("input gradient of a channel-padded stem convolution is implemented for at most %d input "
+                               "channels (got %d)" % (STEM_DGRAD_MAX_CIN, cin))
+    return StemConvFn.apply(x_nchw, weight, bias, dtype)
+
+
+# --------------------------------------------------------------------------------------
 # upsample2x (nearest) -> conv3x3 in its sub-pixel form
 # --------------------------------------------------------------------------------------
 def packed_upconv_weights(weight: torch.Tensor, bias):
@@ -1509,13 +1591,15 @@ class GroupNormFn(torch.autograd.Function):
         x, gamma, beta, film, stats, coef = ctx.saved_tensors
         if dy is None:                       # only the pass-through outputs were used
             dy = torch.zeros_like(x)
-        dx, dgamma, dbeta, dfilm = _gn_backward(dy, x, gamma, beta, film, stats, coef, dres, dres2, ctx.groups, ctx.act)
+        dx, dgamma, dbeta, dfilm = _gn_backward(dy, x, gamma, beta, film, stats, coef, dres, dres2, ctx.groups, ctx.act,
+                                                ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         return dx, dgamma, dbeta, dfilm, None, None, None, None
 
 
-def _gn_backward(dy, x, gamma, beta, film, stats, coef, dres, dres2, groups, act):
+def _gn_backward(dy, x, gamma, beta, film, stats, coef, dres, dres2, groups, act, need_params=True):
     """the GroupNorm backward launch (+ where its parameter gradients go): -> (dx, dgamma, dbeta, dfilm); dgamma / dbeta
-    are None when they went into the gradient sink (now, or as per-sample rows reduced at the next flush point)"""
+    are None when they went into the gradient sink (now, or as per-sample rows reduced at the next flush point), and
+    when neither gamma nor beta wants one (``need_params`` off: the single launch of before, its sums thrown away)"""
     dy = _c(dy)
     dres = _c(dres) if dres is not None else None
     dres2 = _c(dres2) if dres2 is not None else None
@@ -1528,14 +1612,22 @@ def _gn_backward(dy, x, gamma, beta, film, stats, coef, dres, dres2, groups, act
     sg, sb = _slot(gamma), _slot(beta)
     sunk = sg is not None and sb is not None
     deferred = sunk and _defer_wgrad   # per-sample rows now, one multi-layer reduce at the next flush point
+    # trainable gamma / beta without a sink and with three or more samples: the per-sample terms go to rows (plain stores)
+    # and are summed in a fixed order below -- the kernel's fp32 atomics add them in whatever order the blocks finish, and
+    # (a + b) + c != (a + c) + b: two runs of the same step differed in these gradients.  One or two samples: the atomic
+    # sum is exact either way.  Frozen gamma and beta: nobody reads the sums, the one launch stays as it was.
+    rows = need_params and not sunk and N >= 3
     if deferred:
         dgamma, dbeta = _gn_rows(N, C, x.device)
+    elif rows:
+        dgamma = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        dbeta = torch.empty((N, C), dtype=torch.float32, device=x.device)
     else:
         dgamma = sg if sunk else torch.empty(C, dtype=torch.float32, device=x.device)
         dbeta = sb if sunk else torch.empty(C, dtype=torch.float32, device=x.device)
     dfilm = torch.empty_like(film) if film is not None else None
     ws = _gn_ws(N, HW, C, groups, x.device)
-    mode = 2 if deferred else (1 if sunk else 0)
+    mode = 2 if (deferred or rows) else (1 if sunk else 0)
     npass = 3.0 + (dres is not None) + (dres2 is not None)
     _prof_wrap("group_norm bwd (HW=%d)" % HW, npass * x.numel() * x.element_size(), lambda: _lib.check(
         _lib.lib().mdm_gn_bwd(_p(dy), _p(x), _p(g32), _p(b32), _p(film), _p(stats), _p(coef), _p(dres), _p(dres2), _p(dx), _p(dgamma),
@@ -1551,6 +1643,12 @@ def _gn_backward(dy, x, gamma, beta, film, stats, coef, dres, dres2, groups, act
         _grad_sink.ready(gamma)
         _grad_sink.ready(beta)
         return dx, None, None, dfilm
+    if not need_params:
+        return dx, None, None, dfilm
+    if rows:
+        pg, pb = dgamma, dbeta
+        dgamma, dbeta = _prof_wrap("group_norm param rows sum (wgrad of gamma / beta, N=%d)" % N, 2.0 * 4 * (N + 1) * C,
+                                   lambda: (pg.sum(0), pb.sum(0)), kind="hbm")
     return dx, dgamma, dbeta, dfilm
 
 
@@ -1665,7 +1763,8 @@ class GnConvFn(torch.autograd.Function):
                 dhd = torch.empty_like(dh)
                 _lib.check(_lib.lib().mdm_dropout(_p(dh), _p(dhd), dh.numel(), p, seed, off, _dt(dh), _stream()), "mdm_dropout")
                 dh = dhd
-            dx, dgamma, dbeta, dfilm = _gn_backward(dh, x, gamma, beta, film, stats, coef, dres, dres2, ctx.groups, ctx.act)
+            dx, dgamma, dbeta, dfilm = _gn_backward(dh, x, gamma, beta, film, stats, coef, dres, dres2, ctx.groups, ctx.act,
+                                                    nig[1] or nig[2])
         return dx, dgamma, dbeta, dfilm, None, None, None, None, None, dw, db, dres_conv
 
 
@@ -1789,8 +1888,11 @@ class TextKVFn(torch.autograd.Function):
                                        _ptr_array([dcn[l] for l in idx]), len(idx), R, cout, D, _dt(cond), _stream()),
                 "mdm_linear_grouped"))
 
+        nig = ctx.needs_input_grad
         for cout, idx in groups.items():   # (see SharedInputLinearsFn.backward: the weight gradients are handed over first)
             # weight / bias gradients: one grouped launch, into the gradient arena when there is one
+            if not any(nig[2 + 4 * l + 2] or nig[2 + 4 * l + 3] for l in idx):
+                continue   # every projection of this width is frozen: no weight-gradient launch
             slots = [(_slot(ws[l]), _slot(bs[l])) for l in idx]
             sunk = all(a is not None and b is not None for a, b in slots)
             if sunk:
@@ -1884,7 +1986,10 @@ class SharedInputLinearsFn(torch.autograd.Function):
         # These layers' gradients arrive when backward ENDS: nothing of the main stream is left to hide behind.  The weight
         # gradients (side stream) are handed over BEFORE the input-gradient launches, so that they wait for what precedes
         # those, not for them (the hand-off makes the side stream wait for everything queued on the main stream so far).
+        nig = ctx.needs_input_grad
         for cout, idx in groups.items():
+            if not any(nig[1 + 2 * l] or nig[2 + 2 * l] for l in idx):
+                continue   # every layer of this width is frozen: no weight-gradient launch
             slots = [(_slot(ws[l]), _slot(bs[l])) for l in idx]
             sunk = all(a is not None and b is not None for a, b in slots)
             if sunk:
@@ -1894,8 +1999,9 @@ class SharedInputLinearsFn(torch.autograd.Function):
                 dbs = [torch.zeros(bs[l].shape, dtype=torch.float32, device=x.device) for l in idx]
             xs2, dy2 = [x] * len(idx), [dys[l] for l in idx]
 
-            def go(xs2=xs2, dy2=dy2, dws=dws, dbs=dbs, idx=idx, sunk=sunk):
-                wgrad_grouped(xs2, dy2, dws, dbs)
+            def go(xs2=xs2, dy2=dy2, dws=dws, dbs=dbs, idx=idx, sunk=sunk, cout=cout):
+                _prof_wrap("conv_wgrad grouped x%d M=%d N=%d K=%d" % (len(idx), R, cout, D), 2.0 * len(idx) * R * cout * D,
+                           lambda: wgrad_grouped(xs2, dy2, dws, dbs))
                 if sunk:
                     for l in idx:
                         _grad_sink.ready(ws[l])
@@ -2394,6 +2500,51 @@ def sampler_jump(x_s, g_t, g_s, noise=None, rng=None, rng_stream=1, gate=None, o
         "mdm_sampler_jump",
     )
     return out
+
+
+def guide_seed(v, x0, a, b, clip="CLIP", thr=None, image_scale=1.0):
+    """Chain rule of loss-guided sampling through the step's x0 = a x_t + b pred, its image scale and its threshold
+    (include/mdm_hip.h mdm_guide_seed) as ONE kernel: ``v`` = d loss / d x0 in image units, ``x0`` what the step kernel
+    returned, ``a`` / ``b`` per-sample [B].  -> (direct, seed): the x_t term and what goes back through the denoiser.
+    ``clip``: "NONE" | "CLIP" | "DYNAMIC" (needs ``thr`` [B]), the mode the step ran with."""
+    v = _img(v)
+    B = v.shape[0]
+    chw = v.numel() // B
+    if chw % 4:
+        raise _lib.MdmHipError("guide_seed: C * H * W must be a multiple of 4 (got %s)" % (tuple(v.shape),))
+    cm = {"NONE": 0, "CLIP": 1, "DYNAMIC": 2}[clip]
+    x0 = _img(x0) if x0 is not None else None
+    if cm and (x0 is None or x0.shape != v.shape):
+        raise _lib.MdmHipError("guide_seed: clip=%r needs x0 shaped like v" % clip)
+    th = _vec(thr, B) if thr is not None else None
+    if cm == 2 and th is None:
+        raise _lib.MdmHipError("guide_seed: clip='DYNAMIC' needs thr=")
+    direct, seed = torch.empty_like(v), torch.empty_like(v)
+    _lib.check(
+        _lib.lib().mdm_guide_seed(_p(v), _p(x0), _p(_vec(a, B)), _p(_vec(b, B)), _p(th), float(image_scale) if image_scale else 1.0,
+                                  cm, _p(direct), _p(seed), B, chw, _stream()),
+        "mdm_guide_seed",
+    )
+    return direct, seed
+
+
+def guide_apply(x, zeta, direct=None, jt=None):
+    """x -= zeta[b] (direct + jt), IN PLACE on ``x`` as ONE kernel (mdm_guide_apply); either term may be None; a sample
+    with zeta[b] == 0 keeps its bits.  -> x"""
+    x = _inplace_img(x, x, "guide_apply: x")
+    B = x.shape[0]
+    chw = x.numel() // B
+    if chw % 4:
+        raise _lib.MdmHipError("guide_apply: C * H * W must be a multiple of 4 (got %s)" % (tuple(x.shape),))
+    if direct is None and jt is None:
+        raise _lib.MdmHipError("guide_apply: give direct= or jt=")
+    d = _img(direct) if direct is not None else None
+    j = _img(jt) if jt is not None else None
+    for t in (d, j):
+        if t is not None and t.shape != x.shape:
+            raise _lib.MdmHipError("guide_apply: gradient %s vs x %s" % (tuple(t.shape), tuple(x.shape)))
+    _lib.check(_lib.lib().mdm_guide_apply(_p(x), _p(d), _p(j), _p(_vec(zeta, B)), B, chw, _stream()), "mdm_guide_apply")
+    return x
 
 
 def noise_images(images, g, eps=None, rng=None, rng_stream=0, inv_scale=1.0):

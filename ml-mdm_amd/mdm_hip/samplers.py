@@ -20,7 +20,10 @@ same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.
 ``sample(..., known_images=, known_mask=, resample=, known_seed=)`` holds a region of every trajectory on a given image
 (the replacement method of RePaint, Lugmayr et al. 2022, with its resampling jumps; ``KnownRegion`` ->
 ``ops.sampler_known_blend`` / ``ops.sampler_jump``), and ``Diffusion.partial_diffusion`` starts a trajectory late from a
-noised image (SDEdit, Meng et al. 2022).
+noised image (SDEdit, Meng et al. 2022).  ``sample(..., guide=LossGuide(fn))`` is the general case of which a known region
+is the special one: every step is pulled towards a small differentiable loss of the clean-image estimate (diffusion
+posterior sampling, Chung et al. 2023), through the denoiser's input gradient (``ops.stem_conv``) and the kernels
+``ops.guide_seed`` / ``ops.guide_apply``.
 """
 import math
 from dataclasses import dataclass
@@ -246,6 +249,73 @@ class KnownRegion:
         return out
 
 
+class LossGuide:
+    """Loss-guided sampling (diffusion posterior sampling, Chung et al. 2023; "universal" / classifier guidance):
+    ``sample(..., guide=LossGuide(fn, scale, normalize))`` pulls every step towards a small ``fn``.
+
+    ``fn(x0) -> loss [B]``: any differentiable torch function of the top-scale clean-image estimate ``x0`` in image units
+    (what ``_postprocess`` returns for it: fp32 ``[B, C, H, W]``), one NON-NEGATIVE scalar per sample.  Per step, with
+    v = d sum_b loss_b / d x0 and x0 = threshold(scale (a x_t + b pred(x_t))) (``get_x0_eps_from_pred``):
+
+        grad = a (v . m) k + J^T [b (v . m) k]         (J = d pred / d x_t: one autograd pass through the denoiser)
+        x_s <- x_s - zeta_b grad,   zeta_b = scale / max(sqrt(loss_b), 1e-8) if normalize (the DPS step) else scale
+
+    The threshold is differentiated as a CLAMP: m = 0 where x0 was clipped, k = image scale (/ the threshold for the
+    dynamic thresholds); the per-sample quantile of a dynamic threshold is treated as a constant.  Lower scales of a nested
+    model receive their J^T part only.  Under classifier-free guidance the seed goes to both halves of the doubled batch
+    with weights s and 1 - s.  A sample whose loss is exactly 0 is left alone.  The step itself (and the history of
+    ``solver="dpmpp_2m"``) is unguided: the correction is applied to x_s, before the known-region blend of
+    ``known_images=``.  Model parameters are frozen for the duration of the call, so the backward pass launches input
+    gradients only.  The MXFP8 layers are inference-only and raise; ``GraphedSampler`` refuses ``guide=``."""
+
+    SQRT_FLOOR = 1e-8
+
+    def __init__(self, fn, scale=1.0, normalize=True):
+        if not callable(fn):
+            raise TypeError("LossGuide: fn must be callable, x0 [B, C, H, W] -> loss [B] (got %r)" % (type(fn).__name__,))
+        self.fn, self.scale, self.normalize = fn, float(scale), bool(normalize)
+
+    def loss_and_grad(self, x0):
+        """-> (loss [B] detached, d sum(loss) / d x0)"""
+        x = x0.detach().requires_grad_(True)
+        with torch.enable_grad():
+            loss = self.fn(x)
+            if not torch.is_tensor(loss) or tuple(loss.shape) != (x.shape[0],):
+                raise ValueError("LossGuide: fn must return one loss per sample, shape (%d,) (got %s)"
+                                 % (x.shape[0], tuple(loss.shape) if torch.is_tensor(loss) else type(loss).__name__))
+            if not loss.requires_grad:
+                raise ValueError("LossGuide: the loss does not depend on x0 (nothing to differentiate)")
+            v, = torch.autograd.grad(loss.sum(), x)
+        return loss.detach(), v
+
+    def zeta(self, loss):
+        """per-sample step size [B], on the loss's device: no host synchronisation"""
+        z = self.scale / loss.sqrt().clamp(min=self.SQRT_FLOOR) if self.normalize else torch.full_like(loss, self.scale)
+        return torch.where(loss > 0, z, torch.zeros_like(z))
+
+
+def _check_guide(guide):
+    if guide is not None and not isinstance(guide, LossGuide):
+        raise TypeError("guide must be an mdm_hip.LossGuide (got %r)" % (type(guide).__name__,))
+
+
+class _frozen_parameters:
+    """requires_grad of every parameter off inside, restored after: a guided step needs input gradients only"""
+
+    def __init__(self, model):
+        self.params = [p for p in model.parameters()] if isinstance(model, nn.Module) else []
+
+    def __enter__(self):
+        self.saved = [p.requires_grad for p in self.params]
+        for p in self.params:
+            p.requires_grad_(False)
+        return self
+
+    def __exit__(self, *a):
+        for p, r in zip(self.params, self.saved):
+            p.requires_grad_(r)
+
+
 class Sampler(nn.Module):
     def __init__(self, sampler_config: SamplerConfig):
         super().__init__()
@@ -336,10 +406,12 @@ class Sampler(nn.Module):
     # ---- one reverse step (:281-345) -------------------------------------------------------
     def get_prediction_xt_last(self, x_t, pred, g, g_last, prediction_type=None, clip_fn=None, need_noise=False,
                                ddim_eta=None, input_noise=None, image_scale=None, return_eps=True, pred_uncond=None,
-                               guidance_scale=1):
+                               guidance_scale=1, thr_out=None):
+        """``thr_out``: a list of the caller's; the per-sample dynamic threshold of this step (None for the other threshold
+        functions) is appended to it -- what a ``LossGuide`` needs of the step besides x0"""
         if x_t.is_cuda and (clip_fn is None or clip_fn == self.clip_sample):
             return self._xt_last_hip(x_t, pred, g, g_last, prediction_type, clip_fn is not None, need_noise, ddim_eta,
-                                     input_noise, image_scale, return_eps, pred_uncond, guidance_scale)
+                                     input_noise, image_scale, return_eps, pred_uncond, guidance_scale, thr_out)
         if pred_uncond is not None:
             pred = pred_uncond + guidance_scale * (pred - pred_uncond)
         alpha = g / g_last
@@ -347,6 +419,8 @@ class Sampler(nn.Module):
         beta_tilde = beta * (1 - g_last) / (1 - g)
         x0 = self.get_x0_eps_from_pred(x_t, pred, g, prediction_type=prediction_type, return_eps=False)
         scale = 1 if image_scale is None else image_scale
+        if thr_out is not None:
+            thr_out.append(self._dynamic_thr(x0 * scale) if clip_fn == self.clip_sample else None)
         x0 = torch.clip(x0, -scale, scale) / scale if clip_fn is None else clip_fn(x0, scale)
         if ddim_eta is None:  # ancestral DDPM posterior mean
             x_last = x0 * beta * g_last.sqrt() / (1 - g) + x_t * alpha.sqrt() * (1 - g_last) / (1 - g)
@@ -365,7 +439,7 @@ class Sampler(nn.Module):
         return x0, x_last, eps
 
     def _xt_last_hip(self, x_t, pred, g, g_last, prediction_type, use_clip_sample, need_noise, ddim_eta, input_noise,
-                     image_scale, return_eps, pred_uncond, guidance_scale):
+                     image_scale, return_eps, pred_uncond, guidance_scale, thr_out=None):
         """the same update as ONE kernel (two for dynamic thresholding: the quantile sits between them)"""
         pt = prediction_type or self._config.prediction_type
         scale = 1 if image_scale is None else image_scale
@@ -373,6 +447,8 @@ class Sampler(nn.Module):
         kw = dict(prediction_type=pt, ddim_eta=ddim_eta, image_scale=scale, guidance_scale=guidance_scale,
                   pred_uncond=None if pred_uncond is None else pred_uncond.float())
         clip, thr = self._hip_clip(x_t, pred, g, g_last, use_clip_sample, scale, kw)
+        if thr_out is not None:
+            thr_out.append(thr)
         noisy = need_noise and not (ddim_eta is not None and ddim_eta <= 0)
         noise = input_noise
         if noisy and noise is None and self.device_rng is None:
@@ -390,9 +466,8 @@ class Sampler(nn.Module):
         fn = self._config.threshold_function if use_clip_sample else None
         thr, clip = None, "NONE"
         if fn in (ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF):
-            ratio, vmax = (0.995, 100) if fn == ThresholdType.DYNAMIC else (0.95, 1.5)
             x0s, _ = ops.sampler_step(x_t, pred, g, g_last, clip="X0_ONLY", **kw)
-            thr = torch.quantile(x0s.reshape(x0s.shape[0], -1).abs(), ratio, dim=1).clamp(min=1, max=vmax)
+            thr = self._dynamic_thr(x0s)
             clip = "DYNAMIC"
         elif fn == ThresholdType.CLIP:
             clip = "CLIP"
@@ -403,10 +478,20 @@ class Sampler(nn.Module):
             clip = "CLIP"
         return clip, thr
 
+    def _dynamic_thr(self, x0s):
+        """the per-sample threshold [B] of the dynamic threshold functions for the unclipped x0 in image units (the clamped
+        quantile of its magnitude, as ``_threshold_sample`` takes it), None for the others"""
+        fn = self._config.threshold_function
+        if fn not in (ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF):
+            return None
+        ratio, vmax = (0.995, 100) if fn == ThresholdType.DYNAMIC else (0.95, 1.5)
+        flat = x0s if x0s.dtype == torch.float64 else x0s.float()
+        return torch.quantile(flat.reshape(flat.shape[0], -1).abs(), ratio, dim=1).clamp(min=1, max=vmax)
+
     # ---- one step of DPM-Solver++(2M) (not in the reference) ------------------------------------------
     def get_prediction_xt_last_2m(self, x_t, pred, g, g_last, g_prev=None, x0_prev=None, second_order=False,
                                   prediction_type=None, clip_fn=None, image_scale=None, pred_uncond=None,
-                                  guidance_scale=1):
+                                  guidance_scale=1, thr_out=None):
         """One update of DPM-Solver++(2M) (Lu et al. 2022, multistep, data prediction) -> (x0, x_last).
 
         Guidance combine, x0 and threshold as ``get_prediction_xt_last``; then, with alpha = sqrt(gamma), sigma =
@@ -426,12 +511,16 @@ class Sampler(nn.Module):
             kw = dict(prediction_type=pt, image_scale=scale, guidance_scale=guidance_scale,
                       pred_uncond=None if pred_uncond is None else pred_uncond.float())
             clip, thr = self._hip_clip(x_t, pred, g, g_last, clip_fn is not None, scale, kw)
+            if thr_out is not None:
+                thr_out.append(thr)
             return ops.sampler_step_2m(x_t, pred, g, g_last, g_prev=g_prev, x0_prev=x0_prev, second_order=second_order,
                                        clip=clip, thr=thr, **kw)
         if pred_uncond is not None:
             pred = pred_uncond + guidance_scale * (pred - pred_uncond)
         x0 = self.get_x0_eps_from_pred(x_t, pred, g, prediction_type=prediction_type, return_eps=False)
         scale = 1 if image_scale is None else image_scale
+        if thr_out is not None:
+            thr_out.append(self._dynamic_thr(x0 * scale) if clip_fn == self.clip_sample else None)
         x0 = torch.clip(x0, -scale, scale) / scale if clip_fn is None else clip_fn(x0, scale)
         D = x0
         if second_order:
@@ -447,7 +536,7 @@ class Sampler(nn.Module):
     def _threshold_sample(self, sample, ratio=0.995, max_value=100):
         """Imagen dynamic thresholding (:461-498)."""
         shape, dtype = sample.shape, sample.dtype
-        flat = sample.float().reshape(shape[0], -1)
+        flat = (sample if sample.dtype == torch.float64 else sample.float()).reshape(shape[0], -1)   # fp64 stays fp64
         s = torch.quantile(flat.abs(), ratio, dim=1).clamp(min=1, max=max_value).unsqueeze(1)
         return (torch.clamp(flat, -s, s) / s).reshape(shape).to(dtype)
 
@@ -460,6 +549,56 @@ class Sampler(nn.Module):
         if fn == ThresholdType.DYNAMIC_IF:
             return self._threshold_sample(pred_x0 * s, 0.95, 1.5) / s
         return pred_x0
+
+    # ---- loss-guided sampling (LossGuide; not in the reference) ---------------------------------------
+    def _x0_coeffs(self, g, prediction_type=None):
+        """(a, b) of x0 = a x_t + b pred (``get_x0_eps_from_pred``), shaped like ``g``"""
+        pt = prediction_type or self._config.prediction_type
+        if pt in (PredictionType.DDPM, PredictionType.DDIM):
+            return 1 / g.sqrt(), -(1 - g).sqrt() / g.sqrt()
+        if pt == PredictionType.V_PREDICTION:
+            return g.sqrt(), -(1 - g).sqrt()
+        raise ValueError("unsupported prediction type")
+
+    def _guide_update(self, guide, x_in, preds, x0, x_s, g, image_scale, guidance_scale, thr=None):
+        """The guide's correction of one step.  Lists hi -> lo: ``x_in`` the leaves the model was run on, ``preds`` the
+        (conditional, unconditional or None) predictions still attached to the tape, ``x_s`` the step's results; ``x0`` /
+        ``g`` / ``image_scale`` / ``thr``: the top scale's clean-image estimate as the step returned it, its gamma, image scale
+        and dynamic threshold (``thr_out`` of the step; None for the other threshold functions).
+        -> the corrected ``x_s`` list (GPU tensors: in place)"""
+        scale = image_scale if image_scale else 1
+        loss, v = guide.loss_and_grad(x0 * scale if scale != 1 else x0)
+        a, b = self._x0_coeffs(g)
+        fn = self._config.threshold_function
+        dynamic = fn in (ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF)
+        pc, pu = preds[0]
+        if x0.is_cuda:
+            clip = "DYNAMIC" if dynamic else ("CLIP" if fn == ThresholdType.CLIP else "NONE")
+            direct, seed = ops.guide_seed(v.float(), x0, a, b, clip=clip, thr=thr if dynamic else None, image_scale=scale)
+        else:
+            w = v * scale
+            if fn != ThresholdType.NONE:
+                # clipped: x0 = +-fl(1 / scale), and fl(fl(1 / scale) scale) is 1 or a rounding below it when scale is no
+                # power of two -- four ulps of slack, as the kernel takes (mdm_guide_seed)
+                w = w * ((x0 * scale).abs() < 1 - 4 * torch.finfo(x0.dtype).eps).to(v.dtype)
+            if dynamic:   # the quantile the step's clip_sample took, as a constant
+                w = w / _b(thr).to(v.dtype)
+            direct, seed = a * w, b * w
+        seed = seed.to(pc.dtype)
+        outs, seeds = ([pc], [seed]) if pu is None else ([pc, pu], [guidance_scale * seed, (1 - guidance_scale) * seed])
+        jts = torch.autograd.grad(outs, x_in, grad_outputs=seeds, allow_unused=True)
+        zeta = guide.zeta(loss)
+        out = list(x_s)
+        for i, (x, jt) in enumerate(zip(x_s, jts)):
+            d = direct if i == 0 else None
+            if d is None and jt is None:
+                continue
+            if x.is_cuda:
+                out[i] = ops.guide_apply(x, zeta, direct=d, jt=None if jt is None else jt.float())
+            else:
+                grad = d if jt is None else (jt if d is None else d + jt)
+                out[i] = x - _b(zeta).to(x.dtype) * grad
+        return out
 
     def forward_model(self, model, x_t, t, lm_outputs, lm_mask, micros={}, guidance_scale=1):
         """classifier-free guidance doubles the batch: [uncond | cond] (:435-459)."""
@@ -479,29 +618,48 @@ class Sampler(nn.Module):
 
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False):
+                       second_order=False, guide=None):
         """``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is the caller's
         dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
-        ``second_order`` (decided by the caller: off on the first and on the last step) uses it."""
+        ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``guide``: a
+        ``LossGuide`` -- the model runs on a leaf x_t with grad enabled, the step itself unchanged under no_grad, and the
+        guide's correction is applied to its x_s."""
         _check_solver(solver, ddim_eta)
+        _check_guide(guide)
         ones = torch.ones(x_t.shape[0], dtype=torch.long, device=self.gammas.device)
         last = time_step - 1 if time_step_last is None else time_step_last
         t, s = ones * time_step, ones * last
         g, g_last = self.read_gamma(t), self.read_gamma(s)
+        if guide is not None:
+            x_in = x_t.detach().requires_grad_(True)
+            with torch.enable_grad():
+                pc, pu, _ = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
+            thr = []
+            with torch.no_grad():   # the step itself: unchanged, on detached tensors
+                x0, x_s = self._step(x_in.detach(), pc.detach(), None if pu is None else pu.detach(), g, g_last, last,
+                                     guidance_scale, ddim_eta, solver, solver_state, second_order, thr_out=thr)
+            x_s = self._guide_update(guide, [x_in], [(pc, pu)], x0, [x_s], g, self._config.rescale_signal, guidance_scale,
+                                     thr[0])[0]
+            return (x0, x_s, (g, g_last)) if return_details else x_s
         pc, pu, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
+        x0, x_s = self._step(x_t, pc, pu, g, g_last, last, guidance_scale, ddim_eta, solver, solver_state, second_order)
+        return (x0, x_s, (g, g_last)) if return_details else x_s
+
+    def _step(self, x_t, pc, pu, g, g_last, last, guidance_scale, ddim_eta, solver, solver_state, second_order, thr_out=None):
+        """the update of ``get_xt_minus_1`` behind the denoiser call -> (x0, x_s)"""
         if solver is not None:
             st = {} if solver_state is None else solver_state
             x0, x_s = self.get_prediction_xt_last_2m(
                 x_t, pc, g, g_last, g_prev=st.get("g"), x0_prev=st.get("x0"), second_order=second_order,
                 prediction_type=self._config.prediction_type, clip_fn=self.clip_sample,
-                image_scale=self._config.rescale_signal, pred_uncond=pu, guidance_scale=guidance_scale)
+                image_scale=self._config.rescale_signal, pred_uncond=pu, guidance_scale=guidance_scale, thr_out=thr_out)
             st["x0"], st["g"] = x0, g
-            return (x0, x_s, (g, g_last)) if return_details else x_s
+            return x0, x_s
         x0, x_s, _ = self.get_prediction_xt_last(
             x_t, pc, g, g_last, prediction_type=self._config.prediction_type, need_noise=bool(last != 0),
             ddim_eta=ddim_eta, clip_fn=self.clip_sample, image_scale=self._config.rescale_signal, return_eps=False,
-            pred_uncond=pu, guidance_scale=guidance_scale)
-        return (x0, x_s, (g, g_last)) if return_details else x_s
+            pred_uncond=pu, guidance_scale=guidance_scale, thr_out=thr_out)
+        return x0, x_s
 
     # ---- the sampling loop (:510-609) ----------------------------------------------------------
     def set_timesteps(self, num_inference_steps=250):
@@ -514,8 +672,28 @@ class Sampler(nn.Module):
         (``resample_steps=True, num_inference_steps=20..50``)."""
         _check_solver(kwargs.get("solver"), kwargs.get("ddim_eta"))   # here, not at the generator's first next()
         _check_known(kwargs.get("known_images"), kwargs.get("resample", 1), kwargs.get("solver"))
+        guide = kwargs.get("guide")
+        _check_guide(guide)
         gen = self._sample(*args, **kwargs)
-        return gen if kwargs.get("yield_output", False) else next(gen)
+        if guide is None:
+            return gen if kwargs.get("yield_output", False) else next(gen)
+        # a guided call freezes the parameters while it computes (the backward passes launch input gradients only) and
+        # hands them back before it returns -- around every item of a yield_output generator, not across the caller's code
+        model = args[0] if args else kwargs["model"]
+        if not kwargs.get("yield_output", False):
+            with _frozen_parameters(model):
+                return next(gen)
+        return self._frozen_items(gen, model)
+
+    @staticmethod
+    def _frozen_items(gen, model):
+        while True:
+            with _frozen_parameters(model):
+                try:
+                    item = next(gen)
+                except StopIteration:
+                    return
+            yield item
 
     def _scale_info(self, model):
         """-> (top side / side, image_scale) of every scale, hi -> lo: what the step kernel of that scale gets"""
@@ -538,8 +716,10 @@ class Sampler(nn.Module):
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-                known_noise_fn=None, **post_args):
-        """``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
+                known_noise_fn=None, guide=None, **post_args):
+        """``guide``: a ``LossGuide`` -- loss-guided sampling; per step: the update, then the guide's correction, then the
+        known-region blend.  ``guide=None`` leaves every step as it is.
+        ``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
         whichever update made it, every scale's x_s is replaced where the mask is 1 by the known image diffused to that
         scale's target gamma (``known_blend``; the last step goes to gamma = 1: the known region of the result IS the known
         image).  ``resample = r > 1`` (RePaint's jumps of length 1): every step but the last is taken r times, with the
@@ -549,6 +729,8 @@ class Sampler(nn.Module):
         assert not (yield_output and return_sequence)
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
+        _check_guide(guide)
+        extra_kw = {} if guide is None else {"guide": guide}
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -571,7 +753,7 @@ class Sampler(nn.Module):
             for rep in range(reps):
                 x0, x_t, extra = self.get_xt_minus_1(
                     model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
-                    guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, **order)
+                    guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, **order, **extra_kw)
                 if known is not None:
                     is_list = isinstance(x_t, (list, tuple))
                     xs = list(x_t) if is_list else [x_t]
@@ -643,10 +825,11 @@ class NestedSampler(Sampler):
 
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False):
-        """``solver`` / ``solver_state`` / ``second_order`` as ``Sampler.get_xt_minus_1``; the history holds one x0 and
-        one gamma per scale"""
+                       second_order=False, guide=None):
+        """``solver`` / ``solver_state`` / ``second_order`` / ``guide`` as ``Sampler.get_xt_minus_1``; the history holds one
+        x0 and one gamma per scale; the guide's loss sees the top scale, every scale's x_t is a leaf"""
         _check_solver(solver, ddim_eta)
+        _check_guide(guide)
         scales = model.vision_model.nest_ratio + [1]
         if isinstance(x_t, torch.Tensor):  # first step: draw independent noise at every lower resolution (:669-676)
             pyramid = [x_t]
@@ -659,7 +842,26 @@ class NestedSampler(Sampler):
         s = t - 1 if time_step_last is None else ones * time_step_last
         g_t = self.get_gammas(self.read_gamma(t), scales)
         g_s = self.get_gammas(self.read_gamma(s), scales)
+        if guide is not None:
+            x_in = [x.detach().requires_grad_(True) for x in x_t]
+            with torch.enable_grad():
+                pcs, pus = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
+            thr = []   # one entry per scale, hi -> lo
+            with torch.no_grad():   # the step itself: unchanged, on detached tensors
+                x0, x_s = self._steps([x.detach() for x in x_in], [p.detach() for p in pcs],
+                                      [None if p is None else p.detach() for p in pus], g_t, g_s, scales, time_step,
+                                      guidance_scale, ddim_eta, solver, solver_state, second_order, thr_out=thr)
+            x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0],
+                                     1 if self._config.schedule_shifted else scales[0], guidance_scale, thr[0])
+            return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
         pcs, pus = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
+        x0, x_s = self._steps(x_t, pcs, pus, g_t, g_s, scales, time_step, guidance_scale, ddim_eta, solver, solver_state,
+                              second_order)
+        return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
+
+    def _steps(self, x_t, pcs, pus, g_t, g_s, scales, time_step, guidance_scale, ddim_eta, solver, solver_state, second_order,
+               thr_out=None):
+        """the per-scale updates of ``get_xt_minus_1`` behind the denoiser call -> (x0 list, x_s list)"""
         x0, x_s = [], []
         if solver is not None:
             st = {} if solver_state is None else solver_state
@@ -669,19 +871,19 @@ class NestedSampler(Sampler):
                     x, pc, g, gl, g_prev=gp, x0_prev=xp, second_order=second_order,
                     prediction_type=self._config.prediction_type, clip_fn=self.clip_sample,
                     image_scale=sc if not self._config.schedule_shifted else 1, pred_uncond=pu,
-                    guidance_scale=guidance_scale)
+                    guidance_scale=guidance_scale, thr_out=thr_out)
                 x0.append(a)
                 x_s.append(b)
             st["x0"], st["g"] = x0, g_t
-            return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
+            return x0, x_s
         for x, pc, pu, g, gl, sc in zip(x_t, pcs, pus, g_t, g_s, scales):
             a, b, _ = self.get_prediction_xt_last(
                 x, pc, g, gl, prediction_type=self._config.prediction_type, need_noise=bool(time_step != 1),
                 ddim_eta=ddim_eta, clip_fn=self.clip_sample, image_scale=sc if not self._config.schedule_shifted else 1,
-                return_eps=False, pred_uncond=pu, guidance_scale=guidance_scale)
+                return_eps=False, pred_uncond=pu, guidance_scale=guidance_scale, thr_out=thr_out)
             x0.append(a)
             x_s.append(b)
-        return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
+        return x0, x_s
 
     def _postprocess(self, x_t, x0=None, extra=None, yield_full=False, clip=False, output_inner=False, **unused):
         scales = [1 if self._config.schedule_shifted else x.size(-1) / x_t[-1].size(-1) for x in x_t]

@@ -14,8 +14,11 @@ libmdm_hip (see ``ops.py``): implicit-GEMM convs on MFMA, fused
 GroupNorm(+FiLM)(+SiLU), flash-style self+cross attention.  Internally every
 activation is an NHWC tensor of the compute dtype (fp32 parity mode or bf16).
 
-Not supported (raise): temporal/video mode and the LM-head ``SelfAttention1D``
-blocks -- no shipped config enables them.
+Not supported (raise): temporal/video mode -- no shipped config enables it
+(SURVEY.md section 2, row 1).  The LM-head ``SelfAttention1D`` blocks are implemented.
+
+Autograd reaches the model's own input: when ``x_t`` requires grad the stem runs as
+``ops.stem_conv`` (the same two launches forward; ``mdm_conv3x3_stem_dgrad`` backward).
 """
 import copy
 import logging
@@ -657,6 +660,9 @@ class UNet(nn.Module):
             x_t = x_t[0]
         if normalize:   # per-sample x / std (reference :871-872), its own kernel pair
             x_t = ops.sample_std_normalize(x_t.float())
+        if torch.is_grad_enabled() and x_t.requires_grad:
+            # the same two launches, as one node whose backward reaches x_t (the stem's padded Cin has no dgrad pack)
+            return ops.stem_conv(x_t, self.conv_in.weight, self.conv_in.bias, compute_dtype())
         return ops.conv(ops.to_nhwc(x_t, compute_dtype()), self.conv_in.weight, self.conv_in.bias)
 
     def forward_output_layer(self, x):

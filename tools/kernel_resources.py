@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Register / spill / occupancy / LDS table of every kernel of the gfx950 build, from the compiler's own report
 (hipcc -O3 -Rpass-analysis=kernel-resource-usage; no GPU needed).
-   python tools/kernel_resources.py > profiles/rNN_kernel_resources.txt"""
+   python tools/kernel_resources.py > profiles/rNN_kernel_resources.txt
+   python tools/kernel_resources.py LABEL stem.hip ...      # only these sources of csrc/"""
 import glob
 import os
 import re
@@ -33,7 +34,10 @@ def main():
     print("Kernel resources of the gfx950 build (hipcc -O3 -Rpass-analysis=kernel-resource-usage, ROCm 7.2), %s." % (sys.argv[1] if len(sys.argv) > 1 else "HEAD"))
     print("VGPR + AGPR share the 512-entry file of a SIMD lane: waves / SIMD = floor(512 / (VGPRs + AGPRs)), capped by LDS and the block size.")
     print("%-100s %5s %5s %6s %7s %6s %9s" % ("kernel", "VGPR", "AGPR", "spill", "scratch", "occ", "LDS bytes"))
+    only = set(sys.argv[2:])
     for src in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        if only and os.path.basename(src) not in only:
+            continue
         p = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", src, "-o", "/dev/null",
                             "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
         if p.returncode != 0:

@@ -4,7 +4,7 @@ LDS / global store) with too few wait states when the read sits on the TAKEN edg
 recognizer covered the fall-through path only (conv3x3_direct_kernel<64, 64, 8, 32, 4>, HISTORY.md section 4.1e).
 Walks every path of up to 10 wait states after each v_mfma (following branches) and reports reads of its destination
 registers that come earlier than `MIN_WS` (the compiler itself leaves 11 in straight-line code).  CPU-only:
-   python tools/mfma_hazard_scan.py            # csrc/gemm_conv.hip, attention.hip and fp8.hip to ISA; exits 1 on a finding
+   python tools/mfma_hazard_scan.py            # csrc/gemm_conv.hip, attention.hip, fp8.hip and stem.hip to ISA; exits 1 on a finding
    python tools/mfma_hazard_scan.py fp8.hip    # one source only
 Also checks, on the same ISA, that no kernel spills more than SPILL_CAP vector registers, and that the bias-gradient dot
 products of conv_wgrad_bl_kernel still sit behind scalar branches (round 5: as plain code hipcc if-converted them into every
@@ -132,7 +132,7 @@ def loads_between_wide_stores(path):
 
 
 def main():
-    srcs = sys.argv[1:] or ["gemm_conv.hip", "attention.hip", "fp8.hip"]
+    srcs = sys.argv[1:] or ["gemm_conv.hip", "attention.hip", "fp8.hip", "stem.hip"]
     bad = 0
     with tempfile.TemporaryDirectory() as td:
         for s in srcs:
