@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .samplers import NestedSampler, ThresholdType, _check_known, _check_solver
+from .samplers import _check_known, _check_solver
 
 
 class GraphedDenoiser(nn.Module):
@@ -115,9 +115,6 @@ class GraphedSampler:
         self._seed = seed
         self._graphs = {}
         self._adapter_epoch = ops.adapter_epoch()
-        fn = self.sampler._config.threshold_function
-        if fn not in (ThresholdType.CLIP, ThresholdType.NONE, ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF):
-            raise NotImplementedError("GraphedSampler: unknown threshold function %r" % (fn,))
 
     def reset(self):
         self._graphs.clear()
@@ -126,9 +123,7 @@ class GraphedSampler:
     def _tables(self, n_steps, device, resample=1):
         steps = self.sampler.set_timesteps(n_steps)                 # n+1 entries, descending, last = 0
         t, s = steps[:-1], steps[1:]
-        nested = isinstance(self.sampler, NestedSampler)
-        # the last step adds no noise: Sampler tests `last != 0` (:421), NestedSampler `time_step != 1` (:700)
-        gate = (t != 1) if nested else (s != 0)
+        gate = self.sampler._noisy_step(t, s)   # the last step adds no noise
         mk = lambda a, dt: torch.as_tensor(a.copy()).to(device=device, dtype=dt)
         # dpmpp_2m: the time of the step before (step 0 has none: its own, never used) and the order gate -- second order
         # wherever there is history and a finite step in log-SNR, i.e. not on the first and not on the last step
@@ -146,13 +141,12 @@ class GraphedSampler:
                 mk(order, torch.float32), mk(jump, torch.float32)), t
 
     def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1):
-        smp, cfg = self.sampler, self.sampler._config
+        smp = self.sampler
         model = self.pipe.get_model()
         vm = model.vision_model
         dev = xs[0].device
-        nested = isinstance(smp, NestedSampler)
         B = xs[0].shape[0]
-        scales = (vm.nest_ratio + [1]) if nested else [1]
+        image_scales = smp._scale_info(model)[1]
         (tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump), t_host = self._tables(n_steps, dev, resample)
         idx = torch.zeros(1, dtype=torch.long, device=dev)
         rng = ops.DeviceRng(self._seed, dev)
@@ -172,60 +166,38 @@ class GraphedSampler:
         ce, cs, cm = vm.forward_conditioning(cond, mask)
         ce_s, cs_s, cm_s = ce.clone(), cs.clone(), (cm.clone() if cm is not None else None)
         out_scale = model._output_scale
-        fn = cfg.threshold_function
-        clip = {ThresholdType.CLIP: "CLIP", ThresholdType.NONE: "NONE"}.get(fn, "DYNAMIC")
-        # Imagen dynamic thresholding (samplers.py:461-498): a per-sample quantile of |x0| sits between two launches of
-        # the step kernel (x0 only, then the update with the threshold) -- torch.quantile is a sort + lerp on the
-        # device, so it is captured with the rest
-        dyn = {ThresholdType.DYNAMIC: (0.995, 100.0), ThresholdType.DYNAMIC_IF: (0.95, 1.5)}.get(fn)
-        noisy = solver is None and not (ddim_eta is not None and ddim_eta <= 0)
 
         def body():
             t = tab_t.index_select(0, idx)
             s = tab_s.index_select(0, idx)
             gate = tab_gate.index_select(0, idx)
-            g_t, g_s = smp.gammas.index_select(0, t).expand(B), smp.gammas.index_select(0, s).expand(B)
-            if nested:
-                g_t, g_s = smp.get_gammas(g_t, scales), smp.get_gammas(g_s, scales)
-            else:
-                g_t, g_s = [g_t], [g_s]
-            if solver is not None:
-                order = tab_order.index_select(0, idx)
-                g_p = smp.gammas.index_select(0, tab_p.index_select(0, idx)).expand(B)
-                g_p = smp.get_gammas(g_p, scales) if nested else [g_p]
+            gammas = lambda time: smp._gammas_of_scales(model, smp.gammas.index_select(0, time).expand(B))
+            g_t, g_s = gammas(t), gammas(s)
+            history = {}
+            if solver is not None:   # the history lives in x0_prev: the step kernel updates it in place
+                history = dict(second_order=tab_order.index_select(0, idx), g_prev=gammas(tab_p.index_select(0, idx)),
+                               x0_prev=x0_prev, x0_out=x0_prev)
             times = (t - 1).expand(B)
             if guidance != 1:
                 xin = [torch.cat([x, x]) for x in x_static]
                 tin = torch.cat([times, times])
             else:
                 xin, tin = x_static, times
-            preds = vm.forward_denoising(xin if nested else xin[0], tin, ce_s, cs_s, cm_s, micros_s)
-            preds = list(preds) if nested else [preds]
+            preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
+            preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
                 preds = [torch.tanh(p / out_scale) * out_scale for p in preds]
-            for i, (x, p, sc) in enumerate(zip(x_static, preds, scales)):
-                pu = None
-                if guidance != 1:
-                    pu, p = p.chunk(2)
-                img_scale = (sc if not cfg.schedule_shifted else 1) if nested else (cfg.rescale_signal or 1)
-                thr = None
-                if dyn is not None:
-                    x0s, _ = ops.sampler_step(x, p, g_t[i], g_s[i], cfg.prediction_type, ddim_eta=ddim_eta, clip="X0_ONLY",
-                                              image_scale=img_scale, pred_uncond=pu, guidance_scale=guidance)
-                    thr = torch.quantile(x0s.reshape(B, -1).abs(), dyn[0], dim=1).clamp(min=1, max=dyn[1])
-                if solver is not None:
-                    _, x_last = ops.sampler_step_2m(x, p, g_t[i], g_s[i], cfg.prediction_type, g_prev=g_p[i],
-                                                    x0_prev=x0_prev[i], second_order=order, clip=clip, thr=thr,
-                                                    image_scale=img_scale, pred_uncond=pu, guidance_scale=guidance,
-                                                    x0_out=x0_prev[i])
-                    x.copy_(x_last)
-                    continue
-                _, x_last = ops.sampler_step(x, p, g_t[i], g_s[i], cfg.prediction_type, ddim_eta=ddim_eta, need_noise=noisy,
-                                             rng=rng, clip=clip, thr=thr, image_scale=img_scale, pred_uncond=pu,
-                                             guidance_scale=guidance, noise_gate=gate)
-                if noisy:
-                    rng.advance(x.numel())   # same draw order as the eager sampler with use_device_rng()
-                x.copy_(x_last)
+            pus = [None] * len(preds)
+            if guidance != 1:
+                pus, preds = zip(*(p.chunk(2) for p in preds))
+            # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> torch.quantile, a
+            # sort + lerp on the device, -> update kernel, all captured).  Every row draws and advances the generator in
+            # the eager sampler's order (use_device_rng()); the device gate decides whether the noise is added
+            _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, need_noise=True,
+                                         guidance_scale=guidance, ddim_eta=ddim_eta, solver=solver, rng=rng, noise_gate=gate,
+                                         **history)
+            for x, xl in zip(x_static, x_last):
+                x.copy_(xl)
             if known is not None:   # blends hi -> lo, then jumps hi -> lo: the draw order of KnownRegion
                 for i, x in enumerate(x_static):
                     if kn_img[i] is not None:
@@ -292,15 +264,12 @@ class GraphedSampler:
             self._adapter_epoch = ops.adapter_epoch()
         self.pipe.eval()
         smp = self.sampler
-        nested = isinstance(smp, NestedSampler)
         model = self.pipe.get_model()
         if start_noise is None:
             x = self.pipe.get_noise(num_examples, model.input_channels, image_side, device)
-            xs = [x]
-            if nested:   # independent noise at every lower resolution (:669-676)
-                scales = model.vision_model.nest_ratio + [1]
-                xs += [torch.randn(num_examples, x.shape[1], image_side * s // scales[0], image_side * s // scales[0], device=x.device)
-                       for s in scales[1:]]
+            # independent noise at every lower resolution (:669-676)
+            xs = [x] + [torch.randn(num_examples, x.shape[1], image_side // r, image_side // r, device=x.device)
+                        for r in smp._scale_info(model)[0][1:]]
         else:
             xs = [t.to(device).float() for t in (start_noise if isinstance(start_noise, (list, tuple)) else [start_noise])]
         cond, mask = sample["lm_outputs"], sample["lm_mask"]
@@ -353,4 +322,4 @@ class GraphedSampler:
         if order_row is not None:
             order_row.copy_(saved)
         out = [x.clone() for x in ent["x"]]
-        return smp._postprocess(out if nested else out[0], clip=True)
+        return smp._postprocess(smp._from_scales(out), clip=True)

@@ -406,22 +406,31 @@ class Sampler(nn.Module):
     # ---- one reverse step (:281-345) -------------------------------------------------------
     def get_prediction_xt_last(self, x_t, pred, g, g_last, prediction_type=None, clip_fn=None, need_noise=False,
                                ddim_eta=None, input_noise=None, image_scale=None, return_eps=True, pred_uncond=None,
-                               guidance_scale=1, thr_out=None):
+                               guidance_scale=1, thr_out=None, rng=None, noise_gate=None):
         """``thr_out``: a list of the caller's; the per-sample dynamic threshold of this step (None for the other threshold
-        functions) is appended to it -- what a ``LossGuide`` needs of the step besides x0"""
-        if x_t.is_cuda and (clip_fn is None or clip_fn == self.clip_sample):
-            return self._xt_last_hip(x_t, pred, g, g_last, prediction_type, clip_fn is not None, need_noise, ddim_eta,
-                                     input_noise, image_scale, return_eps, pred_uncond, guidance_scale, thr_out)
-        if pred_uncond is not None:
-            pred = pred_uncond + guidance_scale * (pred - pred_uncond)
+        functions) is appended to it -- what a ``LossGuide`` needs of the step besides x0.  GPU tensors only: ``rng`` (an
+        ``ops.DeviceRng`` instead of ``self.device_rng``) and ``noise_gate`` (a device float[1]; 0 = add no noise), which is
+        how one captured graph serves every step."""
+        if self._on_hip(x_t, clip_fn):   # the same update as ONE kernel (two for dynamic thresholding)
+            x_t, pred, kw = self._hip_step_args(x_t, pred, g, g_last, prediction_type, clip_fn, image_scale, pred_uncond,
+                                                guidance_scale, thr_out, ddim_eta)
+            rng = self.device_rng if rng is None else rng
+            noisy = need_noise and not (ddim_eta is not None and ddim_eta <= 0)
+            noise = input_noise
+            if noisy and noise is None and rng is None:
+                noise = torch.randn_like(x_t)   # torch's generator, like the reference (:340)
+            x0, x_last = ops.sampler_step(x_t, pred, g, g_last, ddim_eta=ddim_eta, need_noise=noisy, noise=noise, rng=rng,
+                                          noise_gate=noise_gate, **kw)
+            if noisy and noise is None:
+                rng.advance(x_t.numel())
+            eps = (x_last - _b(g_last).sqrt() * x0) / (1 - _b(g_last)).sqrt() if return_eps else None
+            return x0, x_last, eps
+        if rng is not None or noise_gate is not None:
+            raise ValueError("rng= and noise_gate= belong to the step kernel: GPU tensors only")
         alpha = g / g_last
         beta = 1 - alpha
         beta_tilde = beta * (1 - g_last) / (1 - g)
-        x0 = self.get_x0_eps_from_pred(x_t, pred, g, prediction_type=prediction_type, return_eps=False)
-        scale = 1 if image_scale is None else image_scale
-        if thr_out is not None:
-            thr_out.append(self._dynamic_thr(x0 * scale) if clip_fn == self.clip_sample else None)
-        x0 = torch.clip(x0, -scale, scale) / scale if clip_fn is None else clip_fn(x0, scale)
+        x0 = self._x0_thresholded(x_t, pred, g, prediction_type, clip_fn, image_scale, pred_uncond, guidance_scale, thr_out)
         if ddim_eta is None:  # ancestral DDPM posterior mean
             x_last = x0 * beta * g_last.sqrt() / (1 - g) + x_t * alpha.sqrt() * (1 - g_last) / (1 - g)
         else:
@@ -438,45 +447,45 @@ class Sampler(nn.Module):
         eps = (x_last - g_last.sqrt() * x0) / (1 - g_last).sqrt() if return_eps else None
         return x0, x_last, eps
 
-    def _xt_last_hip(self, x_t, pred, g, g_last, prediction_type, use_clip_sample, need_noise, ddim_eta, input_noise,
-                     image_scale, return_eps, pred_uncond, guidance_scale, thr_out=None):
-        """the same update as ONE kernel (two for dynamic thresholding: the quantile sits between them)"""
-        pt = prediction_type or self._config.prediction_type
+    def _on_hip(self, x_t, clip_fn):
+        """GPU tensors take the step kernels, unless a custom ``clip_fn`` asks for the torch ops"""
+        return x_t.is_cuda and (clip_fn is None or clip_fn == self.clip_sample)
+
+    def _x0_thresholded(self, x_t, pred, g, prediction_type, clip_fn, image_scale, pred_uncond, guidance_scale, thr_out):
+        """what both updates start with, in torch ops: guidance combine, x0, threshold -> x0"""
+        if pred_uncond is not None:
+            pred = pred_uncond + guidance_scale * (pred - pred_uncond)
+        x0 = self.get_x0_eps_from_pred(x_t, pred, g, prediction_type=prediction_type, return_eps=False)
+        scale = 1 if image_scale is None else image_scale
+        if thr_out is not None:
+            thr_out.append(self._dynamic_thr(x0 * scale) if clip_fn == self.clip_sample else None)
+        return torch.clip(x0, -scale, scale) / scale if clip_fn is None else clip_fn(x0, scale)
+
+    def _hip_step_args(self, x_t, pred, g, g_last, prediction_type, clip_fn, image_scale, pred_uncond, guidance_scale,
+                       thr_out, ddim_eta=None):
+        """what both step kernels start with -> (fp32 x_t, fp32 pred, their keyword arguments: prediction type, image scale,
+        guidance, clip mode and per-sample threshold).  The dynamic thresholds cost one launch for the unclipped x0 and
+        the quantile."""
         scale = 1 if image_scale is None else image_scale
         x_t, pred = x_t.float(), pred.float()
-        kw = dict(prediction_type=pt, ddim_eta=ddim_eta, image_scale=scale, guidance_scale=guidance_scale,
-                  pred_uncond=None if pred_uncond is None else pred_uncond.float())
-        clip, thr = self._hip_clip(x_t, pred, g, g_last, use_clip_sample, scale, kw)
-        if thr_out is not None:
-            thr_out.append(thr)
-        noisy = need_noise and not (ddim_eta is not None and ddim_eta <= 0)
-        noise = input_noise
-        if noisy and noise is None and self.device_rng is None:
-            noise = torch.randn_like(x_t)   # torch's generator, like the reference (:340)
-        x0, x_last = ops.sampler_step(x_t, pred, g, g_last, need_noise=noisy, noise=noise, rng=self.device_rng, clip=clip,
-                                      thr=thr, **kw)
-        if noisy and noise is None:
-            self.device_rng.advance(x_t.numel())
-        eps = (x_last - _b(g_last).sqrt() * x0) / (1 - _b(g_last)).sqrt() if return_eps else None
-        return x0, x_last, eps
-
-    def _hip_clip(self, x_t, pred, g, g_last, use_clip_sample, scale, kw):
-        """-> (clip mode of the step kernel, per-sample threshold or None); the dynamic thresholds cost one launch for
-        the unclipped x0 and the quantile"""
-        fn = self._config.threshold_function if use_clip_sample else None
+        kw = dict(prediction_type=prediction_type or self._config.prediction_type, image_scale=scale,
+                  guidance_scale=guidance_scale, pred_uncond=None if pred_uncond is None else pred_uncond.float())
+        fn = self._config.threshold_function if clip_fn is not None else None
         thr, clip = None, "NONE"
         if fn in (ThresholdType.DYNAMIC, ThresholdType.DYNAMIC_IF):
-            x0s, _ = ops.sampler_step(x_t, pred, g, g_last, clip="X0_ONLY", **kw)
+            x0s, _ = ops.sampler_step(x_t, pred, g, g_last, ddim_eta=ddim_eta, clip="X0_ONLY", **kw)
             thr = self._dynamic_thr(x0s)
             clip = "DYNAMIC"
         elif fn == ThresholdType.CLIP:
             clip = "CLIP"
-        elif not use_clip_sample:
+        elif clip_fn is None:
             # clip_fn=None in the reference: clamp(x0, -s, s) / s == CLIP on x0 / s with unit scale ... only for s == 1
             if scale != 1:
                 raise NotImplementedError("clip_fn=None with image_scale != 1 on the HIP path")
             clip = "CLIP"
-        return clip, thr
+        if thr_out is not None:
+            thr_out.append(thr)
+        return x_t, pred, dict(kw, clip=clip, thr=thr)
 
     def _dynamic_thr(self, x0s):
         """the per-sample threshold [B] of the dynamic threshold functions for the unclipped x0 in image units (the clamped
@@ -491,7 +500,7 @@ class Sampler(nn.Module):
     # ---- one step of DPM-Solver++(2M) (not in the reference) ------------------------------------------
     def get_prediction_xt_last_2m(self, x_t, pred, g, g_last, g_prev=None, x0_prev=None, second_order=False,
                                   prediction_type=None, clip_fn=None, image_scale=None, pred_uncond=None,
-                                  guidance_scale=1, thr_out=None):
+                                  guidance_scale=1, thr_out=None, x0_out=None):
         """One update of DPM-Solver++(2M) (Lu et al. 2022, multistep, data prediction) -> (x0, x_last).
 
         Guidance combine, x0 and threshold as ``get_prediction_xt_last``; then, with alpha = sqrt(gamma), sigma =
@@ -503,25 +512,16 @@ class Sampler(nn.Module):
         ``second_order`` must be off when there is no history (first step) and when ``g_last == 1`` (last step: h is
         infinite; first order gives x_last = x0 there, as DDIM does).  First order is DDIM(eta = 0).  Gammas are
         per-sample tensors and need not lie on the schedule.  GPU tensors take ``ops.sampler_step_2m`` (where
-        ``second_order`` may also be a device float[1] gate), CPU tensors the torch ops below."""
-        if x_t.is_cuda and (clip_fn is None or clip_fn == self.clip_sample):
-            pt = prediction_type or self._config.prediction_type
-            scale = 1 if image_scale is None else image_scale
-            x_t, pred = x_t.float(), pred.float()
-            kw = dict(prediction_type=pt, image_scale=scale, guidance_scale=guidance_scale,
-                      pred_uncond=None if pred_uncond is None else pred_uncond.float())
-            clip, thr = self._hip_clip(x_t, pred, g, g_last, clip_fn is not None, scale, kw)
-            if thr_out is not None:
-                thr_out.append(thr)
+        ``second_order`` may also be a device float[1] gate, and ``x0_out`` the buffer x0 is written to: ``x0_prev`` itself
+        keeps the history in place), CPU tensors the torch ops below."""
+        if self._on_hip(x_t, clip_fn):
+            x_t, pred, kw = self._hip_step_args(x_t, pred, g, g_last, prediction_type, clip_fn, image_scale, pred_uncond,
+                                                guidance_scale, thr_out)
             return ops.sampler_step_2m(x_t, pred, g, g_last, g_prev=g_prev, x0_prev=x0_prev, second_order=second_order,
-                                       clip=clip, thr=thr, **kw)
-        if pred_uncond is not None:
-            pred = pred_uncond + guidance_scale * (pred - pred_uncond)
-        x0 = self.get_x0_eps_from_pred(x_t, pred, g, prediction_type=prediction_type, return_eps=False)
-        scale = 1 if image_scale is None else image_scale
-        if thr_out is not None:
-            thr_out.append(self._dynamic_thr(x0 * scale) if clip_fn == self.clip_sample else None)
-        x0 = torch.clip(x0, -scale, scale) / scale if clip_fn is None else clip_fn(x0, scale)
+                                       x0_out=x0_out, **kw)
+        if x0_out is not None:
+            raise ValueError("x0_out= belongs to the step kernel: GPU tensors only")
+        x0 = self._x0_thresholded(x_t, pred, g, prediction_type, clip_fn, image_scale, pred_uncond, guidance_scale, thr_out)
         D = x0
         if second_order:
             # 2 (lambda_a - lambda_b) = log(a (1 - b) / (b (1 - a))) = log1p((a - b) / (b (1 - a))): no cancellation
@@ -602,63 +602,112 @@ class Sampler(nn.Module):
 
     def forward_model(self, model, x_t, t, lm_outputs, lm_mask, micros={}, guidance_scale=1):
         """classifier-free guidance doubles the batch: [uncond | cond] (:435-459)."""
-        pc, pu, extras = self._forward_model_raw(model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
+        (pc,), (pu,), extras = self._forward_model_raw(model, [x_t], t, lm_outputs, lm_mask, micros, guidance_scale)
         return (pc if pu is None else pu + guidance_scale * (pc - pu)), extras
 
+    # ---- what differs between one scale and several: NestedSampler overrides these ----------------------------
     def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale):
-        """-> (conditional prediction, unconditional prediction or None, extras): the guidance combine itself is
-        folded into the step kernel"""
+        """``x_t``: the list of scales -> (conditional predictions, unconditional predictions or Nones, extras), one entry per
+        scale: the guidance combine itself is folded into the step kernel"""
         if guidance_scale != 1:
-            assert x_t.shape[0] * 2 == lm_outputs.shape[0]
-            pred, extras = model(torch.cat([x_t] * 2), torch.cat([t, t]), lm_outputs, lm_mask, micros=micros)
+            assert x_t[0].shape[0] * 2 == lm_outputs.shape[0]
+            pred, extras = model(torch.cat([x_t[0]] * 2), torch.cat([t, t]), lm_outputs, lm_mask, micros=micros)
             pu, pc = pred.chunk(2)
-            return pc, pu, extras.chunk(2)[1]
-        pred, extras = model(x_t, t, lm_outputs, lm_mask, micros)
-        return pred, None, extras
+            return [pc], [pu], extras.chunk(2)[1]
+        pred, extras = model(x_t[0], t, lm_outputs, lm_mask, micros)
+        return [pred], [None], extras
 
+    def _to_scales(self, model, x_t):
+        """what ``get_xt_minus_1`` is given -> the list of scales, hi -> lo"""
+        return [x_t]
+
+    def _from_scales(self, xs):
+        """a list of scales -> the form ``get_xt_minus_1`` takes and returns"""
+        return xs[0]
+
+    def _scale_info(self, model):
+        """-> (top side / side, image_scale) of every scale, hi -> lo: what the step kernel of that scale gets"""
+        return [1], [self._config.rescale_signal or 1]
+
+    def _gammas_of_scales(self, model, gamma):
+        """the schedule's gamma -> that of every scale, hi -> lo"""
+        return [gamma]
+
+    def _noisy_step(self, time_step, last):
+        """the last step adds no noise (:421); elementwise on arrays of times"""
+        return last != 0
+
+    def _scale_gammas(self, model, time, B):
+        """gamma of every scale (hi -> lo) at schedule time ``time``, [B, 1, 1, 1] each"""
+        return self._gammas_of_scales(model, self.read_gamma(torch.ones(B, dtype=torch.long, device=self.gammas.device) * time))
+
+    # ---- one iteration: denoiser, then the update of every scale -----------------------------------------------
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
                        second_order=False, guide=None):
-        """``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is the caller's
-        dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
+        """``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
+        top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
+        the caller's dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
         ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``guide``: a
-        ``LossGuide`` -- the model runs on a leaf x_t with grad enabled, the step itself unchanged under no_grad, and the
-        guide's correction is applied to its x_s."""
+        ``LossGuide`` -- the model runs on leaf x_t with grad enabled, the step itself unchanged under no_grad, and the
+        guide's correction is applied to its x_s; its loss sees the top scale."""
         _check_solver(solver, ddim_eta)
         _check_guide(guide)
-        ones = torch.ones(x_t.shape[0], dtype=torch.long, device=self.gammas.device)
+        x_t = self._to_scales(model, x_t)
+        ones = torch.ones(x_t[0].shape[0], dtype=torch.long, device=self.gammas.device)
         last = time_step - 1 if time_step_last is None else time_step_last
-        t, s = ones * time_step, ones * last
-        g, g_last = self.read_gamma(t), self.read_gamma(s)
-        if guide is not None:
-            x_in = x_t.detach().requires_grad_(True)
+        t = ones * time_step
+        g_t = self._gammas_of_scales(model, self.read_gamma(t))
+        g_s = self._gammas_of_scales(model, self.read_gamma(ones * last))
+        image_scales = self._scale_info(model)[1]
+        st = {} if solver_state is None else solver_state
+        listed = lambda v: v if v is None or isinstance(v, (list, tuple)) else [v]
+        step_kw = dict(guidance_scale=guidance_scale, ddim_eta=ddim_eta, solver=solver, second_order=second_order,
+                       g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
+                       need_noise=solver is None and bool(self._noisy_step(time_step, last)))
+        if guide is None:
+            pcs, pus, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
+            x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, **step_kw)
+        else:
+            x_in = [x.detach().requires_grad_(True) for x in x_t]
             with torch.enable_grad():
-                pc, pu, _ = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
-            thr = []
+                pcs, pus, _ = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
+            thr = []   # one entry per scale, hi -> lo
             with torch.no_grad():   # the step itself: unchanged, on detached tensors
-                x0, x_s = self._step(x_in.detach(), pc.detach(), None if pu is None else pu.detach(), g, g_last, last,
-                                     guidance_scale, ddim_eta, solver, solver_state, second_order, thr_out=thr)
-            x_s = self._guide_update(guide, [x_in], [(pc, pu)], x0, [x_s], g, self._config.rescale_signal, guidance_scale,
-                                     thr[0])[0]
-            return (x0, x_s, (g, g_last)) if return_details else x_s
-        pc, pu, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
-        x0, x_s = self._step(x_t, pc, pu, g, g_last, last, guidance_scale, ddim_eta, solver, solver_state, second_order)
-        return (x0, x_s, (g, g_last)) if return_details else x_s
-
-    def _step(self, x_t, pc, pu, g, g_last, last, guidance_scale, ddim_eta, solver, solver_state, second_order, thr_out=None):
-        """the update of ``get_xt_minus_1`` behind the denoiser call -> (x0, x_s)"""
+                x0, x_s = self._step_scales([x.detach() for x in x_in], [p.detach() for p in pcs],
+                                            [None if p is None else p.detach() for p in pus], g_t, g_s, image_scales,
+                                            thr_out=thr, **step_kw)
+            x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0], image_scales[0], guidance_scale,
+                                     thr[0])
         if solver is not None:
-            st = {} if solver_state is None else solver_state
-            x0, x_s = self.get_prediction_xt_last_2m(
-                x_t, pc, g, g_last, g_prev=st.get("g"), x0_prev=st.get("x0"), second_order=second_order,
-                prediction_type=self._config.prediction_type, clip_fn=self.clip_sample,
-                image_scale=self._config.rescale_signal, pred_uncond=pu, guidance_scale=guidance_scale, thr_out=thr_out)
-            st["x0"], st["g"] = x0, g
-            return x0, x_s
-        x0, x_s, _ = self.get_prediction_xt_last(
-            x_t, pc, g, g_last, prediction_type=self._config.prediction_type, need_noise=bool(last != 0),
-            ddim_eta=ddim_eta, clip_fn=self.clip_sample, image_scale=self._config.rescale_signal, return_eps=False,
-            pred_uncond=pu, guidance_scale=guidance_scale, thr_out=thr_out)
+            st["x0"], st["g"] = self._from_scales(x0), self._from_scales(g_t)
+        if not return_details:
+            return self._from_scales(x_s)
+        return self._from_scales(x0), self._from_scales(x_s), (g_t[-1], g_s[-1])
+
+    def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, need_noise=False, guidance_scale=1, ddim_eta=None,
+                     solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, rng=None, noise_gate=None,
+                     x0_out=None):
+        """The update of every scale behind the denoiser call -> (x0 list, x_s list).  All lists hi -> lo, one entry per
+        scale; ``g_prev`` / ``x0_prev``: the history of ``solver="dpmpp_2m"``, or None.  This is the one reverse step of the
+        eager samplers and of ``GraphedSampler``, whose captured graph passes ``rng``, ``noise_gate``, a device
+        ``second_order`` gate and ``x0_out`` through to the step kernels."""
+        n = len(x_t)
+        g_prev, x0_prev, x0_out = (v or [None] * n for v in (g_prev, x0_prev, x0_out))
+        kw = dict(prediction_type=self._config.prediction_type, clip_fn=self.clip_sample, guidance_scale=guidance_scale,
+                  thr_out=thr_out)
+        x0, x_s = [], []
+        for i in range(n):
+            if solver is not None:
+                a, b = self.get_prediction_xt_last_2m(
+                    x_t[i], pcs[i], g_t[i], g_s[i], g_prev=g_prev[i], x0_prev=x0_prev[i], second_order=second_order,
+                    image_scale=image_scales[i], pred_uncond=pus[i], x0_out=x0_out[i], **kw)
+            else:
+                a, b, _ = self.get_prediction_xt_last(
+                    x_t[i], pcs[i], g_t[i], g_s[i], need_noise=need_noise, ddim_eta=ddim_eta, return_eps=False,
+                    image_scale=image_scales[i], pred_uncond=pus[i], rng=rng, noise_gate=noise_gate, **kw)
+            x0.append(a)
+            x_s.append(b)
         return x0, x_s
 
     # ---- the sampling loop (:510-609) ----------------------------------------------------------
@@ -695,14 +744,6 @@ class Sampler(nn.Module):
                     return
             yield item
 
-    def _scale_info(self, model):
-        """-> (top side / side, image_scale) of every scale, hi -> lo: what the step kernel of that scale gets"""
-        return [1], [self._config.rescale_signal or 1]
-
-    def _scale_gammas(self, model, time, B):
-        """gamma of every scale (hi -> lo) at schedule time ``time``, [B, 1, 1, 1] each"""
-        return [self.read_gamma(torch.ones(B, dtype=torch.long, device=self.gammas.device) * time)]
-
     def _known_region(self, model, x_t, known_images, known_mask, known_seed, known_noise_fn):
         ratios, image_scales = self._scale_info(model)
         top = x_t[0] if isinstance(x_t, (list, tuple)) else x_t
@@ -730,7 +771,6 @@ class Sampler(nn.Module):
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
         _check_guide(guide)
-        extra_kw = {} if guide is None else {"guide": guide}
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -747,22 +787,21 @@ class Sampler(nn.Module):
         for i, ts in enumerate(steps[:-1]):
             # second order needs history (not on the first step of this trajectory, wherever it starts) and a finite
             # step in log-SNR (not on the last one: it goes to gamma = 1)
-            order = dict(solver=solver, solver_state=history, second_order=bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)) \
-                if solver is not None else {}
+            second = solver is not None and bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)
             reps = resample if i < len(steps) - 2 else 1
             for rep in range(reps):
                 x0, x_t, extra = self.get_xt_minus_1(
                     model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
-                    guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, **order, **extra_kw)
+                    guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
+                    solver_state=history, second_order=second, guide=guide)
                 if known is not None:
-                    is_list = isinstance(x_t, (list, tuple))
-                    xs = list(x_t) if is_list else [x_t]
+                    xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
                     g_s = self._scale_gammas(model, steps[i + 1], B)
                     xs = known.blend(xs, g_s)
                     if rep < reps - 1:
                         xs = known.jump(xs, self._scale_gammas(model, ts, B), g_s)
-                    x_t = xs if is_list else xs[0]
+                    x_t = self._from_scales(xs)
             if yield_output:
                 yield self._postprocess(x_t, x0, extra, **post_args)
             if return_sequence:
@@ -798,9 +837,20 @@ class NestedSampler(Sampler):
         scales = model.vision_model.nest_ratio + [1]
         return [scales[0] // s for s in scales], [1 if self._config.schedule_shifted else s for s in scales]
 
-    def _scale_gammas(self, model, time, B):
-        g = self.read_gamma(torch.ones(B, dtype=torch.long, device=self.gammas.device) * time)
-        return self.get_gammas(g, model.vision_model.nest_ratio + [1])
+    def _gammas_of_scales(self, model, gamma):
+        return self.get_gammas(gamma, model.vision_model.nest_ratio + [1])
+
+    def _noisy_step(self, time_step, last):
+        return time_step != 1   # (:700)
+
+    def _to_scales(self, model, x_t):
+        if not isinstance(x_t, torch.Tensor):
+            return x_t
+        # first step: draw independent noise at every lower resolution (:669-676)
+        return [x_t] + [torch.randn_like(F.avg_pool2d(x_t, r)) for r in self._scale_info(model)[0][1:]]
+
+    def _from_scales(self, xs):
+        return xs
 
     def get_xt(self, x0, eps, g, scales):
         return [Sampler.get_xt(self, self._signal(x, s), e, gi) for x, s, e, gi in zip(x0, scales, eps, g)]
@@ -810,80 +860,18 @@ class NestedSampler(Sampler):
                 for x, s, e, gi, gl in zip(x0, scales, eps, g, g_last)]
 
     def forward_model(self, model, x_t, t, lm_outputs, lm_mask, micros={}, guidance_scale=1):
-        pcs, pus = self._forward_model_raw(model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
+        pcs, pus, _ = self._forward_model_raw(model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
         return [pc if pu is None else pu + guidance_scale * (pc - pu) for pc, pu in zip(pcs, pus)]
 
     def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale):
-        """-> (conditional predictions, unconditional predictions or Nones), one entry per scale (:777-790)"""
+        """(:777-790); the nested model returns no extras"""
         if guidance_scale != 1:
             assert x_t[0].shape[0] * 2 == lm_outputs.shape[0]
             p_t = model([torch.cat([x] * 2) for x in x_t], torch.cat([t] * 2), lm_outputs, lm_mask, micros)
             halves = [p.chunk(2) for p in p_t]
-            return [h[1] for h in halves], [h[0] for h in halves]
+            return [h[1] for h in halves], [h[0] for h in halves], None
         p_t = model(x_t, t, lm_outputs, lm_mask, micros)
-        return list(p_t), [None] * len(p_t)
-
-    def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
-                       guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False, guide=None):
-        """``solver`` / ``solver_state`` / ``second_order`` / ``guide`` as ``Sampler.get_xt_minus_1``; the history holds one
-        x0 and one gamma per scale; the guide's loss sees the top scale, every scale's x_t is a leaf"""
-        _check_solver(solver, ddim_eta)
-        _check_guide(guide)
-        scales = model.vision_model.nest_ratio + [1]
-        if isinstance(x_t, torch.Tensor):  # first step: draw independent noise at every lower resolution (:669-676)
-            pyramid = [x_t]
-            for s in scales[1:]:
-                r = scales[0] // s
-                pyramid.append(torch.randn_like(F.avg_pool2d(x_t, r)))
-            x_t = pyramid
-        ones = torch.ones(x_t[0].shape[0], dtype=torch.long, device=self.gammas.device)
-        t = ones * time_step
-        s = t - 1 if time_step_last is None else ones * time_step_last
-        g_t = self.get_gammas(self.read_gamma(t), scales)
-        g_s = self.get_gammas(self.read_gamma(s), scales)
-        if guide is not None:
-            x_in = [x.detach().requires_grad_(True) for x in x_t]
-            with torch.enable_grad():
-                pcs, pus = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
-            thr = []   # one entry per scale, hi -> lo
-            with torch.no_grad():   # the step itself: unchanged, on detached tensors
-                x0, x_s = self._steps([x.detach() for x in x_in], [p.detach() for p in pcs],
-                                      [None if p is None else p.detach() for p in pus], g_t, g_s, scales, time_step,
-                                      guidance_scale, ddim_eta, solver, solver_state, second_order, thr_out=thr)
-            x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0],
-                                     1 if self._config.schedule_shifted else scales[0], guidance_scale, thr[0])
-            return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
-        pcs, pus = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
-        x0, x_s = self._steps(x_t, pcs, pus, g_t, g_s, scales, time_step, guidance_scale, ddim_eta, solver, solver_state,
-                              second_order)
-        return (x0, x_s, (g_t[-1], g_s[-1])) if return_details else x_s
-
-    def _steps(self, x_t, pcs, pus, g_t, g_s, scales, time_step, guidance_scale, ddim_eta, solver, solver_state, second_order,
-               thr_out=None):
-        """the per-scale updates of ``get_xt_minus_1`` behind the denoiser call -> (x0 list, x_s list)"""
-        x0, x_s = [], []
-        if solver is not None:
-            st = {} if solver_state is None else solver_state
-            x0_prev, g_prev = st.get("x0") or [None] * len(scales), st.get("g") or [None] * len(scales)
-            for x, pc, pu, g, gl, gp, xp, sc in zip(x_t, pcs, pus, g_t, g_s, g_prev, x0_prev, scales):
-                a, b = self.get_prediction_xt_last_2m(
-                    x, pc, g, gl, g_prev=gp, x0_prev=xp, second_order=second_order,
-                    prediction_type=self._config.prediction_type, clip_fn=self.clip_sample,
-                    image_scale=sc if not self._config.schedule_shifted else 1, pred_uncond=pu,
-                    guidance_scale=guidance_scale, thr_out=thr_out)
-                x0.append(a)
-                x_s.append(b)
-            st["x0"], st["g"] = x0, g_t
-            return x0, x_s
-        for x, pc, pu, g, gl, sc in zip(x_t, pcs, pus, g_t, g_s, scales):
-            a, b, _ = self.get_prediction_xt_last(
-                x, pc, g, gl, prediction_type=self._config.prediction_type, need_noise=bool(time_step != 1),
-                ddim_eta=ddim_eta, clip_fn=self.clip_sample, image_scale=sc if not self._config.schedule_shifted else 1,
-                return_eps=False, pred_uncond=pu, guidance_scale=guidance_scale, thr_out=thr_out)
-            x0.append(a)
-            x_s.append(b)
-        return x0, x_s
+        return list(p_t), [None] * len(p_t), None
 
     def _postprocess(self, x_t, x0=None, extra=None, yield_full=False, clip=False, output_inner=False, **unused):
         scales = [1 if self._config.schedule_shifted else x.size(-1) / x_t[-1].size(-1) for x in x_t]

@@ -340,7 +340,7 @@ def trainer_golden():
 class _PhiloxFeed:
     """stands in for torch.randn_like inside the REFERENCE sampler: hands out, draw by draw, exactly the numbers the HIP
     step kernel generates from DeviceRng(seed) (element i = lane i & 3 of Philox block offset + i // 4, stream 0; the
-    offset advances by ceil(n / 4) per draw: ml-mdm_amd/mdm_hip/samplers.py:_xt_last_hip) -- oracle/philox_ref.py"""
+    offset advances by ceil(n / 4) per draw: ml-mdm_amd/mdm_hip/samplers.py:get_prediction_xt_last) -- oracle/philox_ref.py"""
 
     def __init__(self, seed):
         import philox_ref as P

@@ -445,19 +445,24 @@ def test_graph_replay_matches_eager(name):
 
 
 @pytest.mark.parametrize("name", ["mini_unet", "mini_nested"])
-@pytest.mark.parametrize("mode", ["ddim", "ddpm_cfg", "ddpm_dynamic"])
+@pytest.mark.parametrize("mode", ["ddim", "ddpm_cfg", "ddpm_dynamic", "ddim_eta05", "ddpm_none"])
 def test_graphed_sampler_matches_eager_sampler(name, mode):
     """GraphedSampler (one hipGraph replay per WHOLE denoise iteration: schedule lookup, denoiser, fused update of every
     scale, RNG / step-counter advance) == the eager sampler on the same start noise; DDPM mode draws its noise inside
-    the step kernel from the same device generator state in both."""
+    the step kernel from the same device generator state in both.  ``ddim_eta05``: noisy DDIM (eta-scaled beta_tilde with
+    in-kernel noise and the noise gate); ``ddpm_none``: threshold NONE."""
     from mdm_hip.graph import GraphedSampler
 
     model, _, _ = PC.build_module(name)
-    pipe = _pipeline(name, model, threshold="DYNAMIC_IF" if mode == "ddpm_dynamic" else "CLIP").to(torch.device("cuda:0"))
+    threshold = {"ddpm_dynamic": "DYNAMIC_IF", "ddpm_none": "NONE"}.get(mode, "CLIP")
+    pipe = _pipeline(name, model, threshold=threshold).to(torch.device("cuda:0"))
     pipe.eval()
     inp = PC.inputs(name)
     cond, mask = inp["cond"].cuda(), inp["mask"].cuda()
-    kw = dict(ddim_eta=0) if mode == "ddim" else dict(ddim_eta=None, guidance_scale=2.5 if mode == "ddpm_cfg" else 1)
+    if mode in ("ddim", "ddim_eta05"):
+        kw = dict(ddim_eta=0 if mode == "ddim" else 0.5)
+    else:
+        kw = dict(ddim_eta=None, guidance_scale=2.5 if mode == "ddpm_cfg" else 1)
     if mode == "ddpm_cfg":
         cond, mask = torch.cat([torch.zeros_like(cond), cond]), torch.cat([mask, mask])
     smp = {"lm_outputs": cond, "lm_mask": mask}
