@@ -39,8 +39,7 @@
  *   3  round 3
  *   5  bf16 tensors: y_pre / aux of mdm_conv_fwd* hold one byte per element, the code of gelu'(pre) (round 6)
  *   6  mdm_conv_fwd_gn / mdm_conv_fwd_gn_ok removed (convolution + GroupNorm in one launch: step-neutral, never the default)
- * Pure additions do not bump it: 83 entry points at present (the last three: mdm_conv3x3_stem_dgrad, mdm_guide_seed,
- * mdm_guide_apply). */
+ * Pure additions do not bump it: 85 entry points at present (the last two: mdm_attn_cross_addv, mdm_pag_combine). */
 #define MDM_HIP_ABI_VERSION 6
 
 #ifdef __cplusplus
@@ -245,6 +244,19 @@ int mdm_attn_bwd(const void* qkv, const void* kvc, const float* mask, const void
                  const void* dout, const float* lse_self, const float* lse_cross, float* delta_self,
                  float* delta_cross, void* dqkv, void* dkvc, int B, int L, int S, int H, int d, int dtype,
                  void* stream);
+/* mdm_attn_cross_addv (a pure addition, no reference line: the reference has no perturbed-attention guidance) -- the
+ * attention of a PERTURBED row of perturbed-attention guidance (Ahn, Cho, Min, Jang, Kim, Kim, Park, Jin, Kim 2024,
+ * "Self-Rectifying Diffusion Sampling with Perturbed-Attention Guidance", ECCV 2024): the self-attention map is the
+ * identity, so softmax(q k^T) v is v itself; the text-cross term stays:
+ *   out = v + softmax_S(q k_c^T / sqrt(d), masked keys excluded) v_c                  [B, L, C], C = H * d
+ * Same tensors as mdm_attn_fwd (qkv [B, L, 3C], of which only q and v are read; kvc [B, S, 2C] or NULL; mask [B, S] of
+ * 0/1 floats or NULL) and the masking of its cross pass: a key with mask == 0 is excluded, a query whose keys are all
+ * masked gets a zero cross term; there, and with kvc == NULL, out holds v bit for bit.  Scores, softmax and accumulation
+ * in fp32.  d in {32, 64, 96, 128}, any S >= 1 (64-key tiles).  dtype: MDM_F32, MDM_BF16, or MDM_F32_SPLIT, which runs
+ * the exact-fp32 products here.  No workspace, no atomics, deterministic, forward only.  The pointers may be offsets of
+ * whole batch rows into larger tensors (16-byte alignment is all that is assumed). */
+int mdm_attn_cross_addv(const void* qkv, const void* kvc, const float* mask, void* out, int B, int L, int S, int H, int d,
+                        int dtype, void* stream);
 
 /* ---- streaming helpers ---------------------------------------------------------------------
  * layout conversion at the model boundary (the reference is NCHW fp32, unet.py:971-987),
@@ -377,6 +389,13 @@ int mdm_noise_images(const float* images, const float* eps, const float* gamma, 
 int mdm_guide_seed(const float* v, const float* x0, const float* a, const float* b, const float* thr, float image_scale,
                    int clip, float* direct, float* seed, int B, size_t chw, void* stream);
 int mdm_guide_apply(float* x, const float* direct, const float* jt, const float* zeta, int B, size_t chw, void* stream);
+/* mdm_pag_combine (a pure addition, no reference line): the combine of perturbed-attention guidance (Ahn et al. 2024; see
+ * mdm_attn_cross_addv) over n fp32 elements, with classifier-free guidance folded in:
+ *   out = (pred_uncond ? pred_uncond + guidance (pred - pred_uncond) : pred) + pag_scale (pred - pred_pert)
+ * pred_pert is the prediction of the perturbed rows.  out MAY alias pred (every thread reads its elements before it
+ * writes them), not the other two.  The step kernels then get pred = out, pred_uncond = NULL, guidance = 1. */
+int mdm_pag_combine(const float* pred, const float* pred_uncond, const float* pred_pert, float guidance, float pag_scale,
+                    float* out, size_t n, void* stream);
 int mdm_diffusion_loss_plan(int B, size_t chw, size_t* ws_bytes);
 int mdm_diffusion_loss_fwd(const float* x_t, const float* pred, const float* images, const float* eps,
                            const float* gamma, float inv_scale, float* loss, float* ws, int B, size_t chw,

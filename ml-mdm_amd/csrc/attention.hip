@@ -1432,3 +1432,194 @@ extern "C" int mdm_attn_bwd(const void* qkv, const void* kvc, const float* mask,
 #undef MDM_ATTN_BWD
   return -1;
 }
+
+// ---------------------------------------------------------------------------------------
+// perturbed-attention rows:  out = v + softmax_S(q k_c^T / sqrt(d), masked) v_c
+// ---------------------------------------------------------------------------------------
+// Perturbed-attention guidance (Ahn, Cho, Min, Jang, Kim, Kim, Park, Jin, Kim 2024, "Self-Rectifying Diffusion Sampling
+// with Perturbed-Attention Guidance") runs the denoiser once more with the self-attention MAP of a few layers replaced by
+// the identity: every query attends to itself only, softmax(q k^T) v becomes v, and the text-cross term stays.  So a
+// perturbed row needs no L x L pass and never reads k: the cross pass of attn_fwd_kernel (same operand plan, same
+// masking: a masked key is excluded, l == 0 gives a zero cross term) at 16 queries per wave, plus the row's own v.
+// Where the cross term is absent (no text keys, or every key of the row masked) out holds v bit for bit.
+// One 64-key tile at a time, staged synchronously: the text is one or two tiles and the perturbed rows of a sampling
+// batch are few (B = 1-4), so the grid (64 queries per block: 32-128 blocks at L = 64 / 256, H = 8) is what is short, as
+// for QT = 1 in attn_fwd_launch.  bf16: K and V natural, V^T fragments by the LDS transpose read; fp32: V staged
+// transposed, both products exact (v_mfma_f32_16x16x4_f32) -- also what DT_F32_SPLIT gets here.
+namespace mdm {
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
+  using G = AttnGeom<T, D>;
+  using F = Frag<T>;
+  constexpr int KSTEPS = G::KSTEPS, DS = G::DS, DT = G::DT;
+  constexpr bool BF = sizeof(T) == 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Ks = smem;
+  char* Vs = smem + G::NAT_BYTES;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int quad = lane >> 4, l16 = lane & 15;
+  const TrOff<D> troff(quad, l16);
+  // the query tiles of one (batch, head) share its text keys: kept on one XCD (see attn_fwd_kernel)
+  const int bx_ = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
+  const int by = bx_ / (int)gridDim.x, bx = bx_ - by * (int)gridDim.x;
+  const int b = by / p.H, h = by - b * p.H;
+  const int qi = bx * 64 + wave * 16 + l16;
+  const bool q_ok = qi < p.L;
+
+  f32x4 o[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -1e30f, l_run = 0.f;
+
+  if (p.kc) {   // block-uniform
+    const T* Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.q_bs + (size_t)h * D;
+    F qf[DS];
+#pragma unroll
+    for (int ks = 0; ks < DS; ++ks)
+      frag_from_global_x(qf[ks], Q + (size_t)(q_ok ? qi : 0) * p.q_rs + ks * 32 + quad * 8, q_ok);
+    const T* Kp = reinterpret_cast<const T*>(p.kc) + (size_t)b * p.c_bs + (size_t)h * D;
+    const T* Vp = reinterpret_cast<const T*>(p.vc) + (size_t)b * p.c_bs + (size_t)h * D;
+    const int rs = p.c_rs, nk = p.S;
+    const float* mrow = p.mask ? p.mask + (size_t)b * p.S : nullptr;
+    const float c2 = p.scale * 1.4426950408889634f;   // scores -> base-2 exponent
+
+    for (int k0 = 0; k0 < nk; k0 += 64) {
+      __syncthreads();   // every wave is done with the tile before
+      load_nat_tile<T, D>(Ks, Kp, rs, k0, nk, tid);
+      if constexpr (BF) load_nat_tile<T, D>(Vs, Vp, rs, k0, nk, tid);
+      else load_tr_tile<T, D>(Vs, Vp, rs, k0, nk, tid);
+      __syncthreads();
+
+      f32x4 s[4];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int row = perm_row(kt, l16);
+        s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < DS; ++ks) {
+          F kf;
+          load_frag_x(kf, Ks + (ks / KSTEPS) * (64 * 128), row, ks % KSTEPS, quad);
+          mma16(s[kt], kf, qf[ks]);
+        }
+      }
+      // base-2 softmax over the tile, running max / sum per query column (lane & 15); the lane holds key positions
+      // (kt>>1)*32 + quad*8 + (kt&1)*4 + i.  The exponent is formed as (s c2) - m with the product ROUNDED first, so that
+      // the largest key of a row gets 2^0 = 1 exactly: with a single live key the cross term is v_c itself, bit for bit.
+      {
+#pragma clang fp contract(off)
+        const bool full = (k0 + 64 <= nk) && !mrow;   // block-uniform
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            float t = s[kt][i] * c2;
+            if (!full) {
+              const int key = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4 + i;
+              bool ok = key < nk;
+              if (ok && mrow) ok = mrow[key] != 0.f;
+              t = ok ? t : -3.0e38f;
+            }
+            s[kt][i] = t;
+          }
+        float mx = -3.0e38f;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][i]);
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, fmaxf(mx, -1e30f));   // a fully masked tile leaves m_run alone
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        float ls = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float e = __builtin_amdgcn_exp2f(s[kt][i] - m_new);   // masked: -3e38 - m = -3e38 -> 0
+            s[kt][i] = e; ls += e;
+          }
+        l_run = l_run * alpha + ls;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt) o[dt] *= alpha;
+      }
+      F pf[2];
+      frag_from_acc_x(pf[0], s[0], s[1]);
+      frag_from_acc_x(pf[1], s[2], s[3]);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+          F vf;
+          if constexpr (BF) troff.read(vf, Vs, dt, hh);
+          else load_frag_x(vf, Vs + (hh / KSTEPS) * (D * 128), dt * 16 + l16, hh % KSTEPS, quad);
+          mma16(o[dt], vf, pf[hh]);
+        }
+    }
+  }
+
+  float l = l_run;
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  const bool live = l > 0.f;            // no text keys, or every key of this row masked: out = v, untouched
+  const float inv = live ? 1.f / l : 0.f;
+  if (!q_ok) return;
+  // the lane's own channels dt*16 + quad*4 + [0, 4) of v, all requested before the first store
+  using V4 = typename std::conditional<BF, bf16x4, f32x4>::type;
+  const T* Vq = reinterpret_cast<const T*>(p.v) + (size_t)b * p.k_bs + (size_t)qi * p.k_rs + (size_t)h * D + quad * 4;
+  T* O = reinterpret_cast<T*>(p.out) + (size_t)b * p.o_bs + (size_t)qi * p.o_rs + (size_t)h * D + quad * 4;
+  V4 vv[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) vv[dt] = *reinterpret_cast<const V4*>(Vq + dt * 16);
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    V4 r = vv[dt];
+    if (live) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[i] = from_f32<T>(to_f32((T)vv[dt][i]) + o[dt][i] * inv);
+    }
+    *reinterpret_cast<V4*>(O + dt * 16) = r;
+  }
+}
+
+}  // namespace mdm
+
+template <typename T, int D>
+static int attn_cross_addv_launch(const AttnArgs& a, hipStream_t st) {
+  using G = AttnGeom<T, D>;
+  constexpr int smem = sizeof(T) == 2 ? 2 * G::NAT_BYTES : G::NAT_BYTES + (G::NAT_BYTES > G::TR_BYTES ? G::NAT_BYTES : G::TR_BYTES);
+  ensure_dynamic_lds(attn_cross_addv_kernel<T, D>, smem);
+  dim3 grid((a.L + 63) / 64, a.B * a.H);   // 16 queries per wave
+  hipLaunchKernelGGL((attn_cross_addv_kernel<T, D>), grid, dim3(256), smem, st, a);
+  MDM_LAUNCH_STATUS();
+}
+
+// qkv [B, L, 3C] (only q and v are read), kvc [B, S, 2C] or null, mask [B, S] or null, out [B, L, C]; no workspace.
+extern "C" int mdm_attn_cross_addv(const void* qkv, const void* kvc, const float* mask, void* out, int B, int L, int S,
+                                   int H, int d, int dtype, void* stream) {
+  MDM_CHECK_ARG(qkv && out);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_F32_SPLIT);
+  if (dtype == DT_F32_SPLIT) dtype = DT_F32;   // the cross products are tiny: exact fp32 meets the split mode's gate
+  MDM_CHECK_ARG(B > 0 && L > 0 && H > 0);
+  MDM_CHECK_ARG(!kvc || S > 0);
+  MDM_CHECK_ARG(d == 32 || d == 64 || d == 96 || d == 128);
+  const int C = H * d;
+  const size_t es = dtype == DT_F32 ? 4 : 2;
+  AttnArgs a = {};
+  a.q = qkv; a.q_bs = (size_t)L * 3 * C; a.q_rs = 3 * C;
+  a.v = (const char*)qkv + (size_t)2 * C * es; a.k_bs = a.q_bs; a.k_rs = 3 * C;
+  if (kvc) { a.kc = kvc; a.vc = (const char*)kvc + (size_t)C * es; a.c_bs = (size_t)S * 2 * C; a.c_rs = 2 * C; }
+  a.mask = kvc ? mask : nullptr; a.out = out; a.o_bs = (size_t)L * C; a.o_rs = C;
+  a.B = B; a.H = H; a.L = L; a.S = S; a.scale = 1.0f / sqrtf((float)d);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define MDM_ATTN_CROSS_ADDV(DD) \
+  case DD: return dtype == DT_F32 ? attn_cross_addv_launch<float, DD>(a, st) : attn_cross_addv_launch<bf16, DD>(a, st);
+  switch (d) {
+    MDM_ATTN_CROSS_ADDV(32) MDM_ATTN_CROSS_ADDV(64) MDM_ATTN_CROSS_ADDV(96) MDM_ATTN_CROSS_ADDV(128)
+    default: MDM_CHECK_ARG(!"unsupported head dim");
+  }
+#undef MDM_ATTN_CROSS_ADDV
+  return -1;
+}

@@ -516,6 +516,31 @@ __global__ __launch_bounds__(256) void guide_apply_kernel(float* __restrict__ x,
   });
 }
 
+// Perturbed-attention guidance (Ahn et al. 2024), the combine in front of the step kernel:
+//   out = (pu ? pu + w (p - pu) : p) + s (p - pp)
+// 16-byte loads and stores over the first n / 4 groups, the last n % 4 elements one by one.  Every thread reads its
+// elements before it writes them, so out may alias pred.
+__device__ __forceinline__ float pag_combine_one(float p, float pu, bool has_u, float pp, float w, float s) {
+  const float base = has_u ? pu + w * (p - pu) : p;
+  return base + s * (p - pp);
+}
+__global__ __launch_bounds__(256) void pag_combine_kernel(const float* pred, const float* pred_uncond, const float* pred_pert,
+                                                          float w, float s, float* out, size_t n) {
+  const size_t n4 = n / 4;
+  const bool has_u = pred_uncond != nullptr;
+  for_each_vec4(n4, [&](size_t i) {
+    const f32x4 p = reinterpret_cast<const f32x4*>(pred)[i];
+    const f32x4 pp = reinterpret_cast<const f32x4*>(pred_pert)[i];
+    const f32x4 pu = has_u ? reinterpret_cast<const f32x4*>(pred_uncond)[i] : p;
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = pag_combine_one(p[e], pu[e], has_u, pp[e], w, s);
+    reinterpret_cast<f32x4*>(out)[i] = o;
+  });
+  const size_t tail = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tail < n) out[tail] = pag_combine_one(pred[tail], has_u ? pred_uncond[tail] : 0.f, has_u, pred_pert[tail], w, s);
+}
+
 }  // namespace mdm
 
 using namespace mdm;
@@ -629,6 +654,15 @@ extern "C" int mdm_guide_apply(float* x, const float* direct, const float* jt, c
   MDM_CHECK_ARG(x != direct && x != jt);
   hipLaunchKernelGGL(guide_apply_kernel, dim3(stream_blocks((size_t)B * (chw / 4))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), x, direct, jt, zeta, B, chw / 4);
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_pag_combine(const float* pred, const float* pred_uncond, const float* pred_pert, float guidance,
+                               float pag_scale, float* out, size_t n, void* stream) {
+  MDM_CHECK_ARG(pred && pred_pert && out && n > 0);
+  MDM_CHECK_ARG(out != pred_uncond && out != pred_pert);   // out may alias pred only
+  hipLaunchKernelGGL(pag_combine_kernel, dim3(stream_blocks((n + 3) / 4)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), pred, pred_uncond, pred_pert, guidance, pag_scale, out, n);
   MDM_LAUNCH_STATUS();
 }
 

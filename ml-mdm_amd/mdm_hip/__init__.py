@@ -15,6 +15,7 @@ Layout of the package
   lora.py         LoRA adapters on the attention projections: attach / merge / unmerge / detach
   fp8.py          opt-in MXFP8 (weights and activations) sampling path of the attention-layer 1x1 GEMMs and, with
                   conv_targets, of the ResNet convolutions (3x3 implicit GEMM): attach / detach
+  pag.py          perturbed-attention guidance: select / perturbed (the samplers' pag_scale / pag_layers)
 """
 import os as _os
 
@@ -40,8 +41,10 @@ from . import lora  # noqa: F401,E402
 from . import fp8  # noqa: F401,E402
 from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
 from .samplers import LossGuide  # noqa: F401,E402
+from . import pag  # noqa: F401,E402
 
 __all__ = [
+    "pag",
     "UNet",
     "UNetConfig",
     "ResNetConfig",

@@ -159,7 +159,7 @@ class Diffusion(nn.Module):
         stream 0 and advanced by ``numel`` per scale, hi -> lo; CPU tensors: the torch formula with ``noise_fn``
         (default ``torch.randn_like``).  ``graphed``: a ``GraphedSampler`` of this pipeline -- the remaining steps are
         replayed by it (``start_step``) instead of the eager sampler.  Other keywords go to ``sample`` (``ddim_eta``,
-        ``solver``, ``guidance_scale``, ``known_images`` ...)."""
+        ``solver``, ``guidance_scale``, ``known_images``, ``pag_scale`` / ``pag_layers`` ...)."""
         self.eval()
         smp, model = self.sampler, self.get_model()
         n = kwargs.get("num_inference_steps", 2000) if kwargs.get("resample_steps", False) else smp.n_steps

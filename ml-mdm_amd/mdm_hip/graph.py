@@ -16,12 +16,14 @@ loading a checkpoint (the packed kernel-layout weights baked into the graph woul
 merging or unmerging LoRA adapters (``mdm_hip.lora``) changes what a forward launches: both classes
 drop their graphs when ``ops.adapter_epoch()`` has moved, so the next call captures anew instead of replaying a stale one.
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
-from .samplers import _check_known, _check_solver
+from . import ops, pag
+from .samplers import _check_known, _check_pag, _check_solver, pag_rows
 
 
 class GraphedDenoiser(nn.Module):
@@ -55,7 +57,11 @@ class GraphedDenoiser(nn.Module):
         if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
             self._graphs.clear()
             self._adapter_epoch = ops.adapter_epoch()
-        key = self._sig(x_t, times, conditioning, cond_mask)
+        # (+ the perturbed rows of perturbed-attention guidance, layer by layer: they change what a forward launches)
+        layers = self.__dict__.get("_attn_layers")
+        if layers is None:
+            layers = self.__dict__["_attn_layers"] = pag.attention_layers(self.model)
+        key = self._sig(x_t, times, conditioning, cond_mask) + (tuple(m._pag_rows for m in layers),)
         ent = self._graphs.get(key)
         is_list = isinstance(x_t, (list, tuple))
         xs = list(x_t) if is_list else [x_t]
@@ -140,7 +146,8 @@ class GraphedSampler:
         return (mk(t, torch.long), mk(s, torch.long), mk(gate.astype("float32"), torch.float32), mk(p, torch.long),
                 mk(order, torch.float32), mk(jump, torch.float32)), t
 
-    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1):
+    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1,
+               pag_scale=0.0, pag_names=()):
         smp = self.sampler
         model = self.pipe.get_model()
         vm = model.vision_model
@@ -178,24 +185,33 @@ class GraphedSampler:
                 history = dict(second_order=tab_order.index_select(0, idx), g_prev=gammas(tab_p.index_select(0, idx)),
                                x0_prev=x0_prev, x0_out=x0_prev)
             times = (t - 1).expand(B)
-            if guidance != 1:
-                xin = [torch.cat([x, x]) for x in x_static]
-                tin = torch.cat([times, times])
+            # the model's batch: [uncond | cond] under classifier-free guidance, + [perturbed] under perturbed-attention
+            # guidance (the static conditioning and micros buffers hold that many rows)
+            reps = (2 if guidance != 1 else 1) + (1 if pag_scale != 0 else 0)
+            if reps > 1:
+                xin = [torch.cat([x] * reps) for x in x_static]
+                tin = torch.cat([times] * reps)
             else:
                 xin, tin = x_static, times
-            preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
+            with (pag.perturbed(vm, pag_names, rows=B) if pag_scale != 0 else contextlib.nullcontext()):
+                preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
             preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
                 preds = [torch.tanh(p / out_scale) * out_scale for p in preds]
-            pus = [None] * len(preds)
-            if guidance != 1:
-                pus, preds = zip(*(p.chunk(2) for p in preds))
+            pus, pps = [None] * len(preds), None
+            if reps > 1:
+                parts = [p.chunk(reps) for p in preds]
+                if pag_scale != 0:
+                    pps, parts = [p[-1] for p in parts], [p[:-1] for p in parts]
+                preds = [p[-1] for p in parts]
+                if guidance != 1:
+                    pus = [p[0] for p in parts]
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> torch.quantile, a
             # sort + lerp on the device, -> update kernel, all captured).  Every row draws and advances the generator in
             # the eager sampler's order (use_device_rng()); the device gate decides whether the noise is added
             _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, need_noise=True,
                                          guidance_scale=guidance, ddim_eta=ddim_eta, solver=solver, rng=rng, noise_gate=gate,
-                                         **history)
+                                         pps=pps, pag_scale=pag_scale, **history)
             for x, xl in zip(x_static, x_last):
                 x.copy_(xl)
             if known is not None:   # blends hi -> lo, then jumps hi -> lo: the draw order of KnownRegion
@@ -239,8 +255,11 @@ class GraphedSampler:
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None, guide=None):
-        """-> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
+               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid"):
+        """``pag_scale`` / ``pag_layers``: perturbed-attention guidance as ``Sampler._sample`` -- the static conditioning and
+        micros buffers carry the perturbed block's rows, the body runs the model under ``pag.perturbed`` and one combine
+        kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
+        -> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
         guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
         drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on).
         ``known_images`` / ``known_mask`` / ``resample`` / ``known_seed``: as ``Sampler._sample``; whether a scale has a
@@ -253,6 +272,7 @@ class GraphedSampler:
                                       "captured in a hipGraph; use the eager Sampler.sample(..., guide=...)")
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
+        _check_pag(pag_scale)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if start_step is not None and start_noise is None:
@@ -279,6 +299,10 @@ class GraphedSampler:
         # (reference diffusion.py:194-196); one value per row of the model's batch (2B under guidance)
         micros = {k: torch.as_tensor(v, device=xs[0].device).reshape(-1).float()
                   for k, v in self.pipe.get_micro_conditioning(sample).items()}
+        pag_names = ()
+        if pag_scale != 0:   # the perturbed block repeats the conditional rows of everything per-row
+            pag_names = pag.layer_names(model.vision_model, pag_layers)
+            cond, mask, micros = pag_rows(xs[0].shape[0], cond, mask, micros)
         key = (tuple(tuple(x.shape) for x in xs), tuple(cond.shape), int(num_inference_steps), ddim_eta, float(guidance_scale),
                torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
                ops.fp32_split_enabled(),   # a captured graph keeps the arithmetic it was captured with
@@ -287,8 +311,10 @@ class GraphedSampler:
         if known_images is not None:
             known = smp._known_region(model, xs, known_images, known_mask, known_seed, None)
             key = key + (tuple(k is not None for k in known.images), int(resample))
+        if pag_scale != 0:
+            key = key + (("pag", float(pag_scale), pag_names),)
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
-                                                   solver, known, int(resample))
+                                                   solver, known, int(resample), float(pag_scale), pag_names)
         for sx, x in zip(ent["x"], xs):
             sx.copy_(x)
         if known is not None:

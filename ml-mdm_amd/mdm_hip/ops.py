@@ -2096,6 +2096,62 @@ def attention(qkv, kvc, mask, heads):
     return AttentionFn.apply(qkv, kvc, mask, heads, torch.is_grad_enabled())
 
 
+def _attn_dims(qkv, kvc, heads):
+    B = qkv.shape[0]
+    C = qkv.shape[-1] // 3
+    L = qkv.numel() // max(B * 3 * C, 1)
+    S = kvc.shape[1] if kvc is not None else 0
+    return B, C, L, S, C // heads
+
+
+def _cross_addv_launch(qkv, kvc, m32, out, row0, rows, heads):
+    """mdm_attn_cross_addv on batch rows [row0, row0 + rows) of contiguous tensors, into the same rows of ``out``"""
+    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
+    _prof_wrap("attn_cross_addv_kernel<d=%d> L=%d" % (d, L), 4.0 * rows * heads * L * S * d, lambda: _lib.check(
+        _lib.lib().mdm_attn_cross_addv(off(qkv), off(kvc), off(m32), off(out), rows, L, S, heads, d, _dt_mm(qkv), _stream()),
+        "mdm_attn_cross_addv",
+    ), kind="attn")
+
+
+def attn_cross_addv(qkv, kvc, mask, heads):
+    """out = v + softmax(q k_c^T / sqrt(d) [masked]) v_c: the attention of perturbed-attention guidance's perturbed rows
+    (self-attention map = identity; include/mdm_hip.h mdm_attn_cross_addv).  Forward only."""
+    _require_gpu(qkv)
+    qkv, kvc = _c(qkv), _c(kvc)
+    m32 = _c(mask.float()) if (mask is not None and kvc is not None) else None
+    out = torch.empty(qkv.shape[:-1] + (qkv.shape[-1] // 3,), dtype=qkv.dtype, device=qkv.device)
+    _cross_addv_launch(qkv, kvc, m32, out, 0, qkv.shape[0], heads)
+    return out
+
+
+def attention_pag(qkv, kvc, mask, heads, rows):
+    """``attention`` on the leading N - rows batch rows, ``attn_cross_addv`` on the trailing ``rows`` (the perturbed block
+    of a perturbed-attention-guidance batch), into one output [N, L, C].  The leading part is the same entry with the same
+    B as ``attention`` on that slice alone.  Inference only: the perturbed kernel has no backward."""
+    _require_gpu(qkv)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, kvc)):
+        raise _lib.MdmHipError("attention_pag is inference only (mdm_attn_cross_addv has no backward): run it under "
+                               "torch.no_grad(), or without perturbed rows")
+    N = qkv.shape[0]
+    rows = int(rows)
+    if not 0 < rows <= N:
+        raise _lib.MdmHipError("attention_pag: rows = %d of a batch of %d" % (rows, N))
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach() if kvc is not None else None)
+    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    m32 = _c(mask.float()) if (mask is not None and kvc is not None) else None
+    out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
+    B = N - rows
+    if B > 0:
+        oc = torch.empty((B,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device) if kvc is not None else None
+        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * B * heads * L * (L + S) * d, lambda: _lib.check(
+            _lib.lib().mdm_attn_fwd(_p(qkv), _p(kvc), _p(m32), _p(out), _p(oc), None, None, B, L, S, heads, d, _dt_mm(qkv), _stream()),
+            "mdm_attn_fwd",
+        ), kind="attn")
+    _cross_addv_launch(qkv, kvc, m32, out, B, rows, heads)
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # streaming helpers
 # --------------------------------------------------------------------------------------
@@ -2545,6 +2601,21 @@ def guide_apply(x, zeta, direct=None, jt=None):
             raise _lib.MdmHipError("guide_apply: gradient %s vs x %s" % (tuple(t.shape), tuple(x.shape)))
     _lib.check(_lib.lib().mdm_guide_apply(_p(x), _p(d), _p(j), _p(_vec(zeta, B)), B, chw, _stream()), "mdm_guide_apply")
     return x
+
+
+def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1.0, pag_scale=0.0, out=None):
+    """Perturbed-attention guidance's combine (include/mdm_hip.h mdm_pag_combine) as ONE kernel:
+    (pred_uncond + w (pred - pred_uncond), or pred when ``pred_uncond`` is None) + s (pred - pred_pert).  ``out`` may be
+    ``pred`` itself.  -> out"""
+    pred, pp = _img(pred), _img(pred_pert)
+    pu = _img(pred_uncond) if pred_uncond is not None else None
+    for t in (pp, pu):
+        if t is not None and t.shape != pred.shape:
+            raise _lib.MdmHipError("pag_combine: prediction %s vs %s" % (tuple(t.shape), tuple(pred.shape)))
+    out = torch.empty_like(pred) if out is None else _inplace_img(out, pred, "pag_combine: out")
+    _lib.check(_lib.lib().mdm_pag_combine(_p(pred), _p(pu), _p(pp), float(guidance_scale), float(pag_scale), _p(out),
+                                          pred.numel(), _stream()), "mdm_pag_combine")
+    return out
 
 
 def noise_images(images, g, eps=None, rng=None, rng_stream=0, inv_scale=1.0):

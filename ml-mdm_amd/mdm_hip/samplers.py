@@ -23,7 +23,9 @@ same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.
 noised image (SDEdit, Meng et al. 2022).  ``sample(..., guide=LossGuide(fn))`` is the general case of which a known region
 is the special one: every step is pulled towards a small differentiable loss of the clean-image estimate (diffusion
 posterior sampling, Chung et al. 2023), through the denoiser's input gradient (``ops.stem_conv``) and the kernels
-``ops.guide_seed`` / ``ops.guide_apply``.
+``ops.guide_seed`` / ``ops.guide_apply``.  ``sample(..., pag_scale=s, pag_layers="mid")`` is perturbed-attention guidance (Ahn
+et al. 2024; ``mdm_hip/pag.py``): B more rows of the model batch with the self-attention map of the selected layers replaced by
+the identity, and one combine (``ops.pag_combine``; ``pag_combine`` on CPU tensors) in front of the unchanged step.
 """
 import math
 from dataclasses import dataclass
@@ -34,7 +36,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, pag
 
 
 class ScheduleType(Enum):
@@ -129,6 +131,32 @@ def _check_known(known_images, resample, solver):
         raise ValueError("resample=%d repeats the steps around a known region: it needs known_images" % resample)
     if resample > 1 and solver is not None:
         raise ValueError("resample=%d with solver=%r: the multistep history is void after a jump" % (resample, solver))
+
+
+def _check_pag(pag_scale, guide=None):
+    if pag_scale < 0:
+        raise ValueError("pag_scale must be >= 0 (got %r); 0 = no perturbed-attention guidance" % (pag_scale,))
+    if pag_scale != 0 and guide is not None:
+        raise NotImplementedError("guide= together with pag_scale != 0: the perturbed rows' attention kernel "
+                                  "(mdm_attn_cross_addv) has no backward, so the guide's input gradient cannot pass it")
+
+
+def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1, pag_scale=0.0):
+    """torch ops of ``ops.pag_combine`` (for CPU tensors): classifier-free guidance plus perturbed-attention guidance (Ahn
+    et al. 2024),  p_u + w (p_c - p_u) + s (p_c - p_hat);  p_c alone in front where ``pred_uncond`` is None"""
+    base = pred if pred_uncond is None else pred_uncond + guidance_scale * (pred - pred_uncond)
+    return base + pag_scale * (pred - pred_pert)
+
+
+def pag_rows(n, lm_outputs, lm_mask, micros):
+    """The conditioning of a perturbed-attention-guidance batch: the model's rows [uncond | cond] (or [cond]) followed by
+    the ``n`` perturbed rows, which carry the CONDITIONAL rows -- the last ``n`` -- of ``lm_outputs``, ``lm_mask`` and every
+    per-row tensor of ``micros`` once more.  -> (lm_outputs, lm_mask, micros)"""
+    rows = lm_outputs.shape[0]
+    ext = lambda v: torch.cat([v, v[-n:]])
+    per_row = lambda v: torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == rows
+    return (ext(lm_outputs), None if lm_mask is None else ext(lm_mask),
+            {k: ext(v) if per_row(v) else v for k, v in micros.items()})
 
 
 def known_blend(x, known, mask, g, inv_scale=1.0, noise=None):
@@ -606,9 +634,21 @@ class Sampler(nn.Module):
         return (pc if pu is None else pu + guidance_scale * (pc - pu)), extras
 
     # ---- what differs between one scale and several: NestedSampler overrides these ----------------------------
-    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale):
+    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, pag_scale=0.0,
+                           pag_layers="mid"):
         """``x_t``: the list of scales -> (conditional predictions, unconditional predictions or Nones, extras), one entry per
-        scale: the guidance combine itself is folded into the step kernel"""
+        scale: the guidance combine itself is folded into the step kernel.  ``pag_scale != 0``: the batch is
+        [uncond | cond | perturbed] ([cond | perturbed] without classifier-free guidance; ``pag_rows``), the model runs once
+        under ``pag.perturbed(..., rows=B)`` and a fourth item, the perturbed predictions, is returned."""
+        if pag_scale != 0:
+            B = x_t[0].shape[0]
+            reps = 3 if guidance_scale != 1 else 2
+            assert B * (reps - 1) == lm_outputs.shape[0]
+            cond, mask, mic = pag_rows(B, lm_outputs, lm_mask, micros)
+            with pag.perturbed(getattr(model, "vision_model", model), pag_layers, rows=B):
+                pred, extras = model(torch.cat([x_t[0]] * reps), torch.cat([t] * reps), cond, mask, micros=mic)
+            parts = pred.chunk(reps)
+            return [parts[-2]], [parts[0] if reps == 3 else None], extras.chunk(reps)[-2], [parts[-1]]
         if guidance_scale != 1:
             assert x_t[0].shape[0] * 2 == lm_outputs.shape[0]
             pred, extras = model(torch.cat([x_t[0]] * 2), torch.cat([t, t]), lm_outputs, lm_mask, micros=micros)
@@ -644,8 +684,9 @@ class Sampler(nn.Module):
     # ---- one iteration: denoiser, then the update of every scale -----------------------------------------------
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False, guide=None):
-        """``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
+                       second_order=False, guide=None, pag_scale=0.0, pag_layers="mid"):
+        """``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).
+        ``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
         top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
         the caller's dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
         ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``guide``: a
@@ -653,6 +694,7 @@ class Sampler(nn.Module):
         guide's correction is applied to its x_s; its loss sees the top scale."""
         _check_solver(solver, ddim_eta)
         _check_guide(guide)
+        _check_pag(pag_scale, guide)
         x_t = self._to_scales(model, x_t)
         ones = torch.ones(x_t[0].shape[0], dtype=torch.long, device=self.gammas.device)
         last = time_step - 1 if time_step_last is None else time_step_last
@@ -665,7 +707,11 @@ class Sampler(nn.Module):
         step_kw = dict(guidance_scale=guidance_scale, ddim_eta=ddim_eta, solver=solver, second_order=second_order,
                        g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
                        need_noise=solver is None and bool(self._noisy_step(time_step, last)))
-        if guide is None:
+        if pag_scale != 0:
+            pcs, pus, _, pps = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
+                                                       pag_scale, pag_layers)
+            x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, pps=pps, pag_scale=pag_scale, **step_kw)
+        elif guide is None:
             pcs, pus, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
             x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, **step_kw)
         else:
@@ -687,13 +733,19 @@ class Sampler(nn.Module):
 
     def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, need_noise=False, guidance_scale=1, ddim_eta=None,
                      solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, rng=None, noise_gate=None,
-                     x0_out=None):
+                     x0_out=None, pps=None, pag_scale=0.0):
         """The update of every scale behind the denoiser call -> (x0 list, x_s list).  All lists hi -> lo, one entry per
         scale; ``g_prev`` / ``x0_prev``: the history of ``solver="dpmpp_2m"``, or None.  This is the one reverse step of the
         eager samplers and of ``GraphedSampler``, whose captured graph passes ``rng``, ``noise_gate``, a device
-        ``second_order`` gate and ``x0_out`` through to the step kernels."""
+        ``second_order`` gate and ``x0_out`` through to the step kernels.  ``pps`` with ``pag_scale != 0``: the perturbed
+        predictions of perturbed-attention guidance -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU tensors:
+        ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1."""
         n = len(x_t)
         g_prev, x0_prev, x0_out = (v or [None] * n for v in (g_prev, x0_prev, x0_out))
+        if pps is not None and pag_scale != 0:
+            pcs = [ops.pag_combine(pc.float(), None if pu is None else pu.float(), pp.float(), guidance_scale, pag_scale)
+                   if pc.is_cuda else pag_combine(pc, pu, pp, guidance_scale, pag_scale) for pc, pu, pp in zip(pcs, pus, pps)]
+            pus, guidance_scale = [None] * n, 1
         kw = dict(prediction_type=self._config.prediction_type, clip_fn=self.clip_sample, guidance_scale=guidance_scale,
                   thr_out=thr_out)
         x0, x_s = [], []
@@ -723,6 +775,7 @@ class Sampler(nn.Module):
         _check_known(kwargs.get("known_images"), kwargs.get("resample", 1), kwargs.get("solver"))
         guide = kwargs.get("guide")
         _check_guide(guide)
+        _check_pag(kwargs.get("pag_scale", 0.0), guide)
         gen = self._sample(*args, **kwargs)
         if guide is None:
             return gen if kwargs.get("yield_output", False) else next(gen)
@@ -757,8 +810,14 @@ class Sampler(nn.Module):
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-                known_noise_fn=None, guide=None, **post_args):
-        """``guide``: a ``LossGuide`` -- loss-guided sampling; per step: the update, then the guide's correction, then the
+                known_noise_fn=None, guide=None, pag_scale=0.0, pag_layers="mid", **post_args):
+        """``pag_scale = s > 0``: perturbed-attention guidance (Ahn et al. 2024).  Every denoiser call carries B more rows,
+        [uncond | cond | perturbed] (``lm_outputs`` stays [uncond | cond], or [cond] at ``guidance_scale == 1``), in which the
+        ``SelfAttention`` layers that ``pag_layers`` selects (``pag.select``: "mid", "deepest", "all", names, a predicate)
+        attend to themselves only, and the step gets  p_u + w (p_c - p_u) + s (p_c - p_hat).  Only the prediction handed to
+        the update changes, so it composes with ``solver=``, ``known_images=`` and a late start; not with ``guide=``
+        (NotImplementedError).  ``pag_scale=0`` leaves every step as it is.
+        ``guide``: a ``LossGuide`` -- loss-guided sampling; per step: the update, then the guide's correction, then the
         known-region blend.  ``guide=None`` leaves every step as it is.
         ``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
         whichever update made it, every scale's x_s is replaced where the mask is 1 by the known image diffused to that
@@ -771,6 +830,7 @@ class Sampler(nn.Module):
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
         _check_guide(guide)
+        _check_pag(pag_scale, guide)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -793,7 +853,7 @@ class Sampler(nn.Module):
                 x0, x_t, extra = self.get_xt_minus_1(
                     model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
-                    solver_state=history, second_order=second, guide=guide)
+                    solver_state=history, second_order=second, guide=guide, pag_scale=pag_scale, pag_layers=pag_layers)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
@@ -863,8 +923,18 @@ class NestedSampler(Sampler):
         pcs, pus, _ = self._forward_model_raw(model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
         return [pc if pu is None else pu + guidance_scale * (pc - pu) for pc, pu in zip(pcs, pus)]
 
-    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale):
+    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, pag_scale=0.0,
+                           pag_layers="mid"):
         """(:777-790); the nested model returns no extras"""
+        if pag_scale != 0:   # as Sampler._forward_model_raw, every scale repeated
+            B = x_t[0].shape[0]
+            reps = 3 if guidance_scale != 1 else 2
+            assert B * (reps - 1) == lm_outputs.shape[0]
+            cond, mask, mic = pag_rows(B, lm_outputs, lm_mask, micros)
+            with pag.perturbed(getattr(model, "vision_model", model), pag_layers, rows=B):
+                p_t = model([torch.cat([x] * reps) for x in x_t], torch.cat([t] * reps), cond, mask, mic)
+            parts = [p.chunk(reps) for p in p_t]
+            return ([p[-2] for p in parts], [p[0] if reps == 3 else None for p in parts], None, [p[-1] for p in parts])
         if guidance_scale != 1:
             assert x_t[0].shape[0] * 2 == lm_outputs.shape[0]
             p_t = model([torch.cat([x] * 2) for x in x_t], torch.cat([t] * 2), lm_outputs, lm_mask, micros)

@@ -257,6 +257,9 @@ class SelfAttention(nn.Module):
     _lora = None
     # MXFP8 sampling path of the plain-GEMM projections (mdm_hip.fp8.attach): the same kind of handle.  None: as above.
     _fp8 = None
+    # perturbed-attention guidance (mdm_hip.pag.perturbed): the trailing _pag_rows batch rows get the identity self-attention
+    # map (ops.attention_pag).  0: as above.
+    _pag_rows = 0
 
     def forward(self, x, cond=None, cond_mask=None):
         N, H, W, C = x.shape
@@ -289,7 +292,11 @@ class SelfAttention(nn.Module):
                     kvc = kvc.reshape(*cn.shape[:-1], kvc.shape[-1])
                 else:
                     kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
-        a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
+        if self._pag_rows:
+            a = ops.attention_pag(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads,
+                                  self._pag_rows)
+        else:
+            a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
         a = a.reshape(N, H, W, C)
         if fp8 is not None and fp8.on("proj_out"):
             x = fp8.conv(a, self.proj_out, residual=x)
