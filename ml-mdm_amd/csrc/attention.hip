@@ -47,6 +47,9 @@ struct AttnArgs {
   int B, H, L, S;
   float scale;                                               // 1/sqrt(d)
   unsigned long long* dbg;                                   // development aid (mdm_dev_set_attn_dbg): phase time stamps, or null
+  // attn_cross_addv_kernel<.., BIAS = true> only (mdm_attn_cross_bias)
+  const float* bias; int bias_ld;                            // [B, L, bias_ld] fp32 logit bias of the text keys, all heads
+  const void* base; size_t base_bs; int base_rs;             // what the cross term is added to; row (b, i) as for q
 };
 
 template <typename T> __device__ __forceinline__ void frag_from_global(Frag<T>& f, const T* p, bool valid);
@@ -1448,7 +1451,16 @@ extern "C" int mdm_attn_bwd(const void* qkv, const void* kvc, const float* mask,
 // transposed, both products exact (v_mfma_f32_16x16x4_f32) -- also what DT_F32_SPLIT gets here.
 namespace mdm {
 
-template <typename T, int D>
+// BIAS = true (mdm_attn_cross_bias: regional prompts, token weights) is the same pass with an additive fp32 bias on the
+// text logits,  out = base + softmax_S(q k_c^T / sqrt(d) + bias[b, l, s]; live keys) v_c:  the exponent is
+// (s c2) + bias log2(e), then - m.  A key is live where key < S, mask != 0 and bias > -1e30 (so -inf excludes, exactly as
+// mask == 0 does: the same -3e38); liveness is per QUERY now, which the running max / sum per lane column already are.
+// A lane's four consecutive keys of one score tile are one 16-byte load of its query's bias row (bias_ld % 4 == 0),
+// issued before the tile's QK^T MFMAs so that it lands under them -- and, in the one in-order counter of gfx950, ahead
+// of the final stores.  The value is selected, never computed on, where the key is excluded or past S (the columns
+// [S, bias_ld) may hold anything, NaN included).  base replaces v as what the cross term is added to: any row-strided
+// view, out itself included (a lane reads its own elements before it stores them).
+template <typename T, int D, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
   using G = AttnGeom<T, D>;
   using F = Frag<T>;
@@ -1484,6 +1496,8 @@ __global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
     const int rs = p.c_rs, nk = p.S;
     const float* mrow = p.mask ? p.mask + (size_t)b * p.S : nullptr;
     const float c2 = p.scale * 1.4426950408889634f;   // scores -> base-2 exponent
+    [[maybe_unused]] const float* brow = nullptr;
+    if constexpr (BIAS) brow = p.bias + ((size_t)b * p.L + (q_ok ? qi : 0)) * p.bias_ld;
 
     for (int k0 = 0; k0 < nk; k0 += 64) {
       __syncthreads();   // every wave is done with the tile before
@@ -1491,6 +1505,19 @@ __global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
       if constexpr (BF) load_nat_tile<T, D>(Vs, Vp, rs, k0, nk, tid);
       else load_tr_tile<T, D>(Vs, Vp, rs, k0, nk, tid);
       __syncthreads();
+
+      // the lane's bias of this tile: keys key0 + [0, 4) per score tile; key0 % 4 == 0 and bias_ld % 4 == 0 >= S keep a
+      // load that starts below S inside the row
+      [[maybe_unused]] f32x4 bv[4];
+      if constexpr (BIAS) {
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+          const int key0 = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4;
+          const bool in = q_ok && key0 < nk;
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          bv[kt] = in ? *reinterpret_cast<const f32x4*>(brow + (in ? key0 : 0)) : z;
+        }
+      }
 
       f32x4 s[4];
 #pragma unroll
@@ -1515,7 +1542,13 @@ __global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             float t = s[kt][i] * c2;
-            if (!full) {
+            if constexpr (BIAS) {
+              const int key = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4 + i;
+              bool ok = key < nk && bv[kt][i] > -1e30f;   // false for NaN too
+              if (ok && mrow) ok = mrow[key] != 0.f;
+              const float bl = (ok ? bv[kt][i] : 0.f) * 1.4426950408889634f;
+              t = ok ? t + bl : -3.0e38f;
+            } else if (!full) {
               const int key = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4 + i;
               bool ok = key < nk;
               if (ok && mrow) ok = mrow[key] != 0.f;
@@ -1568,7 +1601,8 @@ __global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
   if (!q_ok) return;
   // the lane's own channels dt*16 + quad*4 + [0, 4) of v, all requested before the first store
   using V4 = typename std::conditional<BF, bf16x4, f32x4>::type;
-  const T* Vq = reinterpret_cast<const T*>(p.v) + (size_t)b * p.k_bs + (size_t)qi * p.k_rs + (size_t)h * D + quad * 4;
+  const T* Vq = BIAS ? reinterpret_cast<const T*>(p.base) + (size_t)b * p.base_bs + (size_t)qi * p.base_rs + (size_t)h * D + quad * 4
+                     : reinterpret_cast<const T*>(p.v) + (size_t)b * p.k_bs + (size_t)qi * p.k_rs + (size_t)h * D + quad * 4;
   T* O = reinterpret_cast<T*>(p.out) + (size_t)b * p.o_bs + (size_t)qi * p.o_rs + (size_t)h * D + quad * 4;
   V4 vv[DT];
 #pragma unroll
@@ -1586,13 +1620,13 @@ __global__ __launch_bounds__(256) void attn_cross_addv_kernel(AttnArgs p) {
 
 }  // namespace mdm
 
-template <typename T, int D>
+template <typename T, int D, bool BIAS = false>
 static int attn_cross_addv_launch(const AttnArgs& a, hipStream_t st) {
   using G = AttnGeom<T, D>;
   constexpr int smem = sizeof(T) == 2 ? 2 * G::NAT_BYTES : G::NAT_BYTES + (G::NAT_BYTES > G::TR_BYTES ? G::NAT_BYTES : G::TR_BYTES);
-  ensure_dynamic_lds(attn_cross_addv_kernel<T, D>, smem);
+  ensure_dynamic_lds(attn_cross_addv_kernel<T, D, BIAS>, smem);
   dim3 grid((a.L + 63) / 64, a.B * a.H);   // 16 queries per wave
-  hipLaunchKernelGGL((attn_cross_addv_kernel<T, D>), grid, dim3(256), smem, st, a);
+  hipLaunchKernelGGL((attn_cross_addv_kernel<T, D, BIAS>), grid, dim3(256), smem, st, a);
   MDM_LAUNCH_STATUS();
 }
 
@@ -1621,5 +1655,39 @@ extern "C" int mdm_attn_cross_addv(const void* qkv, const void* kvc, const float
     default: MDM_CHECK_ARG(!"unsupported head dim");
   }
 #undef MDM_ATTN_CROSS_ADDV
+  return -1;
+}
+
+// As mdm_attn_cross_addv, with an additive bias on the text logits and a free base operand (include/mdm_hip_ext.h):
+// bias [B, L, bias_ld] fp32, base [B, L, base_ld] and out [B, L, C] of the compute dtype; base may be out, or v of qkv.
+extern "C" int mdm_attn_cross_bias(const void* qkv, const void* kvc, const float* mask, const float* bias, int bias_ld,
+                                   const void* base, int base_ld, void* out, int B, int L, int S, int H, int d, int dtype,
+                                   void* stream) {
+  MDM_CHECK_ARG(qkv && kvc && bias && base && out);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_F32_SPLIT);
+  if (dtype == DT_F32_SPLIT) dtype = DT_F32;   // exact fp32 products, as mdm_attn_cross_addv
+  MDM_CHECK_ARG(B > 0 && L > 0 && H > 0 && S > 0);
+  MDM_CHECK_ARG(d == 32 || d == 64 || d == 96 || d == 128);
+  MDM_CHECK_ARG(bias_ld >= S && bias_ld % 4 == 0);   // a lane's four keys are one aligned 16-byte load inside the row
+  const int C = H * d;
+  MDM_CHECK_ARG(base_ld >= C && base_ld % 4 == 0);
+  const size_t es = dtype == DT_F32 ? 4 : 2;
+  MDM_CHECK_ARG((uintptr_t)bias % 16 == 0 && (uintptr_t)base % (4 * es) == 0);   // the lanes' vector loads
+  AttnArgs a = {};
+  a.q = qkv; a.q_bs = (size_t)L * 3 * C; a.q_rs = 3 * C;
+  a.v = (const char*)qkv + (size_t)2 * C * es; a.k_bs = a.q_bs; a.k_rs = 3 * C;
+  a.kc = kvc; a.vc = (const char*)kvc + (size_t)C * es; a.c_bs = (size_t)S * 2 * C; a.c_rs = 2 * C;
+  a.mask = mask; a.out = out; a.o_bs = (size_t)L * C; a.o_rs = C;
+  a.bias = bias; a.bias_ld = bias_ld;
+  a.base = base; a.base_bs = (size_t)L * base_ld; a.base_rs = base_ld;
+  a.B = B; a.H = H; a.L = L; a.S = S; a.scale = 1.0f / sqrtf((float)d);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define MDM_ATTN_CROSS_BIAS(DD) \
+  case DD: return dtype == DT_F32 ? attn_cross_addv_launch<float, DD, true>(a, st) : attn_cross_addv_launch<bf16, DD, true>(a, st);
+  switch (d) {
+    MDM_ATTN_CROSS_BIAS(32) MDM_ATTN_CROSS_BIAS(64) MDM_ATTN_CROSS_BIAS(96) MDM_ATTN_CROSS_BIAS(128)
+    default: MDM_CHECK_ARG(!"unsupported head dim");
+  }
+#undef MDM_ATTN_CROSS_BIAS
   return -1;
 }

@@ -16,6 +16,8 @@ Layout of the package
   fp8.py          opt-in MXFP8 (weights and activations) sampling path of the attention-layer 1x1 GEMMs and, with
                   conv_targets, of the ResNet convolutions (3x3 implicit GEMM): attach / detach
   pag.py          perturbed-attention guidance: select / perturbed (the samplers' pag_scale / pag_layers)
+  regions.py      regional prompts and token weights, a bias on the text cross-attention logits: RegionPrompts / concat /
+                  applied (the samplers' regions / region_layers)
 """
 import os as _os
 
@@ -42,9 +44,13 @@ from . import fp8  # noqa: F401,E402
 from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
 from .samplers import LossGuide  # noqa: F401,E402
 from . import pag  # noqa: F401,E402
+from . import regions  # noqa: F401,E402
+from .regions import RegionPrompts  # noqa: F401,E402
 
 __all__ = [
     "pag",
+    "regions",
+    "RegionPrompts",
     "UNet",
     "UNetConfig",
     "ResNetConfig",

@@ -15,6 +15,7 @@ _ROOT = os.path.dirname(os.path.dirname(_HERE))
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 HEADER = os.path.join(_ROOT, "include", "mdm_hip.h")            # the drop-in boundary
 DEV_HEADER = os.path.join(_ROOT, "include", "mdm_hip_dev.h")    # profiling aids (bench.py, tools/)
+EXT_HEADER = os.path.join(_ROOT, "include", "mdm_hip_ext.h")    # capabilities the reference does not have
 # MDM_HIP_LIB: load another build of the library (development: in-call A/B of two kernel versions on one GPU box)
 LIB_PATH = os.environ.get("MDM_HIP_LIB") or os.path.join(_HERE, "libmdm_hip.so")
 SOURCES = ["gemm_conv.hip", "norm.hip", "attention.hip", "elementwise.hip", "optim.hip", "diffusion_ops.hip",
@@ -34,7 +35,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     """Compile every HIP source for gfx950 into ml-mdm_amd/mdm_hip/libmdm_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     hdrs = [os.path.join(CSRC, h) for h in ("common.hpp", "conv_args.hpp", "attn32.hpp")]
-    deps = srcs + [HEADER] + hdrs
+    deps = srcs + [HEADER, EXT_HEADER] + hdrs
     if not force and os.path.exists(LIB_PATH):
         if all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
             # the note is renewed only when something it records can have changed since it was written (a commit: .git/HEAD
@@ -177,7 +178,7 @@ def lib():
                 "-- there is no CPU fallback for the product path." % LIB_PATH
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, restype, argtypes, _ in header_prototypes() + header_prototypes(DEV_HEADER):
+        for name, restype, argtypes, _ in header_prototypes() + header_prototypes(DEV_HEADER) + header_prototypes(EXT_HEADER):
             fn = getattr(handle, name)  # AttributeError if the header and the library drift
             fn.restype = restype
             fn.argtypes = argtypes

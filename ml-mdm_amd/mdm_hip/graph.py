@@ -22,11 +22,16 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops, pag
-from .samplers import _check_known, _check_pag, _check_solver, pag_rows
+from . import ops, pag, regions as _regions
+from .samplers import _check_known, _check_pag, _check_regions, _check_solver, pag_rows
 
 
 class GraphedDenoiser(nn.Module):
+    """The model forward as one hipGraph per input signature (and per perturbed-row pattern of perturbed-attention
+    guidance).  While any attention layer carries a cross-attention bias handle (``regions.applied``: regional prompts,
+    token weights) the model is called EAGERLY: the bias tensors belong to the caller, who may rewrite or replace them
+    between calls, so no graph is captured with them -- and a graph captured without the bias is never replayed."""
+
     def __init__(self, model: nn.Module, warmup: int = 2):
         super().__init__()
         self.model = model
@@ -54,13 +59,15 @@ class GraphedDenoiser(nn.Module):
     def forward(self, x_t, times, conditioning=None, cond_mask=None, micros={}):
         if torch.is_grad_enabled() or self.model.training or micros:
             return self.model(x_t, times, conditioning, cond_mask, micros)
+        layers = self.__dict__.get("_attn_layers")
+        if layers is None:
+            layers = self.__dict__["_attn_layers"] = pag.attention_layers(self.model)
+        if _regions.any_applied(layers):
+            return self.model(x_t, times, conditioning, cond_mask, micros)
         if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
             self._graphs.clear()
             self._adapter_epoch = ops.adapter_epoch()
         # (+ the perturbed rows of perturbed-attention guidance, layer by layer: they change what a forward launches)
-        layers = self.__dict__.get("_attn_layers")
-        if layers is None:
-            layers = self.__dict__["_attn_layers"] = pag.attention_layers(self.model)
         key = self._sig(x_t, times, conditioning, cond_mask) + (tuple(m._pag_rows for m in layers),)
         ent = self._graphs.get(key)
         is_list = isinstance(x_t, (list, tuple))
@@ -147,7 +154,7 @@ class GraphedSampler:
                 mk(order, torch.float32), mk(jump, torch.float32)), t
 
     def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1,
-               pag_scale=0.0, pag_names=()):
+               pag_scale=0.0, pag_names=(), bias_source=None, region_names=()):
         smp = self.sampler
         model = self.pipe.get_model()
         vm = model.vision_model
@@ -173,6 +180,9 @@ class GraphedSampler:
         ce, cs, cm = vm.forward_conditioning(cond, mask)
         ce_s, cs_s, cm_s = ce.clone(), cs.clone(), (cm.clone() if cm is not None else None)
         out_scale = model._output_scale
+        # regional prompts: static bias buffers, one per attention resolution -- the warm-up passes discover the resolutions
+        # (each buffer starts as a copy of the caller's bias); every sample() call fills them anew
+        bias_s = _regions.StaticBias(bias_source) if bias_source is not None else None
 
         def body():
             t = tab_t.index_select(0, idx)
@@ -193,7 +203,8 @@ class GraphedSampler:
                 tin = torch.cat([times] * reps)
             else:
                 xin, tin = x_static, times
-            with (pag.perturbed(vm, pag_names, rows=B) if pag_scale != 0 else contextlib.nullcontext()):
+            with (pag.perturbed(vm, pag_names, rows=B) if pag_scale != 0 else contextlib.nullcontext()), \
+                    (_regions.applied(vm, bias_s, region_names) if bias_s is not None else contextlib.nullcontext()):
                 preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
             preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
@@ -240,6 +251,8 @@ class GraphedSampler:
             if kn_rng is not None:
                 kn_rng.state.zero_()
         torch.cuda.current_stream().wait_stream(side)
+        if bias_s is not None:
+            bias_s.freeze()   # a resolution first met during the capture would be an allocation inside the graph: an error
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             body()
@@ -247,7 +260,7 @@ class GraphedSampler:
         # function; once freed, a later allocation reuses their memory and the replayed index_select reads garbage
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
-                   t_host=t_host, order=tab_order, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
+                   t_host=t_host, order=tab_order, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
                    keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev))
         self._graphs[key] = ent
         return ent
@@ -255,8 +268,13 @@ class GraphedSampler:
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid"):
-        """``pag_scale`` / ``pag_layers``: perturbed-attention guidance as ``Sampler._sample`` -- the static conditioning and
+               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all"):
+        """``regions`` / ``region_layers``: regional prompts and token weights as ``Sampler._sample``.  Each graph entry owns
+        static bias buffers, one per attention resolution, filled by ``copy_`` from ``regions`` on every call (the pattern
+        of the known images), and its body runs the model under ``regions.applied`` with a handle over those buffers.  The
+        graph key holds ("regions", S, ld, the resolved layer names): other masks or weights replay the same graph, another
+        S or layer set captures anew.
+        ``pag_scale`` / ``pag_layers``: perturbed-attention guidance as ``Sampler._sample`` -- the static conditioning and
         micros buffers carry the perturbed block's rows, the body runs the model under ``pag.perturbed`` and one combine
         kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
         -> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
@@ -273,6 +291,7 @@ class GraphedSampler:
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
         _check_pag(pag_scale)
+        _check_regions(regions)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if start_step is not None and start_noise is None:
@@ -313,8 +332,19 @@ class GraphedSampler:
             key = key + (tuple(k is not None for k in known.images), int(resample))
         if pag_scale != 0:
             key = key + (("pag", float(pag_scale), pag_names),)
+        bias_source, region_names = None, ()
+        if regions is not None:
+            if regions.rows != xs[0].shape[0] or regions.S != cond.shape[1]:
+                raise ValueError("regions over %d rows of %d tokens for a batch of %d images with %d tokens"
+                                 % (regions.rows, regions.S, xs[0].shape[0], cond.shape[1]))
+            region_names = _regions.layer_names(model.vision_model, region_layers)
+            bias_source = regions.rows_for(guidance_scale != 1, pag_scale != 0, xs[0].device)
+            key = key + (("regions", regions.S, regions.ld, region_names),)
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
-                                                   solver, known, int(resample), float(pag_scale), pag_names)
+                                                   solver, known, int(resample), float(pag_scale), pag_names, bias_source,
+                                                   region_names)
+        if bias_source is not None:
+            ent["bias"].fill(bias_source)
         for sx, x in zip(ent["x"], xs):
             sx.copy_(x)
         if known is not None:

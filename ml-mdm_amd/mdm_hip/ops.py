@@ -2152,6 +2152,81 @@ def attention_pag(qkv, kvc, mask, heads, rows):
     return out
 
 
+def _cross_bias_check(what, qkv, kvc, bias):
+    """the operands of mdm_attn_cross_bias -> bias as the kernel reads it (fp32, contiguous [N, L, ld])"""
+    _require_gpu(qkv)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, kvc, bias)):
+        raise _lib.MdmHipError("%s is inference only (mdm_attn_cross_bias has no backward): run it under torch.no_grad()"
+                               % what)
+    if kvc is None:
+        raise _lib.MdmHipError("%s: no text keys (kvc is None) -- there are no logits to bias" % what)
+    N, L, S = qkv.shape[0], qkv.numel() // max(qkv.shape[0] * qkv.shape[-1], 1), kvc.shape[1]
+    if bias.dim() != 3 or bias.shape[0] != N or bias.shape[1] != L or bias.shape[2] < S or bias.shape[2] % 4:
+        raise _lib.MdmHipError("%s: bias %s for N = %d, L = %d, S = %d (wanted [N, L, ld], ld >= S, ld %% 4 == 0)"
+                               % (what, tuple(bias.shape), N, L, S))
+    if bias.dtype != torch.float32 or bias.device != qkv.device:
+        raise _lib.MdmHipError("%s: the bias is fp32 on the tensors' device (got %s on %s)" % (what, bias.dtype, bias.device))
+    return _c(bias.detach())
+
+
+def _cross_bias_launch(qkv, kvc, m32, bias, base, out, row0, rows, heads):
+    """mdm_attn_cross_bias on batch rows [row0, row0 + rows) of contiguous tensors, into the same rows of ``out``.
+    ``base``: None = v of qkv, else a contiguous [N, L, C] tensor (``out`` itself: in place)."""
+    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
+    bp, bld = (off(qkv) + 2 * C * qkv.element_size(), 3 * C) if base is None else (off(base), C)
+    _prof_wrap("attn_cross_addv_kernel<d=%d, bias> L=%d" % (d, L), 4.0 * rows * heads * L * S * d, lambda: _lib.check(
+        _lib.lib().mdm_attn_cross_bias(off(qkv), off(kvc), off(m32), off(bias), bias.shape[-1], bp, bld, off(out), rows, L, S,
+                                       heads, d, _dt_mm(qkv), _stream()),
+        "mdm_attn_cross_bias",
+    ), kind="attn")
+
+
+def attn_cross_bias(qkv, kvc, mask, bias, heads, base=None):
+    """out = base + softmax(q k_c^T / sqrt(d) + bias [masked; bias <= -1e30 excludes]) v_c  (include/mdm_hip_ext.h
+    mdm_attn_cross_bias).  ``bias``: fp32 [N, L, ld], ld >= S, ld % 4 == 0.  ``base=None``: v of ``qkv``, into a new tensor;
+    a contiguous [N, L, C] tensor of qkv's dtype: the term is added onto it IN PLACE and it is returned.  Forward only."""
+    bias = _cross_bias_check("attn_cross_bias", qkv, kvc, bias)
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
+    m32 = _c(mask.float()) if mask is not None else None
+    shape = qkv.shape[:-1] + (qkv.shape[-1] // 3,)
+    if base is None:
+        out = torch.empty(shape, dtype=qkv.dtype, device=qkv.device)
+    else:
+        if tuple(base.shape) != tuple(shape) or base.dtype != qkv.dtype or not base.is_contiguous() or base.device != qkv.device:
+            raise _lib.MdmHipError("attn_cross_bias: base %s %s (wanted a contiguous %s %s)"
+                                   % (tuple(base.shape), base.dtype, tuple(shape), qkv.dtype))
+        out = base
+    _cross_bias_launch(qkv, kvc, m32, bias, base, out, 0, qkv.shape[0], heads)
+    return out
+
+
+def attention_biased(qkv, kvc, mask, bias, heads, pag_rows=0):
+    """``attention`` with ``bias`` [N, L, ld] added to the text logits (regional prompts, token weights): on the leading
+    N - pag_rows batch rows ``mdm_attn_fwd`` without text keys writes the self part and ``mdm_attn_cross_bias`` adds the
+    biased cross part in place; the trailing ``pag_rows`` (the perturbed block of perturbed-attention guidance) are the same
+    kernel on base = v.  Inference only: the kernel has no backward."""
+    bias = _cross_bias_check("attention_biased", qkv, kvc, bias)
+    N = qkv.shape[0]
+    rows = int(pag_rows)
+    if not 0 <= rows <= N:
+        raise _lib.MdmHipError("attention_biased: pag_rows = %d of a batch of %d" % (rows, N))
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
+    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    m32 = _c(mask.float()) if mask is not None else None
+    out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
+    B = N - rows
+    if B > 0:
+        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * B * heads * L * L * d, lambda: _lib.check(
+            _lib.lib().mdm_attn_fwd(_p(qkv), None, None, _p(out), None, None, None, B, L, 0, heads, d, _dt_mm(qkv), _stream()),
+            "mdm_attn_fwd",
+        ), kind="attn")
+        _cross_bias_launch(qkv, kvc, m32, bias, out, out, 0, B, heads)
+    if rows > 0:
+        _cross_bias_launch(qkv, kvc, m32, bias, None, out, B, rows, heads)
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # streaming helpers
 # --------------------------------------------------------------------------------------

@@ -26,7 +26,13 @@ posterior sampling, Chung et al. 2023), through the denoiser's input gradient (`
 ``ops.guide_seed`` / ``ops.guide_apply``.  ``sample(..., pag_scale=s, pag_layers="mid")`` is perturbed-attention guidance (Ahn
 et al. 2024; ``mdm_hip/pag.py``): B more rows of the model batch with the self-attention map of the selected layers replaced by
 the identity, and one combine (``ops.pag_combine``; ``pag_combine`` on CPU tensors) in front of the unchanged step.
+``sample(..., regions=rp, region_layers="all")`` is regional prompting and token weighting (``mdm_hip/regions.py``): the
+``RegionPrompts`` handle ``rp`` gives an additive bias on the text logits of the selected attention layers, per query position
+and per token (``ops.attention_biased``).  The sampler extends its rows for the batch it builds -- 0 in the unconditional rows,
+the conditional rows' bias once more in the perturbed block -- and switches it on (``regions.applied``) around the denoiser call
+of each step alone; steps, solvers, known regions and the other guidances are untouched.
 """
+import contextlib
 import math
 from dataclasses import dataclass
 from enum import Enum
@@ -37,6 +43,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, pag
+from . import regions as _regions
 
 
 class ScheduleType(Enum):
@@ -139,6 +146,14 @@ def _check_pag(pag_scale, guide=None):
     if pag_scale != 0 and guide is not None:
         raise NotImplementedError("guide= together with pag_scale != 0: the perturbed rows' attention kernel "
                                   "(mdm_attn_cross_addv) has no backward, so the guide's input gradient cannot pass it")
+
+
+def _check_regions(regions, guide=None):
+    if regions is not None and guide is not None:
+        raise NotImplementedError("guide= together with regions=: the biased cross-attention kernel (mdm_attn_cross_bias) "
+                                  "has no backward, so the guide's input gradient cannot pass it")
+    if regions is not None and not callable(getattr(regions, "rows_for", None)):
+        raise ValueError("regions = %r (wanted a mdm_hip.RegionPrompts)" % (regions,))
 
 
 def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1, pag_scale=0.0):
@@ -684,8 +699,9 @@ class Sampler(nn.Module):
     # ---- one iteration: denoiser, then the update of every scale -----------------------------------------------
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False, guide=None, pag_scale=0.0, pag_layers="mid"):
-        """``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).
+                       second_order=False, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all"):
+        """``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).  ``regions`` / ``region_layers``:
+        regional prompts and token weights (see ``_sample``): switched on around the denoiser call below, nowhere else.
         ``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
         top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
         the caller's dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
@@ -695,7 +711,14 @@ class Sampler(nn.Module):
         _check_solver(solver, ddim_eta)
         _check_guide(guide)
         _check_pag(pag_scale, guide)
+        _check_regions(regions, guide)
         x_t = self._to_scales(model, x_t)
+        biased = contextlib.nullcontext()
+        if regions is not None:
+            if regions.rows != x_t[0].shape[0]:
+                raise ValueError("regions over %d rows for a batch of %d images" % (regions.rows, x_t[0].shape[0]))
+            biased = _regions.applied(getattr(model, "vision_model", model),
+                                      regions.rows_for(guidance_scale != 1, pag_scale != 0, x_t[0].device), region_layers)
         ones = torch.ones(x_t[0].shape[0], dtype=torch.long, device=self.gammas.device)
         last = time_step - 1 if time_step_last is None else time_step_last
         t = ones * time_step
@@ -708,11 +731,13 @@ class Sampler(nn.Module):
                        g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
                        need_noise=solver is None and bool(self._noisy_step(time_step, last)))
         if pag_scale != 0:
-            pcs, pus, _, pps = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
-                                                       pag_scale, pag_layers)
+            with biased:
+                pcs, pus, _, pps = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
+                                                           pag_scale, pag_layers)
             x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, pps=pps, pag_scale=pag_scale, **step_kw)
         elif guide is None:
-            pcs, pus, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
+            with biased:
+                pcs, pus, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
             x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, **step_kw)
         else:
             x_in = [x.detach().requires_grad_(True) for x in x_t]
@@ -776,6 +801,7 @@ class Sampler(nn.Module):
         guide = kwargs.get("guide")
         _check_guide(guide)
         _check_pag(kwargs.get("pag_scale", 0.0), guide)
+        _check_regions(kwargs.get("regions"), guide)
         gen = self._sample(*args, **kwargs)
         if guide is None:
             return gen if kwargs.get("yield_output", False) else next(gen)
@@ -810,8 +836,16 @@ class Sampler(nn.Module):
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-                known_noise_fn=None, guide=None, pag_scale=0.0, pag_layers="mid", **post_args):
-        """``pag_scale = s > 0``: perturbed-attention guidance (Ahn et al. 2024).  Every denoiser call carries B more rows,
+                known_noise_fn=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
+                **post_args):
+        """``regions = rp`` (a ``mdm_hip.RegionPrompts`` over the conditional rows of ``lm_outputs``): in the
+        ``SelfAttention`` layers with text keys that ``region_layers`` selects (the vocabulary of ``pag.select``; default
+        every one) the text logits get rp's bias -- log(token weight) + log(region coverage of the query position); 0 in the
+        unconditional rows; the perturbed block of ``pag_scale`` repeats the conditional rows'.  The switch is held around
+        each step's denoiser call only, never across a ``yield``.  Composes with ``solver=``, ``known_images=``, a late
+        start, ``pag_scale``, LoRA and MXFP8; not with ``guide=`` (NotImplementedError).  ``regions=None`` leaves every step
+        as it is.
+        ``pag_scale = s > 0``: perturbed-attention guidance (Ahn et al. 2024).  Every denoiser call carries B more rows,
         [uncond | cond | perturbed] (``lm_outputs`` stays [uncond | cond], or [cond] at ``guidance_scale == 1``), in which the
         ``SelfAttention`` layers that ``pag_layers`` selects (``pag.select``: "mid", "deepest", "all", names, a predicate)
         attend to themselves only, and the step gets  p_u + w (p_c - p_u) + s (p_c - p_hat).  Only the prediction handed to
@@ -831,6 +865,7 @@ class Sampler(nn.Module):
         _check_known(known_images, resample, solver)
         _check_guide(guide)
         _check_pag(pag_scale, guide)
+        _check_regions(regions, guide)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -853,7 +888,8 @@ class Sampler(nn.Module):
                 x0, x_t, extra = self.get_xt_minus_1(
                     model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
-                    solver_state=history, second_order=second, guide=guide, pag_scale=pag_scale, pag_layers=pag_layers)
+                    solver_state=history, second_order=second, guide=guide, pag_scale=pag_scale, pag_layers=pag_layers,
+                    regions=regions, region_layers=region_layers)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]

@@ -260,6 +260,9 @@ class SelfAttention(nn.Module):
     # perturbed-attention guidance (mdm_hip.pag.perturbed): the trailing _pag_rows batch rows get the identity self-attention
     # map (ops.attention_pag).  0: as above.
     _pag_rows = 0
+    # regional prompts / token weights (mdm_hip.regions.applied): a handle whose bias(N, H, W) -> fp32 [N, H * W, ld] is added
+    # to the text logits (ops.attention_biased).  None: as above.
+    _cross_bias = None
 
     def forward(self, x, cond=None, cond_mask=None):
         N, H, W, C = x.shape
@@ -292,7 +295,10 @@ class SelfAttention(nn.Module):
                     kvc = kvc.reshape(*cn.shape[:-1], kvc.shape[-1])
                 else:
                     kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
-        if self._pag_rows:
+        if self._cross_bias is not None and kvc is not None:
+            a = ops.attention_biased(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask, self._cross_bias.bias(N, H, W),
+                                     self.num_heads, self._pag_rows)
+        elif self._pag_rows:
             a = ops.attention_pag(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads,
                                   self._pag_rows)
         else:
