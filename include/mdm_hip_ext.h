@@ -26,6 +26,30 @@ int mdm_attn_cross_bias(const void* qkv, const void* kvc, const float* mask, con
                         const void* base, int base_ld, void* out, int B, int L, int S, int H, int d, int dtype,
                         void* stream);
 
+/* FreeU (Si et al., CVPR 2024) fused into the up path's skip concat: backbone h [N, H, W, C1], skip r [N, H, W, C2], NHWC,
+ * of dtype MDM_F32 or MDM_BF16 (the fp32-split mode has fp32 tensors: MDM_F32), arithmetic in fp32 ->
+ *   out[.., 0:C1/2]   = h[.., :C1/2] * m       m = b, or with `structure` (FreeU v2)  1 + (b - 1) hm[n, y, x],
+ *                                              hm = (mu - min mu) / (max mu - min mu), mu = mean of h over all C1 channels,
+ *                                              min / max over the pixels of sample n; max == min: hm = 1 (m = b)
+ *   out[.., C1/2:C1]  = h[.., C1/2:]           bit for bit
+ *   out[.., C1:C1+C2] = r + (s - 1) / (H W) * sum_k coef_k[n, c] phi_k(y, x),   coef_k = sum_{y, x} r phi_k,
+ *       phi = {1, cos t1, sin t1, cos t2, sin t2, cos t3, sin t3}, t1 = 2 pi y / H, t2 = 2 pi x / W, t3 = t1 + t2
+ * -- the Fourier filter of the paper at threshold 1 (rows H/2 - 1 .. H/2 and columns W/2 - 1 .. W/2 of the shifted
+ * spectrum scaled by s) in closed form; exact for H, W >= 2.  s == 1 copies r bit for bit, b == 1 copies h bit for bit.
+ * Limits: H, W >= 2, H + W <= 1024, N <= 65535, C1 % 16 == 0 and C2 % 8 == 0 for bf16, C1 % 8 == 0 and C2 % 4 == 0 for
+ * fp32; b finite and > 0, s finite and >= 0.
+ * mdm_freeu_plan (host-only): the bytes of the fp32 workspace both launches share.
+ * mdm_freeu_stats: reads r once -> coef [N, 7, C2] in ws (per-slab partials summed in slab order); with `structure`
+ *   reads h once -> mu [N, H W] and the per-sample min / max in ws.  h may be NULL without `structure`.
+ * mdm_freeu_apply: mdm_concat's forward with both transforms, from the ws that mdm_freeu_stats filled for the same
+ *   tensors and the same `structure`.  out must not alias h or r.
+ * No allocation, no host sync, no atomics: capturable, and two runs are bit-identical.  Forward only. */
+int mdm_freeu_plan(int N, int H, int W, int C1, int C2, int dtype, int structure, size_t* ws_bytes);
+int mdm_freeu_stats(const void* h, const void* r, void* ws, size_t ws_bytes, int N, int H, int W, int C1, int C2,
+                    int structure, int dtype, void* stream);
+int mdm_freeu_apply(const void* h, const void* r, const void* ws, size_t ws_bytes, void* out, int N, int H, int W, int C1,
+                    int C2, float b, float s, int structure, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ Layout of the package
   pag.py          perturbed-attention guidance: select / perturbed (the samplers' pag_scale / pag_layers)
   regions.py      regional prompts and token weights, a bias on the text cross-attention logits: RegionPrompts / concat /
                   applied (the samplers' regions / region_layers)
+  freeu.py        FreeU on the up path's skip concat: FreeU / select / applied (the samplers' freeu)
 """
 import os as _os
 
@@ -46,8 +47,12 @@ from .samplers import LossGuide  # noqa: F401,E402
 from . import pag  # noqa: F401,E402
 from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
+from . import freeu  # noqa: F401,E402
+from .freeu import FreeU  # noqa: F401,E402
 
 __all__ = [
+    "freeu",
+    "FreeU",
     "pag",
     "regions",
     "RegionPrompts",

@@ -22,8 +22,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops, pag, regions as _regions
-from .samplers import _check_known, _check_pag, _check_regions, _check_solver, pag_rows
+from . import freeu as _freeu, ops, pag, regions as _regions
+from .samplers import _check_freeu, _check_known, _check_pag, _check_regions, _check_solver, pag_rows
 
 
 class GraphedDenoiser(nn.Module):
@@ -67,8 +67,13 @@ class GraphedDenoiser(nn.Module):
         if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
             self._graphs.clear()
             self._adapter_epoch = ops.adapter_epoch()
-        # (+ the perturbed rows of perturbed-attention guidance, layer by layer: they change what a forward launches)
-        key = self._sig(x_t, times, conditioning, cond_mask) + (tuple(m._pag_rows for m in layers),)
+        # (+ the perturbed rows of perturbed-attention guidance, layer by layer, and the FreeU switch of every block: they
+        # change what a forward launches)
+        blocks = self.__dict__.get("_res_blocks")
+        if blocks is None:
+            blocks = self.__dict__["_res_blocks"] = _freeu.res_blocks(self.model)
+        key = self._sig(x_t, times, conditioning, cond_mask) + (tuple(m._pag_rows for m in layers),
+                                                                tuple(m._freeu for m in blocks))
         ent = self._graphs.get(key)
         is_list = isinstance(x_t, (list, tuple))
         xs = list(x_t) if is_list else [x_t]
@@ -154,7 +159,7 @@ class GraphedSampler:
                 mk(order, torch.float32), mk(jump, torch.float32)), t
 
     def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1,
-               pag_scale=0.0, pag_names=(), bias_source=None, region_names=()):
+               pag_scale=0.0, pag_names=(), bias_source=None, region_names=(), freeu=None):
         smp = self.sampler
         model = self.pipe.get_model()
         vm = model.vision_model
@@ -204,7 +209,8 @@ class GraphedSampler:
             else:
                 xin, tin = x_static, times
             with (pag.perturbed(vm, pag_names, rows=B) if pag_scale != 0 else contextlib.nullcontext()), \
-                    (_regions.applied(vm, bias_s, region_names) if bias_s is not None else contextlib.nullcontext()):
+                    (_regions.applied(vm, bias_s, region_names) if bias_s is not None else contextlib.nullcontext()), \
+                    (_freeu.applied(vm, freeu) if freeu is not None else contextlib.nullcontext()):
                 preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
             preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
@@ -268,8 +274,10 @@ class GraphedSampler:
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all"):
-        """``regions`` / ``region_layers``: regional prompts and token weights as ``Sampler._sample``.  Each graph entry owns
+               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all", freeu=None):
+        """``freeu``: a ``mdm_hip.FreeU`` as ``Sampler._sample`` -- the body runs the model under ``freeu.applied``; the graph
+        key holds ("freeu", the resolved block names, their b's, their s's, structure): other values capture anew.
+        ``regions`` / ``region_layers``: regional prompts and token weights as ``Sampler._sample``.  Each graph entry owns
         static bias buffers, one per attention resolution, filled by ``copy_`` from ``regions`` on every call (the pattern
         of the known images), and its body runs the model under ``regions.applied`` with a handle over those buffers.  The
         graph key holds ("regions", S, ld, the resolved layer names): other masks or weights replay the same graph, another
@@ -292,6 +300,7 @@ class GraphedSampler:
         _check_known(known_images, resample, solver)
         _check_pag(pag_scale)
         _check_regions(regions)
+        _check_freeu(freeu)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if start_step is not None and start_noise is None:
@@ -340,9 +349,11 @@ class GraphedSampler:
             region_names = _regions.layer_names(model.vision_model, region_layers)
             bias_source = regions.rows_for(guidance_scale != 1, pag_scale != 0, xs[0].device)
             key = key + (("regions", regions.S, regions.ld, region_names),)
+        if freeu is not None:
+            key = key + (_freeu.graph_key(model.vision_model, freeu),)
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
                                                    solver, known, int(resample), float(pag_scale), pag_names, bias_source,
-                                                   region_names)
+                                                   region_names, freeu)
         if bias_source is not None:
             ent["bias"].fill(bias_source)
         for sx, x in zip(ent["x"], xs):

@@ -2312,6 +2312,54 @@ def concat(a, b):
     return ConcatFn.apply(a, b)
 
 
+_freeu_plans = {}   # (N, H, W, C1, C2, dtype code, structure) -> workspace bytes of mdm_freeu_plan
+
+
+def concat_freeu(x, skip, b, s, structure=False, layer=None):
+    """``concat(x, skip)`` with FreeU (Si et al., CVPR 2024) applied to both on the way (include/mdm_hip_ext.h
+    mdm_freeu_stats + mdm_freeu_apply): the first C1 / 2 channels of the backbone ``x`` [N, H, W, C1] times ``b`` (with
+    ``structure``, FreeU v2: times 1 + (b - 1) hm, hm the per-sample min-max normalised channel mean of x), and the 2 x 2
+    lowest spatial frequencies of ``skip`` [N, H, W, C2] times ``s``.  b = s = 1 is ``concat`` bit for bit.  ``layer``: the
+    name an error message gives.  Forward only: the kernels have no backward."""
+    _require_gpu(x)
+    _require_gpu(skip)
+    what = "concat_freeu" if layer is None else "concat_freeu (%s)" % layer
+    if torch.is_grad_enabled() and (x.requires_grad or skip.requires_grad):
+        raise _lib.MdmHipError("%s is inference only (mdm_freeu_apply has no backward): run it under torch.no_grad()" % what)
+    if x.dim() != 4 or skip.dim() != 4 or x.shape[:3] != skip.shape[:3] or x.dtype != skip.dtype or x.device != skip.device:
+        raise _lib.MdmHipError("%s: backbone %s %s and skip %s %s (wanted NHWC tensors of one dtype that differ in C only)"
+                               % (what, tuple(x.shape), x.dtype, tuple(skip.shape), skip.dtype))
+    b, s, structure = float(b), float(s), bool(structure)
+    if not (0 < b < float("inf")) or not (0 <= s < float("inf")):
+        raise _lib.MdmHipError("%s: b = %r, s = %r (wanted finite b > 0 and s >= 0)" % (what, b, s))
+    N, H, W, C1 = x.shape
+    C2 = skip.shape[-1]
+    if H < 2 or W < 2:
+        raise _lib.MdmHipError("%s: a %d x %d feature map -- the closed form of the Fourier filter needs H, W >= 2" % (what, H, W))
+    epv = _epv(x)
+    if C1 % (2 * epv) or C2 % epv or C1 == 0 or C2 == 0:
+        raise _lib.MdmHipError("%s: C1 = %d, C2 = %d in %s (wanted C1 %% %d == 0 and C2 %% %d == 0)"
+                               % (what, C1, C2, x.dtype, 2 * epv, epv))
+    x, skip = _c(x.detach()), _c(skip.detach())
+    L, dt = _lib.lib(), _dt(x)
+    key = (N, H, W, C1, C2, dt, structure)
+    wsb = _freeu_plans.get(key)
+    if wsb is None:
+        v = ctypes.c_size_t(0)
+        _lib.check(L.mdm_freeu_plan(N, H, W, C1, C2, dt, int(structure), ctypes.byref(v)), what + ": mdm_freeu_plan")
+        wsb = _freeu_plans[key] = v.value
+    ws = _f32_ws(wsb, x.device)
+    out = torch.empty((N, H, W, C1 + C2), dtype=x.dtype, device=x.device)
+    esz = x.element_size()
+    _prof_wrap("freeu_stats", float((skip.numel() + (x.numel() if structure else 0)) * esz), lambda: _lib.check(
+        L.mdm_freeu_stats(_p(x), _p(skip), _p(ws), wsb, N, H, W, C1, C2, int(structure), dt, _stream()),
+        what + ": mdm_freeu_stats"), kind="hbm")
+    _prof_wrap("freeu_apply", 2.0 * out.numel() * esz, lambda: _lib.check(
+        L.mdm_freeu_apply(_p(x), _p(skip), _p(ws), wsb, _p(out), N, H, W, C1, C2, b, s, int(structure), dt, _stream()),
+        what + ": mdm_freeu_apply"), kind="hbm")
+    return out
+
+
 class Upsample2xFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -31,6 +31,9 @@ the identity, and one combine (``ops.pag_combine``; ``pag_combine`` on CPU tenso
 and per token (``ops.attention_biased``).  The sampler extends its rows for the batch it builds -- 0 in the unconditional rows,
 the conditional rows' bias once more in the perturbed block -- and switches it on (``regions.applied``) around the denoiser call
 of each step alone; steps, solvers, known regions and the other guidances are untouched.
+``sample(..., freeu=FreeU(b=(b1, b2), s=(s1, s2)))`` is FreeU (Si et al. 2024; ``mdm_hip/freeu.py``): the skip concats of the
+selected up blocks scale half of the backbone channels and damp the skips' lowest spatial frequencies (``ops.concat_freeu``),
+switched on (``freeu.applied``) around the denoiser call of each step alone, every row of the model batch alike.
 """
 import contextlib
 import math
@@ -42,6 +45,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import freeu as _freeu
 from . import ops, pag
 from . import regions as _regions
 
@@ -154,6 +158,14 @@ def _check_regions(regions, guide=None):
                                   "has no backward, so the guide's input gradient cannot pass it")
     if regions is not None and not callable(getattr(regions, "rows_for", None)):
         raise ValueError("regions = %r (wanted a mdm_hip.RegionPrompts)" % (regions,))
+
+
+def _check_freeu(freeu, guide=None):
+    if freeu is not None and guide is not None:
+        raise NotImplementedError("guide= together with freeu=: the fused concat (mdm_freeu_apply) has no backward, so the "
+                                  "guide's input gradient cannot pass it")
+    if freeu is not None and not isinstance(freeu, _freeu.FreeU):
+        raise ValueError("freeu = %r (wanted a mdm_hip.FreeU)" % (freeu,))
 
 
 def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1, pag_scale=0.0):
@@ -699,8 +711,10 @@ class Sampler(nn.Module):
     # ---- one iteration: denoiser, then the update of every scale -----------------------------------------------
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all"):
-        """``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).  ``regions`` / ``region_layers``:
+                       second_order=False, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
+                       freeu=None):
+        """``freeu``: a ``mdm_hip.FreeU`` (see ``_sample``), switched on around the denoiser call below, nowhere else.
+        ``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).  ``regions`` / ``region_layers``:
         regional prompts and token weights (see ``_sample``): switched on around the denoiser call below, nowhere else.
         ``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
         top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
@@ -712,8 +726,10 @@ class Sampler(nn.Module):
         _check_guide(guide)
         _check_pag(pag_scale, guide)
         _check_regions(regions, guide)
+        _check_freeu(freeu, guide)
         x_t = self._to_scales(model, x_t)
         biased = contextlib.nullcontext()
+        scaled = contextlib.nullcontext() if freeu is None else _freeu.applied(getattr(model, "vision_model", model), freeu)
         if regions is not None:
             if regions.rows != x_t[0].shape[0]:
                 raise ValueError("regions over %d rows for a batch of %d images" % (regions.rows, x_t[0].shape[0]))
@@ -731,12 +747,12 @@ class Sampler(nn.Module):
                        g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
                        need_noise=solver is None and bool(self._noisy_step(time_step, last)))
         if pag_scale != 0:
-            with biased:
+            with biased, scaled:
                 pcs, pus, _, pps = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
                                                            pag_scale, pag_layers)
             x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, pps=pps, pag_scale=pag_scale, **step_kw)
         elif guide is None:
-            with biased:
+            with biased, scaled:
                 pcs, pus, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
             x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, **step_kw)
         else:
@@ -802,6 +818,7 @@ class Sampler(nn.Module):
         _check_guide(guide)
         _check_pag(kwargs.get("pag_scale", 0.0), guide)
         _check_regions(kwargs.get("regions"), guide)
+        _check_freeu(kwargs.get("freeu"), guide)
         gen = self._sample(*args, **kwargs)
         if guide is None:
             return gen if kwargs.get("yield_output", False) else next(gen)
@@ -837,8 +854,15 @@ class Sampler(nn.Module):
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
                 known_noise_fn=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
-                **post_args):
-        """``regions = rp`` (a ``mdm_hip.RegionPrompts`` over the conditional rows of ``lm_outputs``): in the
+                freeu=None, **post_args):
+        """``freeu = FreeU(b=(b1, b2), s=(s1, s2), structure=False, levels="deepest2")``: FreeU (Si et al. 2024) -- in the up
+        blocks that ``freeu.select`` names, the skip concat multiplies the first half of the backbone channels by b (v2,
+        ``structure=True``: by 1 + (b - 1) x the min-max normalised channel mean) and the 2 x 2 lowest spatial frequencies
+        of the skip by s, for every row of the model batch alike.  No extra denoiser call.  The switch is held around each
+        step's denoiser call only, never across a ``yield``.  Composes with ``solver=``, ``known_images=``, a late start,
+        ``pag_scale``, ``regions``, LoRA and MXFP8; not with ``guide=`` (NotImplementedError).  ``freeu=None`` leaves every
+        step as it is.
+        ``regions = rp`` (a ``mdm_hip.RegionPrompts`` over the conditional rows of ``lm_outputs``): in the
         ``SelfAttention`` layers with text keys that ``region_layers`` selects (the vocabulary of ``pag.select``; default
         every one) the text logits get rp's bias -- log(token weight) + log(region coverage of the query position); 0 in the
         unconditional rows; the perturbed block of ``pag_scale`` repeats the conditional rows'.  The switch is held around
@@ -866,6 +890,7 @@ class Sampler(nn.Module):
         _check_guide(guide)
         _check_pag(pag_scale, guide)
         _check_regions(regions, guide)
+        _check_freeu(freeu, guide)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -889,7 +914,7 @@ class Sampler(nn.Module):
                     model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
                     solver_state=history, second_order=second, guide=guide, pag_scale=pag_scale, pag_layers=pag_layers,
-                    regions=regions, region_layers=region_layers)
+                    regions=regions, region_layers=region_layers, freeu=freeu)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]

@@ -348,6 +348,12 @@ class ResNetBlock(nn.Module):
             c = resnet_configs[-1].output_channels
             self.resample = nn.Conv2d(c, c, kernel_size=3, stride=2 if downsample_output else 1, padding=1, bias=True)
 
+    # FreeU (mdm_hip.freeu.applied): (b, s, structure) -- the up path's skip concat of this block scales half of the
+    # backbone channels and damps the skip's lowest spatial frequencies on the way (ops.concat_freeu).  None: no line below
+    # launches anything it did not launch before.  _freeu_name: the block's module name, for an error message.
+    _freeu = None
+    _freeu_name = None
+
     def forward(self, x, temb_act, skip_activations=None, return_activations=False, conditioning=None, cond_mask=None,
                 tap=None):
         """``tap``: where the incoming x is recorded as a skip activation, if it is (see ResNet.forward)"""
@@ -362,7 +368,10 @@ class ResNetBlock(nn.Module):
         L = self.num_attention_layers
         for i in range(self.num_residual_blocks):
             if skip_activations is not None:
-                x = ops.concat(x, skip_activations.pop(0))
+                if self._freeu is None:
+                    x = ops.concat(x, skip_activations.pop(0))
+                else:
+                    x = ops.concat_freeu(x, skip_activations.pop(0), *self._freeu, layer=self._freeu_name)
                 tap = None
             x = self.resnets[i](x, temb_act, tap)
             tap = None
