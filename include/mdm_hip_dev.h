@@ -18,6 +18,11 @@ int mdm_conv_wgrad_tile(int M, int Cout, int K, int dtype);
  *   0  1 = the LDS-DMA of conv_gemm_bl_kernel fetches nothing (timing only: what the k-loop costs without memory).  Its
  *      uniform branch also keeps the compiler's register allocation of the 3x3 instantiations (see conv_args.hpp)
  *   2  force the forward tile of conv_gemm_bl_kernel (128128 / 256192 / 256256; tools/kbench.py KB_TILE)
+ *   3  force the weight-gradient tile edge (128 / 256, 0 = cost model) wherever the kernel of that edge is eligible (256:
+ *      bf16, Cout >= 192 and K >= 192; elsewhere the cost model still decides).  Read by the one function behind
+ *      mdm_conv_wgrad_plan, mdm_conv_wgrad_tile, the launch and the workspace size, and by the grouped launch's tile
+ *      choice, so they stay consistent; set it before the plan call and leave it until after mdm_conv_wgrad_reduce.  Any
+ *      other value is an argument error (tests/conv_variant_cases.py: the 256-edge kernels at test size)
  *   8  1 = the narrow weight gradients (64 output channels, >= 262144 pixels) go back to the split GEMM (no wgrad_direct_kernel:
  *      the reference of tests/test_ops_gpu.py's direct-kernel test) */
 int mdm_dev_set_knob(int idx, int value);

@@ -2245,6 +2245,12 @@ static int launch_conv_bl_splitk(ConvArgs a, int splits, float* ws, hipStream_t 
 // 130 GEMMs of a step -- is exactly one round of 256x192 tiles at M = 16384).
 static int g_force_tile = 0;   // development knob 2 (mdm_dev_set_knob): 128128 / 256192 / 256256, 0 = cost model
 static int g_no_wgrad_direct = 0;   // development knob 8 (mdm_dev_set_knob): 1 = no wgrad_direct_kernel (split GEMM for the narrow weight gradients too)
+static int g_force_wgrad_tile = 0;   // development knob 3 (mdm_dev_set_knob): 128 / 256 = that weight-gradient tile edge wherever it is eligible, 0 = cost model
+// the forced weight-gradient tile edge for a problem, 0 = none (knob at 0, or 256 asked of a problem the 8-wave kernel does not take)
+static int wgrad_forced_tile(int Cout, int K, int dtype) {
+  if (g_force_wgrad_tile == 256) return (dtype == DT_BF16 && Cout >= 192 && K >= 192) ? 256 : 0;
+  return g_force_wgrad_tile;
+}
 static int conv_tile_code(int M, int Cout, int dtype) {
   if (Cout <= 32) return 128032;
   if (Cout <= 64) return 128064;
@@ -2388,9 +2394,12 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(DirectArgs p) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) o[i] = acc[nb][mb][i] + bv[mb][i];
           if (p.res) {
+            // same arithmetic as conv_epilogue: the sum + bias is rounded to bf16 BEFORE the residual is added (the
+            // convolution's output and the add are separate bf16 ops of the reference's autocast graph) -- so a layer gives
+            // the same bits whether its image is large enough for this kernel or goes through the implicit GEMM
             const bf16x4 rv = *reinterpret_cast<const bf16x4*>(p.res + off);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] += (float)rv[i];
+            for (int i = 0; i < 4; ++i) o[i] = (float)(bf16)o[i] + (float)rv[i];
           }
           bf16x4 ov;
 #pragma unroll
@@ -2675,9 +2684,10 @@ extern "C" int mdm_linear_grouped(const void* const* x, const void* const* w_pac
 extern "C" int mdm_dev_ffn_aux_bytes(void) { return kFfnAuxByte ? 1 : 2; }
 
 extern "C" int mdm_dev_set_knob(int idx, int value) {
-  MDM_CHECK_ARG(idx == 0 || idx == 2 || idx == 8);
+  MDM_CHECK_ARG(idx == 0 || idx == 2 || idx == 3 || idx == 8);
   if (idx == 0) g_dev_flags = value ? 2 : 0;
   else if (idx == 2) g_force_tile = value;
+  else if (idx == 3) { MDM_CHECK_ARG(value == 0 || value == 128 || value == 256); g_force_wgrad_tile = value; }
   else g_no_wgrad_direct = value;
   return 0;
 }
@@ -2880,8 +2890,10 @@ static void wgrad_choose(int M, int Cout, int K, int dtype, int* te_out, int* sp
   const int mt_total = (M + bkm - 1) / bkm;
   double best = 1e30;
   int best_te = 128, best_s = 1;
+  const int forced = wgrad_forced_tile(Cout, K, dtype);
   for (int te = 128; te <= 256; te += 128) {
     if (te == 256 && !(dtype == DT_BF16 && Cout >= 192 && K >= 192)) continue;
+    if (forced && te != forced) continue;
     const int tiles = ((Cout + te - 1) / te) * ((K + te - 1) / te);
     const int slots = te == 256 ? 256 : 512;
     const double t_tile = (te == 256 ? 1.7 : 1.06) * (dtype == DT_F32 ? 8.0 : 1.0), t_fix = te == 256 ? 12.0 : 5.0;
@@ -3019,6 +3031,7 @@ extern "C" int mdm_conv_wgrad_blocked(const void* x, const void* dyb, int want_b
 // chip without a split (the caller then launches them one by one through mdm_conv_wgrad).
 static int wgrad_group_tile(int M, int Cout, int K, int groups) {
   if (groups < 2 || groups > WG_MAXG || M < 4096) return 0;
+  if (const int forced = wgrad_forced_tile(Cout, K, DT_BF16)) return forced;
   const long t256 = (long)((Cout + 255) / 256) * ((K + 255) / 256) * groups;
   const long t128 = (long)((Cout + 127) / 128) * ((K + 127) / 128) * groups;
   const int cus = device_cus();
@@ -3056,6 +3069,7 @@ extern "C" int mdm_conv_wgrad_grouped(const void* const* x, const void* const* d
     gr.x[g] = x[g]; gr.dy[g] = dy[g]; gr.out[g] = dw[g]; gr.bout[g] = dbias ? dbias[g] : nullptr;
   }
   int te = wgrad_group_tile(M, Cout, Cin, groups);
+  if (!te) te = wgrad_forced_tile(Cout, Cin, DT_BF16);
   if (!te) te = (Cout >= 192 && Cin >= 192) ? 256 : 128;   // legal for any group size; the plan decides when it pays
   const int tiles = ((Cout + te - 1) / te) * ((Cin + te - 1) / te);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);

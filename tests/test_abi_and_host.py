@@ -67,6 +67,37 @@ def test_tile_and_split_cost_models():
         assert -(-mt // per) == sp.value                        # canonical: no empty split
     assert L.mdm_conv_wgrad_tile(4096, 64, 64, BF16) == 128     # 256 needs both output dims >= 192
     assert L.mdm_conv_wgrad_tile(16384, 768, 3072, F32) == 128
+    # development knob 3 forces the weight-gradient tile edge wherever the kernel of that edge is eligible; plan, tile and
+    # workspace size follow it together, and at 0 everything above is what the cost model says
+    def plan(M, Cout, K, dt=BF16):
+        sp, ws = ctypes.c_int(0), ctypes.c_size_t(0)
+        assert L.mdm_conv_wgrad_plan(M, Cout, K, dt, ctypes.byref(sp), ctypes.byref(ws)) == 0
+        return L.mdm_conv_wgrad_tile(M, Cout, K, dt), sp.value, ws.value
+    shapes = [(16384, 768, 3072), (65536, 512, 4608), (630, 200, 648), (512, 264, 2304), (4096, 64, 64), (630, 136, 64)]
+    at0 = {s: plan(*s) for s in shapes}
+    assert at0[(630, 200, 648)][0] == 128 and at0[(512, 264, 2304)][0] == 128     # test-sized problems never pick 256 on their own
+    try:
+        for forced in (128, 256):
+            assert L.mdm_dev_set_knob(3, forced) == 0
+            for (M, Cout, K) in shapes:
+                te, sp, ws = plan(M, Cout, K)
+                assert te == (forced if (forced == 128 or (Cout >= 192 and K >= 192)) else 128), (forced, M, Cout, K)
+                assert 1 <= sp <= 64 and ws >= sp * Cout * K * 4
+                mt = -(-M // 64)
+                assert -(-mt // -(-mt // sp)) == sp                 # still a canonical split count
+                if te == at0[(M, Cout, K)][0]:
+                    assert (te, sp, ws) == at0[(M, Cout, K)]        # forcing what the model chose changes nothing
+            assert L.mdm_conv_wgrad_tile(16384, 768, 3072, F32) == 128      # fp32 has one tile
+            tile = ctypes.c_int(0)
+            assert L.mdm_conv_wgrad_group_plan(4096, 512, 256, BF16, 4, ctypes.byref(tile)) == 0 and tile.value == forced
+            assert L.mdm_conv_wgrad_group_plan(4096, 128, 64, BF16, 5, ctypes.byref(tile)) == 0 and tile.value == (128 if forced == 128 else 0)
+            assert L.mdm_conv_wgrad_group_plan(4096, 512, 256, BF16, 1, ctypes.byref(tile)) == 0 and tile.value == 0   # not a group
+        for bad in (1, 64, 192, 512, -128):
+            assert L.mdm_dev_set_knob(3, bad) != 0
+        assert plan(630, 200, 648)[0] == 256                        # a rejected value leaves the knob where it was
+    finally:
+        assert L.mdm_dev_set_knob(3, 0) == 0
+    assert {s: plan(*s) for s in shapes} == at0
 
 
 def test_forward_split_k_plan():

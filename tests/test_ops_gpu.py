@@ -39,6 +39,11 @@ def nchw(t_nhwc):
     return t_nhwc.float().cpu().permute(0, 3, 1, 2).contiguous()
 
 
+# (Cin, Cout, ksize, stride) -> the forward kernel of a bf16 image of >= 65536 pixels, W % 64 == 0, H % 8 == 0
+DIRECT_FWD = {(32, 32, 3, 1): "conv3x3_direct_kernel<32, 32, 8, 64, 2>", (32, 64, 3, 1): "conv3x3_direct_kernel<32, 64, 8, 64, 4>",
+              (64, 32, 3, 1): "conv3x3_direct_kernel<64, 32, 8, 32, 2>", (64, 64, 3, 1): "conv3x3_direct_kernel<64, 64, 8, 32, 4>"}
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize(
     "N,H,W,Cin,Cout,ks,stride",
@@ -50,25 +55,26 @@ def nchw(t_nhwc):
         (1, 7, 5, 24, 8, 3, 1),         # small N config
         (2, 32, 32, 32, 32, 3, 1),
         (2, 12, 12, 136, 264, 3, 1),    # Cin not a multiple of the k-tile
-        (8, 121, 119, 40, 136, 3, 1),   # 450 tiles of 256x256: the 8-wave big-tile kernel, ragged M / N / K
+        (8, 121, 119, 40, 136, 3, 1),   # 450 tiles of 256x256: the 8-wave big-tile conv_gemm_kernel, ragged M / N / K (input gradient: 128x64)
         (4, 128, 128, 72, 200, 1, 1),   # same, 1x1, exactly one wave of tiles
-        (4, 256, 256, 16, 72, 3, 2),    # same, stride 2 (forward) + transposed gradient
-        (3, 24, 20, 264, 328, 3, 1),    # Cout >= 256 and K >= 256: the 256x256 transpose-read wgrad tile, ragged
-        (2, 16, 16, 512, 256, 1, 1),    # same, 1x1
-        # Cin % 64 == 0 (bf16): the buffer-addressed k-loop (conv_gemm_bl_kernel), 128x128 and 256x256 tiles
+        (4, 256, 256, 16, 72, 3, 2),    # stride 2: conv_gemm_kernel 128x128 forward (the cost model keeps Cout = 72 off the big tile), MODE_3x3_T2 gradient on 128x32
+        (3, 24, 20, 264, 328, 3, 1),    # Cout >= 256 and K >= 256, ragged: conv_wgrad_tr_kernel at the 128 edge (the cost model picks the 256
+                                        # edge only from about M = 16384, 768 x 2304; tests/conv_variant_cases.py forces it with knob 3)
+        (2, 16, 16, 512, 256, 1, 1),    # same, 1x1: conv_wgrad_bl_kernel, 128 edge
+        # Cin % 64 == 0 (bf16): the buffer-addressed k-loop (conv_gemm_bl_kernel), 128x128 and 256x192 tiles
         (3, 20, 24, 128, 136, 3, 1),    # 128x128, ragged M / N, image borders inside a tile
         (2, 18, 22, 64, 200, 3, 2),     # 128x128, stride 2
-        (8, 127, 63, 128, 320, 3, 1),   # 256x256 forward (ragged M / N), 128x128 input gradient
-        (8, 127, 63, 128, 264, 1, 1),   # 256x256, 1x1
-        (8, 254, 126, 64, 264, 3, 2),   # 256x256, stride 2
+        (8, 127, 63, 128, 320, 3, 1),   # 256x192 forward (ragged M / N), 128x128 input gradient
+        (8, 127, 63, 128, 264, 1, 1),   # 256x192, 1x1
+        (8, 254, 126, 64, 264, 3, 2),   # 256x192, stride 2
         # stride 2 with Cout % 64 == 0, even H / W (bf16): the pixel-unshuffled input gradient (mdm_conv_s2_dgrad)
         (2, 32, 32, 256, 256, 3, 2),
         (4, 64, 48, 128, 192, 3, 2),    # ragged tiles of the 4 Cin = 512 wide output
         # power-of-two images / 1x1: the buffer-addressed wgrad (conv_wgrad_bl_kernel)
         (3, 4, 8, 64, 72, 3, 1),        # 128x128 tile, ragged reduction tail (M = 96), image borders everywhere
         (5, 9, 7, 64, 136, 1, 1),       # 128x128, 1x1, M = 315
-        (2, 16, 16, 256, 320, 3, 1),    # 256x256 tile (K = 2304), ragged Cout
-        (4, 128, 128, 64, 264, 1, 1),   # 256x256, 1x1 (M = 65536), K below one tile
+        (2, 16, 16, 256, 320, 3, 1),    # 128 edge (K = 2304), ragged Cout; forward and input gradient run split over K
+        (4, 128, 128, 64, 264, 1, 1),   # 128 edge, 1x1 (M = 65536), K below one tile
         # 1024 tiles of 128x128 on 512 resident blocks: the persistent kernel's second output tile per block
         (8, 128, 128, 64, 128, 1, 1),   # single k-tile (K = 64)
         (8, 128, 128, 64, 128, 3, 1),
@@ -86,6 +92,7 @@ def nchw(t_nhwc):
     ],
 )
 def test_conv_fwd_bwd(dtype, N, H, W, Cin, Cout, ks, stride):
+    # (which kernel each bf16 shape runs is pinned row by row in tests/test_conv_variants_gpu.py; here the direct-kernel cases)
     from mdm_hip import ops
 
     g = torch.Generator().manual_seed(0)
@@ -103,6 +110,9 @@ def test_conv_fwd_bwd(dtype, N, H, W, Cin, Cout, ks, stride):
     bd = b.detach().to(dev()).requires_grad_()
     rd = nhwc(res.detach(), dtype).requires_grad_()
     y = ops.conv(xd, wd, bd, residual=rd, stride=stride)
+    if dtype == torch.bfloat16 and (Cin, Cout, ks, stride) in DIRECT_FWD and N * H * W >= 65536:
+        from mdm_hip import _lib
+        assert _lib.lib().mdm_last_gemm_kernel().decode() == DIRECT_FWD[(Cin, Cout, ks, stride)]
     y.backward(nhwc(gy, dtype))
     tol = TOL[dtype]
     assert relerr(nchw(y), y_ref) < tol
@@ -181,6 +191,7 @@ def test_conv_wgrad_direct_kernel(N, H, W, Cin, ks):
 
     dw, db, names = grads(0)
     assert any("wgrad_direct_kernel" in n for n in names), names
+    assert any(n.startswith("wgrad_direct_kernel<64, 9, 8>") for n in names), names
     dw_ref, db_ref, names_ref = grads(1)
     assert not any("wgrad_direct_kernel" in n for n in names_ref), names_ref
     assert relerr(dw, dw_ref) < 2e-5 and relerr(db, db_ref) < 2e-5
