@@ -50,6 +50,43 @@ int mdm_freeu_stats(const void* h, const void* r, void* ws, size_t ws_bytes, int
 int mdm_freeu_apply(const void* h, const void* r, const void* ws, size_t ws_bytes, void* out, int N, int H, int W, int C1,
                     int C2, float b, float s, int structure, int dtype, void* stream);
 
+/* Projected and rescaled classifier-free guidance: the combine in front of mdm_sampler_step / mdm_sampler_step_2m, which
+ * then get pred_uncond = NULL and guidance = 1 (the place of mdm_pag_combine).  APG (Sadat, Hilliges, Weber, ICLR 2025),
+ * CFG rescale (Lin, Liu, Li, Yang, WACV 2024, section 3.4) and the guidance interval (Kynkaanniemi et al., NeurIPS 2024)
+ * as a device gate.  fp32 [B, chw] tensors, gamma [B]; per sample, with x0 = a x_t + be p (pred_type 2, V: a = sqrt(g),
+ * be = -sqrt(1 - g); 0 / 1, eps: a = 1 / sqrt(g), be = -sqrt(1 - g) / sqrt(g)):
+ *   D = a x_t + be p_c ;  E = be (p_c - p_u) + momentum run_prev  (run_prev taken as 0 where it is NULL or run_gate is off)
+ *   run_out = E   (before the cap)
+ *   s = min(1, norm_threshold / (image_scale sqrt(<E, E> / chw)))   (norm_threshold == 0, or a zero E: s = 1)
+ *   c = <E, D> / <D, D>   (<D, D> == 0: c = 0)
+ *   p_g = p_c + (guidance - 1) s (E - (1 - eta) c D) / be
+ *   out = p_g (rescale std(p_c) / std(p_g) + 1 - rescale)   (population std over chw; rescale == 0 or std(p_g) == 0: out = p_g)
+ * eta = 1, norm_threshold = 0, no run buffers and rescale = 0: plain classifier-free guidance up to rounding.
+ * norm_threshold caps the RMS of the update in IMAGE units (the paper's L2 radius r = norm_threshold sqrt(chw)), so one
+ * value serves every scale of a nested model.  be == 0 (gamma == 1): out = p_c.
+ * run_gate, w_gate: DEVICE float[1], NULL = on; they select.  run_gate off: run_prev is not read.  w_gate off (outside the
+ * guidance interval): out = p_c bit for bit, x_t / p_u / ws are not read, and the history passes through -- run_out =
+ * run_prev bit for bit (0 where run_gate is off too).  So one captured graph serves a whole trajectory.
+ * mdm_cfg_plan (host-only): the bytes of the fp32 workspace both launches share -- per sample and per slab of the image 3
+ *   sums, 9 with the rescale (the Gram matrix of (p_c, E, D) and their plain sums: the variance of p_g follows from them,
+ *   there is no second pass over the images).
+ * mdm_cfg_stats: reads x_t, p_c, p_u (and run_prev) once; writes the per-slab sums and, if run_out is given, E.  run_out may
+ *   alias run_prev, nothing else.  run_out == NULL: no momentum (run_prev must be NULL too).  |momentum| < 1.
+ * mdm_cfg_combine: adds every sample's slab sums in a fixed order in fp64, forms the coefficients in fp64 and writes out.
+ *   `run`: the run_out that mdm_cfg_stats wrote for this step (E is read from it, pred_uncond is not read), or NULL (E is
+ *   formed from pred_uncond again).  Same tensors, gates, gamma, B, chw, pred_type and rescale > 0 as the statistics call.
+ *   out may alias pred, nothing else.  rescale in [0, 1], norm_threshold >= 0, image_scale > 0, eta and guidance finite.
+ * Limits: chw % 4 == 0, 1 <= B <= 65535, 16-byte aligned tensors.  The slab geometry depends on chw alone: a sample's result
+ * does not depend on the rest of the batch.  No allocation, no host sync, no atomics: capturable, and two runs are
+ * bit-identical. */
+int mdm_cfg_plan(int B, size_t chw, int rescale_on, size_t* ws_bytes);
+int mdm_cfg_stats(const float* x_t, const float* pred, const float* pred_uncond, const float* gamma, const float* run_prev,
+                  float* run_out, const float* run_gate, const float* w_gate, float momentum, int rescale_on, void* ws,
+                  size_t ws_bytes, int B, size_t chw, int pred_type, void* stream);
+int mdm_cfg_combine(const float* x_t, const float* pred, const float* pred_uncond, const float* gamma, const float* run,
+                    const float* w_gate, const void* ws, size_t ws_bytes, float* out, float guidance, float eta,
+                    float norm_threshold, float rescale, float image_scale, int B, size_t chw, int pred_type, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ Layout of the package
   regions.py      regional prompts and token weights, a bias on the text cross-attention logits: RegionPrompts / concat /
                   applied (the samplers' regions / region_layers)
   freeu.py        FreeU on the up path's skip concat: FreeU / select / applied (the samplers' freeu)
+  guidance.py     projected and rescaled classifier-free guidance (APG, CFG rescale, guidance interval): CFG / cfg_combine
+                  (the samplers' cfg)
 """
 import os as _os
 
@@ -49,8 +51,12 @@ from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
 from . import freeu  # noqa: F401,E402
 from .freeu import FreeU  # noqa: F401,E402
+from . import guidance  # noqa: F401,E402
+from .guidance import CFG  # noqa: F401,E402
 
 __all__ = [
+    "guidance",
+    "CFG",
     "freeu",
     "FreeU",
     "pag",

@@ -144,7 +144,7 @@ class Diffusion(nn.Module):
 
     def sample(self, num_examples, sample, image_side, device, **kwargs):
         """keywords go to the sampler's ``sample`` (``guidance_scale``, ``solver``, ``known_images``, ``pag_scale``, ``regions`` /
-        ``region_layers`` ...)"""
+        ``region_layers``, ``freeu``, ``cfg`` ...)"""
         self.eval()
         noise = self.get_noise(num_examples, self.get_model().input_channels, image_side, device)
         return self.sampler.sample(self.get_model(), noise, sample["lm_outputs"], sample["lm_mask"],

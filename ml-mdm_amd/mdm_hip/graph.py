@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import freeu as _freeu, ops, pag, regions as _regions
-from .samplers import _check_freeu, _check_known, _check_pag, _check_regions, _check_solver, pag_rows
+from .samplers import _check_cfg, _check_freeu, _check_known, _check_pag, _check_regions, _check_solver, pag_rows
 
 
 class GraphedDenoiser(nn.Module):
@@ -124,7 +124,12 @@ class GraphedSampler:
     repeats every row of the iteration tables but the last r times and ends the body with the jump kernel of every scale,
     gated by a device table (1 on all but the last row of a group).  ``start_step`` starts the replay at the first row
     whose time is <= it (the SDEdit start; ``start_noise`` then carries the noised image).  Without known images and
-    with resample == 1 the captured graph has no launch more than before."""
+    with resample == 1 the captured graph has no launch more than before.
+
+    ``cfg=CFG(...)`` (projected / rescaled guidance, ``mdm_hip/guidance.py``): the body runs the combine kernels of every
+    scale on every row, gated by two device tables -- the interval gate (off: the conditional prediction passes through bit
+    for bit) and the history gate of the momentum (off up to and on the first guided row of the call: the static momentum
+    buffers are then not read, so what a warm-up pass or an earlier call left in them is never seen)."""
 
     def __init__(self, pipeline, warmup: int = 2, seed: int = 0):
         self.pipe = pipeline
@@ -159,7 +164,7 @@ class GraphedSampler:
                 mk(order, torch.float32), mk(jump, torch.float32)), t
 
     def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1,
-               pag_scale=0.0, pag_names=(), bias_source=None, region_names=(), freeu=None):
+               pag_scale=0.0, pag_names=(), bias_source=None, region_names=(), freeu=None, cfg=None):
         smp = self.sampler
         model = self.pipe.get_model()
         vm = model.vision_model
@@ -179,6 +184,13 @@ class GraphedSampler:
         # dpmpp_2m: the x0 of the step before, per scale.  Read only where the order gate is on, so what a warm-up pass or
         # an earlier sample() call left in it is never seen: step 0 (gate off) rewrites it
         x0_prev = [torch.zeros_like(x) for x in xs] if solver is not None else None
+        # cfg: the momentum history per scale and the two gate tables, one row per replay; sample() fills the tables for
+        # the rows it replays.  Until then: guidance on, no history -- what the warm-up passes (row 0) run with
+        cfg_state = cfg_run_gate = cfg_w_gate = None
+        if cfg is not None:
+            cfg_state = {"cfg_run": [torch.zeros_like(x) for x in xs]} if cfg.momentum != 0 else {}
+            cfg_run_gate = torch.zeros(len(t_host), dtype=torch.float32, device=dev)
+            cfg_w_gate = torch.ones(len(t_host), dtype=torch.float32, device=dev)
         micros_s = {k: v.clone() for k, v in micros.items()}   # micro-conditioning ([B] per key, diffusion.py:136-141): static inputs
         # the text path (lm_proj, masked mean, cond_emb) does not depend on t: computed once per sample() call into
         # static buffers, outside the per-step graph
@@ -226,6 +238,9 @@ class GraphedSampler:
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> torch.quantile, a
             # sort + lerp on the device, -> update kernel, all captured).  Every row draws and advances the generator in
             # the eager sampler's order (use_device_rng()); the device gate decides whether the noise is added
+            if cfg is not None:
+                history.update(cfg=cfg, cfg_state=cfg_state,
+                               cfg_gates=(cfg_run_gate.index_select(0, idx), cfg_w_gate.index_select(0, idx)))
             _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, need_noise=True,
                                          guidance_scale=guidance, ddim_eta=ddim_eta, solver=solver, rng=rng, noise_gate=gate,
                                          pps=pps, pag_scale=pag_scale, **history)
@@ -267,15 +282,21 @@ class GraphedSampler:
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
                    t_host=t_host, order=tab_order, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
-                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev))
+                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate,
+                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev, cfg_state))
         self._graphs[key] = ent
         return ent
 
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all", freeu=None):
-        """``freeu``: a ``mdm_hip.FreeU`` as ``Sampler._sample`` -- the body runs the model under ``freeu.applied``; the graph
+               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all", freeu=None,
+               cfg=None):
+        """``cfg``: a ``mdm_hip.CFG`` as ``Sampler._sample`` (nothing changes at ``guidance_scale == 1``).  The graph key
+        holds ("cfg", eta, norm_threshold, momentum, rescale, interval): other values capture anew.  Each entry owns the
+        momentum buffers and the two gate tables; every call rewrites the tables for the rows it replays, so a late start
+        and a second call begin without history, as the eager sampler does.
+        ``freeu``: a ``mdm_hip.FreeU`` as ``Sampler._sample`` -- the body runs the model under ``freeu.applied``; the graph
         key holds ("freeu", the resolved block names, their b's, their s's, structure): other values capture anew.
         ``regions`` / ``region_layers``: regional prompts and token weights as ``Sampler._sample``.  Each graph entry owns
         static bias buffers, one per attention resolution, filled by ``copy_`` from ``regions`` on every call (the pattern
@@ -301,6 +322,9 @@ class GraphedSampler:
         _check_pag(pag_scale)
         _check_regions(regions)
         _check_freeu(freeu)
+        _check_cfg(cfg, None, pag_scale)
+        if cfg is not None and guidance_scale == 1:
+            cfg = None
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if start_step is not None and start_noise is None:
@@ -351,9 +375,11 @@ class GraphedSampler:
             key = key + (("regions", regions.S, regions.ld, region_names),)
         if freeu is not None:
             key = key + (_freeu.graph_key(model.vision_model, freeu),)
+        if cfg is not None:
+            key = key + (cfg.key(),)
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
                                                    solver, known, int(resample), float(pag_scale), pag_names, bias_source,
-                                                   region_names, freeu)
+                                                   region_names, freeu, cfg)
         if bias_source is not None:
             ent["bias"].fill(bias_source)
         for sx, x in zip(ent["x"], xs):
@@ -377,6 +403,14 @@ class GraphedSampler:
                 raise ValueError("start_step = %r is below every step of the schedule" % (start_step,))
             first = int(rows[0]) if len(rows) else ent["n"]   # t = 0: nothing left to replay
         ent["idx"].fill_(first)
+        if cfg is not None:
+            # the interval gate of every row, and the history gate: on from the row after the first guided one of this call
+            w_on = np.asarray([cfg.on(t, smp.n_steps) for t in ent["t_host"]], dtype="float32")
+            seen = np.concatenate(([0.0], np.cumsum(w_on[first:])[:-1])) if first < ent["n"] else np.zeros(0)
+            run_on = np.zeros(ent["n"], dtype="float32")
+            run_on[first:] = seen > 0
+            ent["cfg_w_gate"].copy_(torch.from_numpy(w_on))
+            ent["cfg_run_gate"].copy_(torch.from_numpy(run_on))
         if seed is not None:
             ent["rng"].state.copy_(torch.tensor([seed & (2**63 - 1), 0], dtype=torch.int64))
         # dpmpp_2m from a late start: there is no history at the first replayed row -- its order gate is off for this call

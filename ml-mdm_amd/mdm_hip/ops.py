@@ -2741,6 +2741,72 @@ def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1.0, pag_scale=0.0,
     return out
 
 
+_cfg_plans = {}   # (B, chw, rescale on) -> workspace bytes of mdm_cfg_plan
+
+
+def _gate(gate, what):
+    """a device float[1] that a kernel selects by (None = on)"""
+    if gate is None:
+        return None
+    _require_gpu(gate)
+    if gate.dtype != torch.float32 or gate.numel() != 1:
+        raise _lib.MdmHipError("%s must be a device float[1] (got %s %s)" % (what, gate.dtype, tuple(gate.shape)))
+    return _c(gate.detach().reshape(-1))
+
+
+def cfg_combine(x_t, pred, pred_uncond, g, prediction_type, guidance_scale, eta=1.0, norm_threshold=0.0, momentum=0.0,
+                rescale=0.0, image_scale=1.0, run_prev=None, run_out=None, run_gate=None, w_gate=None, out=None):
+    """Projected and rescaled classifier-free guidance (mdm_hip/guidance.py; include/mdm_hip_ext.h mdm_cfg_stats +
+    mdm_cfg_combine) as TWO kernels: per-sample statistics, then the combine.  -> (p_g, run)
+
+    ``momentum != 0``: ``run`` is the update of this step, written to ``run_out`` (which may be ``run_prev`` itself; a new
+    tensor if None), and ``run_prev`` the one of the step before (None = no history); ``momentum == 0``: no run buffers,
+    ``run`` is None.  ``run_gate`` / ``w_gate``: device float[1] gates, None = on -- ``run_gate`` off: ``run_prev`` is not
+    read (no history); ``w_gate`` off: p_g is ``pred`` and ``run`` is ``run_prev`` bit for bit (zeros where ``run_gate`` is
+    off too), so that one captured graph serves every step.  ``out`` may be ``pred`` itself.  The workspace comes from the
+    caching allocator: no host sync, capturable."""
+    x_t, pred, pu = _img(x_t), _img(pred), _img(pred_uncond)
+    B = x_t.shape[0]
+    chw = x_t.numel() // B
+    for t, what in ((pred, "pred"), (pu, "pred_uncond")):
+        if t.shape != x_t.shape:
+            raise _lib.MdmHipError("cfg_combine: %s %s vs x_t %s" % (what, tuple(t.shape), tuple(x_t.shape)))
+    if chw % 4:
+        raise _lib.MdmHipError("cfg_combine: C * H * W must be a multiple of 4 (got %s)" % (tuple(x_t.shape),))
+    g = _vec(g, B)
+    momentum, rescale = float(momentum), float(rescale)
+    rp = ro = None
+    if momentum != 0:
+        if run_prev is not None:
+            rp = _img(run_prev)
+            if rp.shape != x_t.shape:
+                raise _lib.MdmHipError("cfg_combine: run_prev %s vs x_t %s" % (tuple(rp.shape), tuple(x_t.shape)))
+        ro = torch.empty_like(x_t) if run_out is None else _inplace_img(run_out, x_t, "cfg_combine: run_out")
+    elif run_prev is not None or run_out is not None:
+        raise _lib.MdmHipError("cfg_combine: run_prev= / run_out= belong to momentum != 0")
+    rg, wg = _gate(run_gate, "cfg_combine: run_gate"), _gate(w_gate, "cfg_combine: w_gate")
+    out = torch.empty_like(pred) if out is None else _inplace_img(out, pred, "cfg_combine: out")
+    L = _lib.lib()
+    key = (B, chw, rescale > 0)
+    wsb = _cfg_plans.get(key)
+    if wsb is None:
+        v = ctypes.c_size_t(0)
+        _lib.check(L.mdm_cfg_plan(B, chw, int(rescale > 0), ctypes.byref(v)), "mdm_cfg_plan")
+        wsb = _cfg_plans[key] = v.value
+    ws = _f32_ws(wsb, x_t.device)
+    pt = _PT[prediction_type.upper()] if isinstance(prediction_type, str) else _ptype(prediction_type)   # names too, as the torch ops
+    sc = float(image_scale) if image_scale else 1.0
+    n = float(x_t.numel() * 4)
+    _prof_wrap("cfg_stats", n * (3 + (rp is not None) + (ro is not None)), lambda: _lib.check(
+        L.mdm_cfg_stats(_p(x_t), _p(pred), _p(pu), _p(g), _p(rp), _p(ro), _p(rg), _p(wg), momentum, int(rescale > 0), _p(ws),
+                        wsb, B, chw, pt, _stream()), "mdm_cfg_stats"), kind="hbm")
+    _prof_wrap("cfg_combine", n * 4, lambda: _lib.check(
+        L.mdm_cfg_combine(_p(x_t), _p(pred), _p(pu), _p(g), _p(ro), _p(wg), _p(ws), wsb, _p(out), float(guidance_scale),
+                          float(eta), float(norm_threshold), rescale, sc, B, chw, pt, _stream()), "mdm_cfg_combine"),
+        kind="hbm")
+    return out, ro
+
+
 def noise_images(images, g, eps=None, rng=None, rng_stream=0, inv_scale=1.0):
     """x_t = sqrt(g) * images * inv_scale + sqrt(1 - g) * eps (reference samplers.py:244-246).  ``eps=None`` draws the
     noise inside the kernel from ``rng``.  -> (x_t, eps)"""

@@ -34,6 +34,10 @@ of each step alone; steps, solvers, known regions and the other guidances are un
 ``sample(..., freeu=FreeU(b=(b1, b2), s=(s1, s2)))`` is FreeU (Si et al. 2024; ``mdm_hip/freeu.py``): the skip concats of the
 selected up blocks scale half of the backbone channels and damp the skips' lowest spatial frequencies (``ops.concat_freeu``),
 switched on (``freeu.applied``) around the denoiser call of each step alone, every row of the model batch alike.
+``sample(..., cfg=CFG(eta=, norm_threshold=, momentum=, rescale=, interval=))`` replaces the classifier-free guidance combine
+p_u + w (p_c - p_u) by the projected and rescaled one (``mdm_hip/guidance.py``: adaptive projected guidance, Sadat et al.
+2025; the std rescale of Lin et al. 2024; the guidance interval of Kynkaanniemi et al. 2024): per scale two launches
+(``ops.cfg_combine``; ``guidance.cfg_combine`` on CPU tensors) in front of the unchanged step, as PAG's combine.
 """
 import contextlib
 import math
@@ -46,6 +50,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import freeu as _freeu
+from . import guidance as _guidance
 from . import ops, pag
 from . import regions as _regions
 
@@ -166,6 +171,22 @@ def _check_freeu(freeu, guide=None):
                                   "guide's input gradient cannot pass it")
     if freeu is not None and not isinstance(freeu, _freeu.FreeU):
         raise ValueError("freeu = %r (wanted a mdm_hip.FreeU)" % (freeu,))
+
+
+def _check_cfg(cfg, guide=None, pag_scale=0.0):
+    if cfg is None:
+        return
+    if not isinstance(cfg, _guidance.CFG):
+        raise ValueError("cfg = %r (wanted a mdm_hip.CFG)" % (cfg,))
+    cfg.validate()
+    if guide is not None:
+        raise NotImplementedError("guide= together with cfg=: the guide seeds the two halves of the doubled batch with the "
+                                  "weights of the plain combine (w and 1 - w); the projected / rescaled combine depends on "
+                                  "per-sample statistics of both predictions, and its Jacobian is not implemented")
+    if pag_scale != 0:
+        raise NotImplementedError("pag_scale != 0 together with cfg=: mdm_pag_combine adds the perturbed-attention term to "
+                                  "the plain combine; projecting, capping and rescaling an update of three predictions is "
+                                  "not implemented")
 
 
 def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1, pag_scale=0.0):
@@ -712,8 +733,11 @@ class Sampler(nn.Module):
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
                        second_order=False, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
-                       freeu=None):
-        """``freeu``: a ``mdm_hip.FreeU`` (see ``_sample``), switched on around the denoiser call below, nowhere else.
+                       freeu=None, cfg=None):
+        """``cfg``: a ``mdm_hip.CFG`` (see ``_sample``) -- with ``guidance_scale != 1`` the step gets the projected / rescaled
+        combine of the two predictions; the momentum history lives in ``solver_state["cfg_run"]`` (one tensor per scale,
+        absent until the first guided step), so without a ``solver_state`` every call starts without history.
+        ``freeu``: a ``mdm_hip.FreeU`` (see ``_sample``), switched on around the denoiser call below, nowhere else.
         ``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).  ``regions`` / ``region_layers``:
         regional prompts and token weights (see ``_sample``): switched on around the denoiser call below, nowhere else.
         ``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
@@ -727,6 +751,7 @@ class Sampler(nn.Module):
         _check_pag(pag_scale, guide)
         _check_regions(regions, guide)
         _check_freeu(freeu, guide)
+        _check_cfg(cfg, guide, pag_scale)
         x_t = self._to_scales(model, x_t)
         biased = contextlib.nullcontext()
         scaled = contextlib.nullcontext() if freeu is None else _freeu.applied(getattr(model, "vision_model", model), freeu)
@@ -746,6 +771,8 @@ class Sampler(nn.Module):
         step_kw = dict(guidance_scale=guidance_scale, ddim_eta=ddim_eta, solver=solver, second_order=second_order,
                        g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
                        need_noise=solver is None and bool(self._noisy_step(time_step, last)))
+        if cfg is not None and guidance_scale != 1:
+            step_kw.update(cfg=cfg, cfg_state=st, cfg_on=cfg.on(time_step, self.n_steps))
         if pag_scale != 0:
             with biased, scaled:
                 pcs, pus, _, pps = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
@@ -774,15 +801,19 @@ class Sampler(nn.Module):
 
     def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, need_noise=False, guidance_scale=1, ddim_eta=None,
                      solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, rng=None, noise_gate=None,
-                     x0_out=None, pps=None, pag_scale=0.0):
+                     x0_out=None, pps=None, pag_scale=0.0, cfg=None, cfg_state=None, cfg_on=True, cfg_gates=None):
         """The update of every scale behind the denoiser call -> (x0 list, x_s list).  All lists hi -> lo, one entry per
         scale; ``g_prev`` / ``x0_prev``: the history of ``solver="dpmpp_2m"``, or None.  This is the one reverse step of the
         eager samplers and of ``GraphedSampler``, whose captured graph passes ``rng``, ``noise_gate``, a device
         ``second_order`` gate and ``x0_out`` through to the step kernels.  ``pps`` with ``pag_scale != 0``: the perturbed
         predictions of perturbed-attention guidance -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU tensors:
-        ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1."""
+        ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1.  ``cfg`` (a
+        ``mdm_hip.CFG``) with ``guidance_scale != 1`` does the same with the projected / rescaled combine (``_cfg_scales``)."""
         n = len(x_t)
         g_prev, x0_prev, x0_out = (v or [None] * n for v in (g_prev, x0_prev, x0_out))
+        if cfg is not None and guidance_scale != 1:
+            pcs = self._cfg_scales(cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, cfg_state, cfg_on, cfg_gates)
+            pus, guidance_scale = [None] * n, 1
         if pps is not None and pag_scale != 0:
             pcs = [ops.pag_combine(pc.float(), None if pu is None else pu.float(), pp.float(), guidance_scale, pag_scale)
                    if pc.is_cuda else pag_combine(pc, pu, pp, guidance_scale, pag_scale) for pc, pu, pp in zip(pcs, pus, pps)]
@@ -803,6 +834,35 @@ class Sampler(nn.Module):
             x_s.append(b)
         return x0, x_s
 
+    def _cfg_scales(self, cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, state=None, on=True, gates=None):
+        """The projected / rescaled guidance combine of every scale (``mdm_hip/guidance.py``) -> the guided predictions.
+        ``state``: the trajectory's dict; ``state["cfg_run"]`` holds the momentum history, one tensor per scale, updated here
+        (GPU tensors: in place) and absent until the first guided step.  Eager: ``on`` says whether the step lies in the
+        guidance interval -- outside it nothing is launched, the conditional predictions pass through and the history
+        stays.  ``GraphedSampler``: ``gates`` = (run_gate, w_gate), device float[1] each, and static history buffers in
+        ``state["cfg_run"]``; the same kernels run gated on every row, to the same bits."""
+        if gates is None and not on:
+            return pcs
+        state = {} if state is None else state
+        run = state.get("cfg_run")
+        run_gate, w_gate = gates if gates is not None else (None, None)
+        kw = dict(cfg.options(), prediction_type=self._config.prediction_type)
+        out, runs = [], []
+        for i, (x, pc, pu) in enumerate(zip(x_t, pcs, pus)):
+            prev = None if run is None else run[i]
+            if pc.is_cuda:
+                p, r = ops.cfg_combine(x.float(), pc.float(), pu.float(), g_t[i], guidance_scale=guidance_scale,
+                                       image_scale=image_scales[i], run_prev=prev, run_out=prev, run_gate=run_gate,
+                                       w_gate=w_gate, **kw)
+            else:
+                p, r = _guidance.cfg_combine(x, pc, pu, g_t[i], guidance_scale=guidance_scale, image_scale=image_scales[i],
+                                             run_prev=prev, **kw)
+            out.append(p)
+            runs.append(r)
+        if cfg.momentum != 0:
+            state["cfg_run"] = runs
+        return out
+
     # ---- the sampling loop (:510-609) ----------------------------------------------------------
     def set_timesteps(self, num_inference_steps=250):
         ratio = (self._config.num_diffusion_steps + 1) / (num_inference_steps + 1)
@@ -819,6 +879,7 @@ class Sampler(nn.Module):
         _check_pag(kwargs.get("pag_scale", 0.0), guide)
         _check_regions(kwargs.get("regions"), guide)
         _check_freeu(kwargs.get("freeu"), guide)
+        _check_cfg(kwargs.get("cfg"), guide, kwargs.get("pag_scale", 0.0))
         gen = self._sample(*args, **kwargs)
         if guide is None:
             return gen if kwargs.get("yield_output", False) else next(gen)
@@ -854,8 +915,21 @@ class Sampler(nn.Module):
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
                 known_noise_fn=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
-                freeu=None, **post_args):
-        """``freeu = FreeU(b=(b1, b2), s=(s1, s2), structure=False, levels="deepest2")``: FreeU (Si et al. 2024) -- in the up
+                freeu=None, cfg=None, **post_args):
+        """``cfg = CFG(eta=1, norm_threshold=0, momentum=0, rescale=0, interval=None)`` with ``guidance_scale != 1``: the
+        classifier-free guidance combine  p_u + w (p_c - p_u)  is replaced by the projected / rescaled one of
+        ``mdm_hip/guidance.py`` -- adaptive projected guidance (Sadat et al. 2025: the part of the update parallel to the
+        conditional x0 scaled by ``eta``, its RMS in image units capped at ``norm_threshold`` -- the paper's radius over
+        sqrt(C H W), so one value serves every scale --, a ``momentum`` across steps), the std rescale (Lin et al. 2024,
+        ``rescale`` = phi) and the guidance interval (Kynkaanniemi et al. 2024: outside ``interval``, in fractions of
+        ``num_diffusion_steps``, the step takes the conditional prediction).  One combine per scale in front of the unchanged
+        step (GPU tensors: ``ops.cfg_combine``, two launches; CPU tensors: ``guidance.cfg_combine``), which then gets no
+        unconditional prediction and guidance 1.  The momentum history, one buffer per scale, starts empty with every
+        trajectory, wherever it starts, and every denoiser call updates it, the repeats of ``resample`` included.  Only
+        the prediction handed to the update changes, so it composes with ``ddim_eta``, ``solver=``, ``known_images=``, a late
+        start, ``regions``, ``freeu``, LoRA, MXFP8 and every threshold function; not with ``guide=`` or ``pag_scale != 0``
+        (NotImplementedError).  ``cfg=None``, or ``guidance_scale == 1``, leaves every step as it is.
+        ``freeu = FreeU(b=(b1, b2), s=(s1, s2), structure=False, levels="deepest2")``: FreeU (Si et al. 2024) -- in the up
         blocks that ``freeu.select`` names, the skip concat multiplies the first half of the backbone channels by b (v2,
         ``structure=True``: by 1 + (b - 1) x the min-max normalised channel mean) and the 2 x 2 lowest spatial frequencies
         of the skip by s, for every row of the model batch alike.  No extra denoiser call.  The switch is held around each
@@ -891,6 +965,7 @@ class Sampler(nn.Module):
         _check_pag(pag_scale, guide)
         _check_regions(regions, guide)
         _check_freeu(freeu, guide)
+        _check_cfg(cfg, guide, pag_scale)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -903,7 +978,7 @@ class Sampler(nn.Module):
             known = self._known_region(model, x_t, known_images, known_mask, known_seed, known_noise_fn)
         seq = [x_t] if return_sequence else []
         x0 = extra = None
-        history = {}   # dpmpp_2m: x0 and gamma of the step before, per scale
+        history = {}   # dpmpp_2m: x0 and gamma of the step before, per scale; cfg: the momentum buffers ("cfg_run")
         for i, ts in enumerate(steps[:-1]):
             # second order needs history (not on the first step of this trajectory, wherever it starts) and a finite
             # step in log-SNR (not on the last one: it goes to gamma = 1)
@@ -914,7 +989,7 @@ class Sampler(nn.Module):
                     model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
                     solver_state=history, second_order=second, guide=guide, pag_scale=pag_scale, pag_layers=pag_layers,
-                    regions=regions, region_layers=region_layers, freeu=freeu)
+                    regions=regions, region_layers=region_layers, freeu=freeu, cfg=cfg)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
