@@ -6,7 +6,8 @@ Layout of the package
   unet.py         UNet, config dataclasses (mirror of ml_mdm.models.unet)
   nested_unet.py  NestedUNet (mirror of ml_mdm.models.nested_unet)
   diffusion.py    Diffusion / NestedDiffusion train-step + sampling call surface
-  samplers.py     noise schedules + DDPM/DDIM updates; LossGuide: loss-guided (DPS) sampling through the model's input gradient
+  samplers.py     noise schedules + DDPM/DDIM updates; LossGuide: loss-guided (DPS) sampling through the model's input gradient;
+                  SampleOptions: the sampling options beyond the reference, their checks and what they compose with
   configs.py      the three shipped architectures (cc12m 64 / 256 / 1024)
   distributed.py  one-process-per-GPU data parallel gradient reducer over RCCL
   registry.py     plug into the reference's ml_mdm.config registries when present

@@ -143,8 +143,8 @@ class Diffusion(nn.Module):
         return torch.randn(num_examples, input_channels, image_side, image_side).to(device)  # CPU RNG, as the reference (:177)
 
     def sample(self, num_examples, sample, image_side, device, **kwargs):
-        """keywords go to the sampler's ``sample`` (``guidance_scale``, ``solver``, ``known_images``, ``pag_scale``, ``regions`` /
-        ``region_layers``, ``freeu``, ``cfg`` ...)"""
+        """keywords go to the sampler's ``sample`` (``guidance_scale``, ``solver``, ``known_images`` ..., and the options of
+        ``samplers.SampleOptions``)"""
         self.eval()
         noise = self.get_noise(num_examples, self.get_model().input_channels, image_side, device)
         return self.sampler.sample(self.get_model(), noise, sample["lm_outputs"], sample["lm_mask"],
@@ -161,7 +161,7 @@ class Diffusion(nn.Module):
         stream 0 and advanced by ``numel`` per scale, hi -> lo; CPU tensors: the torch formula with ``noise_fn``
         (default ``torch.randn_like``).  ``graphed``: a ``GraphedSampler`` of this pipeline -- the remaining steps are
         replayed by it (``start_step``) instead of the eager sampler.  Other keywords go to ``sample`` (``ddim_eta``,
-        ``solver``, ``guidance_scale``, ``known_images``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers`` ...)."""
+        ``solver``, ``guidance_scale``, ``known_images`` ..., and the options of ``samplers.SampleOptions``)."""
         self.eval()
         smp, model = self.sampler, self.get_model()
         n = kwargs.get("num_inference_steps", 2000) if kwargs.get("resample_steps", False) else smp.n_steps

@@ -13,7 +13,7 @@ No default values for ``b`` and ``s``: the published ones belong to Stable Diffu
 """
 import math
 
-from .unet import ResNetBlock
+from .unet import ResNetBlock, switched
 
 LEVEL_SETS = ("deepest2",)
 
@@ -113,34 +113,12 @@ def graph_key(vision_model, cfg):
             cfg.structure)
 
 
-def res_blocks(vision_model):
-    """every ``ResNetBlock``, in ``modules()`` order: a cache of captured forwards (``GraphedDenoiser``) keys on their
-    ``_freeu`` beside the shapes"""
-    return [m for m in vision_model.modules() if isinstance(m, ResNetBlock)]
-
-
-class applied:
+class applied(switched):
     """``with applied(vision_model, cfg):`` -- inside, the selected up blocks concatenate through ``ops.concat_freeu``; on
     exit (also by an exception) every block has what it had before."""
 
     def __init__(self, vision_model, cfg):
-        self.selection = select(vision_model, cfg)
-        self.structure = cfg.structure
-
-    def __enter__(self):
-        self.saved = [(m.__dict__.get("_freeu"), m.__dict__.get("_freeu_name")) for _, m, _, _ in self.selection]
-        for n, m, b, s in self.selection:
-            m._freeu, m._freeu_name = (b, s, self.structure), n
-        return self
-
-    def __exit__(self, *exc):
-        for (_, m, _, _), (sw, name) in zip(self.selection, self.saved):
-            for attr, v in (("_freeu", sw), ("_freeu_name", name)):
-                if v is not None:
-                    setattr(m, attr, v)
-                else:
-                    m.__dict__.pop(attr, None)   # back to the class attribute
-        return False
+        super().__init__((m, {"_freeu": (b, s, cfg.structure), "_freeu_name": n}) for n, m, b, s in select(vision_model, cfg))
 
 
-__all__ = ["FreeU", "select", "applied", "graph_key", "res_blocks", "up_blocks"]
+__all__ = ["FreeU", "select", "applied", "graph_key", "up_blocks"]

@@ -16,14 +16,13 @@ loading a checkpoint (the packed kernel-layout weights baked into the graph woul
 merging or unmerging LoRA adapters (``mdm_hip.lora``) changes what a forward launches: both classes
 drop their graphs when ``ops.adapter_epoch()`` has moved, so the next call captures anew instead of replaying a stale one.
 """
-import contextlib
-
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import freeu as _freeu, ops, pag, regions as _regions
-from .samplers import _check_cfg, _check_freeu, _check_known, _check_pag, _check_regions, _check_solver, pag_rows
+from . import ops, regions as _regions
+from .samplers import SampleOptions, _check_known, _check_solver, pag_rows, repeat_rows, split_rows
+from .unet import switch_state, switchable
 
 
 class GraphedDenoiser(nn.Module):
@@ -38,6 +37,7 @@ class GraphedDenoiser(nn.Module):
         self._warmup = warmup
         self._graphs = {}
         self._adapter_epoch = ops.adapter_epoch()
+        self._switchable = switchable(model)
 
     # attributes the diffusion / sampler code reads from the vision model
     def __getattr__(self, name):
@@ -59,21 +59,15 @@ class GraphedDenoiser(nn.Module):
     def forward(self, x_t, times, conditioning=None, cond_mask=None, micros={}):
         if torch.is_grad_enabled() or self.model.training or micros:
             return self.model(x_t, times, conditioning, cond_mask, micros)
-        layers = self.__dict__.get("_attn_layers")
-        if layers is None:
-            layers = self.__dict__["_attn_layers"] = pag.attention_layers(self.model)
-        if _regions.any_applied(layers):
+        switches = switch_state(self._switchable)
+        if any(h is not None for h in switches["_cross_bias"]):
             return self.model(x_t, times, conditioning, cond_mask, micros)
         if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
             self._graphs.clear()
             self._adapter_epoch = ops.adapter_epoch()
         # (+ the perturbed rows of perturbed-attention guidance, layer by layer, and the FreeU switch of every block: they
         # change what a forward launches)
-        blocks = self.__dict__.get("_res_blocks")
-        if blocks is None:
-            blocks = self.__dict__["_res_blocks"] = _freeu.res_blocks(self.model)
-        key = self._sig(x_t, times, conditioning, cond_mask) + (tuple(m._pag_rows for m in layers),
-                                                                tuple(m._freeu for m in blocks))
+        key = self._sig(x_t, times, conditioning, cond_mask) + (switches["_pag_rows"], switches["_freeu"])
         ent = self._graphs.get(key)
         is_list = isinstance(x_t, (list, tuple))
         xs = list(x_t) if is_list else [x_t]
@@ -163,9 +157,12 @@ class GraphedSampler:
         return (mk(t, torch.long), mk(s, torch.long), mk(gate.astype("float32"), torch.float32), mk(p, torch.long),
                 mk(order, torch.float32), mk(jump, torch.float32)), t
 
-    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver=None, known=None, resample=1,
-               pag_scale=0.0, pag_names=(), bias_source=None, region_names=(), freeu=None, cfg=None):
+    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver, known, resample, opts, names,
+               bias_source):
+        """``opts``: the call's ``SampleOptions``, with what ``sample`` resolved of them for this model: ``names``, its
+        ``layer_names``, and the caller's bias handle (None without ``regions``)"""
         smp = self.sampler
+        cfg = opts.cfg_at(guidance)
         model = self.pipe.get_model()
         vm = model.vision_model
         dev = xs[0].device
@@ -214,36 +211,23 @@ class GraphedSampler:
             times = (t - 1).expand(B)
             # the model's batch: [uncond | cond] under classifier-free guidance, + [perturbed] under perturbed-attention
             # guidance (the static conditioning and micros buffers hold that many rows)
-            reps = (2 if guidance != 1 else 1) + (1 if pag_scale != 0 else 0)
-            if reps > 1:
-                xin = [torch.cat([x] * reps) for x in x_static]
-                tin = torch.cat([times] * reps)
-            else:
-                xin, tin = x_static, times
-            with (pag.perturbed(vm, pag_names, rows=B) if pag_scale != 0 else contextlib.nullcontext()), \
-                    (_regions.applied(vm, bias_s, region_names) if bias_s is not None else contextlib.nullcontext()), \
-                    (_freeu.applied(vm, freeu) if freeu is not None else contextlib.nullcontext()):
+            uncond, pert = opts.blocks(guidance)
+            xin, tin = repeat_rows(x_static, times, 1 + uncond + pert)
+            with opts.switches(vm, guidance, B, names=names, bias=bias_s):
                 preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
             preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
                 preds = [torch.tanh(p / out_scale) * out_scale for p in preds]
-            pus, pps = [None] * len(preds), None
-            if reps > 1:
-                parts = [p.chunk(reps) for p in preds]
-                if pag_scale != 0:
-                    pps, parts = [p[-1] for p in parts], [p[:-1] for p in parts]
-                preds = [p[-1] for p in parts]
-                if guidance != 1:
-                    pus = [p[0] for p in parts]
+            preds, pus, pps = split_rows(preds, uncond, pert)
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> torch.quantile, a
             # sort + lerp on the device, -> update kernel, all captured).  Every row draws and advances the generator in
             # the eager sampler's order (use_device_rng()); the device gate decides whether the noise is added
             if cfg is not None:
-                history.update(cfg=cfg, cfg_state=cfg_state,
+                history.update(cfg_state=cfg_state,
                                cfg_gates=(cfg_run_gate.index_select(0, idx), cfg_w_gate.index_select(0, idx)))
-            _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, need_noise=True,
+            _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, opts, need_noise=True,
                                          guidance_scale=guidance, ddim_eta=ddim_eta, solver=solver, rng=rng, noise_gate=gate,
-                                         pps=pps, pag_scale=pag_scale, **history)
+                                         pps=pps, **history)
             for x, xl in zip(x_static, x_last):
                 x.copy_(xl)
             if known is not None:   # blends hi -> lo, then jumps hi -> lo: the draw order of KnownRegion
@@ -290,22 +274,21 @@ class GraphedSampler:
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all", freeu=None,
-               cfg=None):
-        """``cfg``: a ``mdm_hip.CFG`` as ``Sampler._sample`` (nothing changes at ``guidance_scale == 1``).  The graph key
-        holds ("cfg", eta, norm_threshold, momentum, rescale, interval): other values capture anew.  Each entry owns the
-        momentum buffers and the two gate tables; every call rewrites the tables for the rows it replays, so a late start
-        and a second call begin without history, as the eager sampler does.
-        ``freeu``: a ``mdm_hip.FreeU`` as ``Sampler._sample`` -- the body runs the model under ``freeu.applied``; the graph
-        key holds ("freeu", the resolved block names, their b's, their s's, structure): other values capture anew.
-        ``regions`` / ``region_layers``: regional prompts and token weights as ``Sampler._sample``.  Each graph entry owns
-        static bias buffers, one per attention resolution, filled by ``copy_`` from ``regions`` on every call (the pattern
-        of the known images), and its body runs the model under ``regions.applied`` with a handle over those buffers.  The
-        graph key holds ("regions", S, ld, the resolved layer names): other masks or weights replay the same graph, another
-        S or layer set captures anew.
-        ``pag_scale`` / ``pag_layers``: perturbed-attention guidance as ``Sampler._sample`` -- the static conditioning and
-        micros buffers carry the perturbed block's rows, the body runs the model under ``pag.perturbed`` and one combine
-        kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
+               start_step=None, **options):
+        """``options``: the keywords of ``SampleOptions`` (what each does is said there), with these graph-specific facts;
+        the key parts are ``SampleOptions.graph_key``, and the body runs the model under ``SampleOptions.switches``.
+        ``guide``: refused -- neither the user's function nor the autograd pass of every step can be captured.
+        ``cfg``: the graph key holds ("cfg", eta, norm_threshold, momentum, rescale, interval): other values capture anew.
+        Each entry owns the momentum buffers and the two gate tables; every call rewrites the tables for the rows it
+        replays, so a late start and a second call begin without history, as the eager sampler does.
+        ``freeu``: the graph key holds ("freeu", the resolved block names, their b's, their s's, structure): other values
+        capture anew.
+        ``regions`` / ``region_layers``: each graph entry owns static bias buffers, one per attention resolution, filled by
+        ``copy_`` from ``regions`` on every call (the pattern of the known images), and its body hands the switch a handle
+        over those buffers.  The graph key holds ("regions", S, ld, the resolved layer names): other masks or weights
+        replay the same graph, another S or layer set captures anew.
+        ``pag_scale`` / ``pag_layers``: the static conditioning and micros buffers carry the perturbed block's rows and one
+        combine kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
         -> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
         guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
         drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on).
@@ -313,18 +296,15 @@ class GraphedSampler:
         known image, and ``resample``, are part of the graph key.  ``start_step=t``: replay only the rows whose time is
         <= t, from ``start_noise`` = the image noised to the first of them (``Diffusion.partial_diffusion(...,
         graphed=self)`` does the noising); the first replayed row of ``dpmpp_2m`` is first order, as in the eager sampler."""
-        if guide is not None:
+        opts = SampleOptions(**options)
+        if opts.guide is not None:
             raise NotImplementedError("GraphedSampler does not take guide=: loss-guided sampling calls an arbitrary user "
                                       "function and an autograd pass through the denoiser every step, and neither can be "
                                       "captured in a hipGraph; use the eager Sampler.sample(..., guide=...)")
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
-        _check_pag(pag_scale)
-        _check_regions(regions)
-        _check_freeu(freeu)
-        _check_cfg(cfg, None, pag_scale)
-        if cfg is not None and guidance_scale == 1:
-            cfg = None
+        opts.check()
+        cfg = opts.cfg_at(guidance_scale)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if start_step is not None and start_noise is None:
@@ -351,9 +331,12 @@ class GraphedSampler:
         # (reference diffusion.py:194-196); one value per row of the model's batch (2B under guidance)
         micros = {k: torch.as_tensor(v, device=xs[0].device).reshape(-1).float()
                   for k, v in self.pipe.get_micro_conditioning(sample).items()}
-        pag_names = ()
-        if pag_scale != 0:   # the perturbed block repeats the conditional rows of everything per-row
-            pag_names = pag.layer_names(model.vision_model, pag_layers)
+        regions = opts.regions
+        if regions is not None and (regions.rows != xs[0].shape[0] or regions.S != cond.shape[1]):
+            raise ValueError("regions over %d rows of %d tokens for a batch of %d images with %d tokens"
+                             % (regions.rows, regions.S, xs[0].shape[0], cond.shape[1]))
+        names = opts.layer_names(model.vision_model)
+        if opts.pag_scale != 0:   # the perturbed block repeats the conditional rows of everything per-row
             cond, mask, micros = pag_rows(xs[0].shape[0], cond, mask, micros)
         key = (tuple(tuple(x.shape) for x in xs), tuple(cond.shape), int(num_inference_steps), ddim_eta, float(guidance_scale),
                torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
@@ -363,23 +346,10 @@ class GraphedSampler:
         if known_images is not None:
             known = smp._known_region(model, xs, known_images, known_mask, known_seed, None)
             key = key + (tuple(k is not None for k in known.images), int(resample))
-        if pag_scale != 0:
-            key = key + (("pag", float(pag_scale), pag_names),)
-        bias_source, region_names = None, ()
-        if regions is not None:
-            if regions.rows != xs[0].shape[0] or regions.S != cond.shape[1]:
-                raise ValueError("regions over %d rows of %d tokens for a batch of %d images with %d tokens"
-                                 % (regions.rows, regions.S, xs[0].shape[0], cond.shape[1]))
-            region_names = _regions.layer_names(model.vision_model, region_layers)
-            bias_source = regions.rows_for(guidance_scale != 1, pag_scale != 0, xs[0].device)
-            key = key + (("regions", regions.S, regions.ld, region_names),)
-        if freeu is not None:
-            key = key + (_freeu.graph_key(model.vision_model, freeu),)
-        if cfg is not None:
-            key = key + (cfg.key(),)
+        key = key + opts.graph_key(model.vision_model, guidance_scale, names)
+        bias_source = None if regions is None else regions.rows_for(*opts.blocks(guidance_scale), xs[0].device)
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
-                                                   solver, known, int(resample), float(pag_scale), pag_names, bias_source,
-                                                   region_names, freeu, cfg)
+                                                   solver, known, int(resample), opts, names, bias_source)
         if bias_source is not None:
             ent["bias"].fill(bias_source)
         for sx, x in zip(ent["x"], xs):

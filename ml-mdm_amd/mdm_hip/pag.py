@@ -10,7 +10,7 @@ samplers do the rest (``Sampler.sample(..., pag_scale=s, pag_layers="mid")``, ``
 """
 import re
 
-from .unet import SelfAttention
+from .unet import SelfAttention, switched
 
 LAYER_SETS = ("mid", "deepest", "all")
 _MID = re.compile(r"(^|\.)mid_blocks\.\d+\.attn\.\d+$")
@@ -69,13 +69,7 @@ def layer_names(vision_model, layers="mid"):
     return tuple(n for n, _ in select(vision_model, layers))
 
 
-def attention_layers(vision_model):
-    """every ``SelfAttention`` layer, in ``modules()`` order: a cache of captured forwards (``GraphedDenoiser``) keys on
-    their ``_pag_rows`` beside the shapes"""
-    return [m for m in vision_model.modules() if isinstance(m, SelfAttention)]
-
-
-class perturbed:
+class perturbed(switched):
     """``with perturbed(vision_model, layers, rows):`` -- inside, the trailing ``rows`` batch rows of every selected layer
     get the identity self-attention map; on exit (also by an exception) every layer has what it had before."""
 
@@ -83,19 +77,4 @@ class perturbed:
         rows = int(rows)
         if rows < 0:
             raise ValueError("perturbed: rows = %d" % rows)
-        self.modules = [m for _, m in select(vision_model, layers)]
-        self.rows = rows
-
-    def __enter__(self):
-        self.saved = [m._pag_rows for m in self.modules]
-        for m in self.modules:
-            m._pag_rows = self.rows
-        return self
-
-    def __exit__(self, *exc):
-        for m, r in zip(self.modules, self.saved):
-            if r:
-                m._pag_rows = r
-            else:
-                m.__dict__.pop("_pag_rows", None)   # back to the class attribute
-        return False
+        super().__init__((m, {"_pag_rows": rows}) for _, m in select(vision_model, layers))

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops, pag
+from .unet import switched
 
 NEG_INF = float("-inf")
 
@@ -254,7 +255,7 @@ def layer_names(vision_model, layers="all"):
     return names
 
 
-class applied:
+class applied(switched):
     """``with applied(vision_model, rp, layers="all"):`` -- inside, the selected ``SelfAttention`` layers that have text keys
     add ``rp.bias(N, H, W)`` to their text logits (``rp``: a ``RegionPrompts``, or any handle with that method); on exit
     (also by an exception) every layer has what it had before."""
@@ -262,26 +263,7 @@ class applied:
     def __init__(self, vision_model, rp, layers="all"):
         if not callable(getattr(rp, "bias", None)):
             raise ValueError("applied: %r has no bias(N, h, w)" % (rp,))
-        self.modules = [vision_model.get_submodule(n) for n in layer_names(vision_model, layers)]
-        self.rp = rp
-
-    def __enter__(self):
-        self.saved = [m.__dict__.get("_cross_bias") for m in self.modules]
-        for m in self.modules:
-            m._cross_bias = self.rp
-        return self
-
-    def __exit__(self, *exc):
-        for m, h in zip(self.modules, self.saved):
-            if h is not None:
-                m._cross_bias = h
-            else:
-                m.__dict__.pop("_cross_bias", None)   # back to the class attribute
-        return False
-
-
-def any_applied(layers):
-    return any(m._cross_bias is not None for m in layers)
+        super().__init__((vision_model.get_submodule(n), {"_cross_bias": rp}) for n in layer_names(vision_model, layers))
 
 
 __all__ = ["RegionPrompts", "BatchBias", "StaticBias", "concat", "applied", "layer_names"]

@@ -20,28 +20,14 @@ same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.
 ``sample(..., known_images=, known_mask=, resample=, known_seed=)`` holds a region of every trajectory on a given image
 (the replacement method of RePaint, Lugmayr et al. 2022, with its resampling jumps; ``KnownRegion`` ->
 ``ops.sampler_known_blend`` / ``ops.sampler_jump``), and ``Diffusion.partial_diffusion`` starts a trajectory late from a
-noised image (SDEdit, Meng et al. 2022).  ``sample(..., guide=LossGuide(fn))`` is the general case of which a known region
-is the special one: every step is pulled towards a small differentiable loss of the clean-image estimate (diffusion
-posterior sampling, Chung et al. 2023), through the denoiser's input gradient (``ops.stem_conv``) and the kernels
-``ops.guide_seed`` / ``ops.guide_apply``.  ``sample(..., pag_scale=s, pag_layers="mid")`` is perturbed-attention guidance (Ahn
-et al. 2024; ``mdm_hip/pag.py``): B more rows of the model batch with the self-attention map of the selected layers replaced by
-the identity, and one combine (``ops.pag_combine``; ``pag_combine`` on CPU tensors) in front of the unchanged step.
-``sample(..., regions=rp, region_layers="all")`` is regional prompting and token weighting (``mdm_hip/regions.py``): the
-``RegionPrompts`` handle ``rp`` gives an additive bias on the text logits of the selected attention layers, per query position
-and per token (``ops.attention_biased``).  The sampler extends its rows for the batch it builds -- 0 in the unconditional rows,
-the conditional rows' bias once more in the perturbed block -- and switches it on (``regions.applied``) around the denoiser call
-of each step alone; steps, solvers, known regions and the other guidances are untouched.
-``sample(..., freeu=FreeU(b=(b1, b2), s=(s1, s2)))`` is FreeU (Si et al. 2024; ``mdm_hip/freeu.py``): the skip concats of the
-selected up blocks scale half of the backbone channels and damp the skips' lowest spatial frequencies (``ops.concat_freeu``),
-switched on (``freeu.applied``) around the denoiser call of each step alone, every row of the model batch alike.
-``sample(..., cfg=CFG(eta=, norm_threshold=, momentum=, rescale=, interval=))`` replaces the classifier-free guidance combine
-p_u + w (p_c - p_u) by the projected and rescaled one (``mdm_hip/guidance.py``: adaptive projected guidance, Sadat et al.
-2025; the std rescale of Lin et al. 2024; the guidance interval of Kynkaanniemi et al. 2024): per scale two launches
-(``ops.cfg_combine``; ``guidance.cfg_combine`` on CPU tensors) in front of the unchanged step, as PAG's combine.
+noised image (SDEdit, Meng et al. 2022).  Five options act on the denoiser call or on the prediction handed to the update
+and leave the update alone -- loss guidance (``guide``), perturbed-attention guidance (``pag_scale`` / ``pag_layers``), regional
+prompts and token weights (``regions`` / ``region_layers``), FreeU (``freeu``) and projected / rescaled classifier-free
+guidance (``cfg``): ``SampleOptions`` says what each does, holds their checks and is what travels from ``sample`` to the step.
 """
 import contextlib
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from enum import Enum
 
 import numpy as np
@@ -53,6 +39,7 @@ from . import freeu as _freeu
 from . import guidance as _guidance
 from . import ops, pag
 from . import regions as _regions
+from .unet import switched
 
 
 class ScheduleType(Enum):
@@ -149,46 +136,6 @@ def _check_known(known_images, resample, solver):
         raise ValueError("resample=%d with solver=%r: the multistep history is void after a jump" % (resample, solver))
 
 
-def _check_pag(pag_scale, guide=None):
-    if pag_scale < 0:
-        raise ValueError("pag_scale must be >= 0 (got %r); 0 = no perturbed-attention guidance" % (pag_scale,))
-    if pag_scale != 0 and guide is not None:
-        raise NotImplementedError("guide= together with pag_scale != 0: the perturbed rows' attention kernel "
-                                  "(mdm_attn_cross_addv) has no backward, so the guide's input gradient cannot pass it")
-
-
-def _check_regions(regions, guide=None):
-    if regions is not None and guide is not None:
-        raise NotImplementedError("guide= together with regions=: the biased cross-attention kernel (mdm_attn_cross_bias) "
-                                  "has no backward, so the guide's input gradient cannot pass it")
-    if regions is not None and not callable(getattr(regions, "rows_for", None)):
-        raise ValueError("regions = %r (wanted a mdm_hip.RegionPrompts)" % (regions,))
-
-
-def _check_freeu(freeu, guide=None):
-    if freeu is not None and guide is not None:
-        raise NotImplementedError("guide= together with freeu=: the fused concat (mdm_freeu_apply) has no backward, so the "
-                                  "guide's input gradient cannot pass it")
-    if freeu is not None and not isinstance(freeu, _freeu.FreeU):
-        raise ValueError("freeu = %r (wanted a mdm_hip.FreeU)" % (freeu,))
-
-
-def _check_cfg(cfg, guide=None, pag_scale=0.0):
-    if cfg is None:
-        return
-    if not isinstance(cfg, _guidance.CFG):
-        raise ValueError("cfg = %r (wanted a mdm_hip.CFG)" % (cfg,))
-    cfg.validate()
-    if guide is not None:
-        raise NotImplementedError("guide= together with cfg=: the guide seeds the two halves of the doubled batch with the "
-                                  "weights of the plain combine (w and 1 - w); the projected / rescaled combine depends on "
-                                  "per-sample statistics of both predictions, and its Jacobian is not implemented")
-    if pag_scale != 0:
-        raise NotImplementedError("pag_scale != 0 together with cfg=: mdm_pag_combine adds the perturbed-attention term to "
-                                  "the plain combine; projecting, capping and rescaling an update of three predictions is "
-                                  "not implemented")
-
-
 def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1, pag_scale=0.0):
     """torch ops of ``ops.pag_combine`` (for CPU tensors): classifier-free guidance plus perturbed-attention guidance (Ahn
     et al. 2024),  p_u + w (p_c - p_u) + s (p_c - p_hat);  p_c alone in front where ``pred_uncond`` is None"""
@@ -205,6 +152,22 @@ def pag_rows(n, lm_outputs, lm_mask, micros):
     per_row = lambda v: torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == rows
     return (ext(lm_outputs), None if lm_mask is None else ext(lm_mask),
             {k: ext(v) if per_row(v) else v for k, v in micros.items()})
+
+
+def repeat_rows(xs, t, reps):
+    """every scale of ``xs`` and the times ``t`` once per block of the model batch ([uncond | cond | perturbed]: ``reps``
+    of them); one block: as given, no copy"""
+    return (xs, t) if reps == 1 else ([torch.cat([x] * reps) for x in xs], torch.cat([t] * reps))
+
+
+def split_rows(preds, uncond, pert):
+    """what the model made of such a batch, per scale -> (conditional predictions, unconditional ones or Nones, perturbed
+    ones or None): the blocks present are [uncond |] cond [| perturbed]"""
+    if not (uncond or pert):
+        return list(preds), [None] * len(preds), None
+    parts = [p.chunk(1 + uncond + pert) for p in preds]
+    return ([p[int(uncond)] for p in parts], [p[0] if uncond else None for p in parts],
+            [p[-1] for p in parts] if pert else None)
 
 
 def known_blend(x, known, mask, g, inv_scale=1.0, noise=None):
@@ -370,9 +333,153 @@ class LossGuide:
         return torch.where(loss > 0, z, torch.zeros_like(z))
 
 
-def _check_guide(guide):
-    if guide is not None and not isinstance(guide, LossGuide):
-        raise TypeError("guide must be an mdm_hip.LossGuide (got %r)" % (type(guide).__name__,))
+@dataclass(frozen=True)
+class SampleOptions:
+    """The sampling options beyond the reference, as the keywords of ``Sampler.sample``, ``get_xt_minus_1``,
+    ``GraphedSampler.sample``, ``Diffusion.sample`` and ``Diffusion.partial_diffusion``.  Every default leaves every step
+    as it is; each option changes the denoiser call or the prediction handed to the update, never the update, so all of
+    them compose with ``ddim_eta``, ``solver=``, ``known_images=`` / ``resample``, a late start, LoRA and MXFP8.
+
+    ``guide``: a ``LossGuide`` -- loss-guided sampling; per step: the update, then the guide's correction, then the
+    known-region blend.  The model runs on leaf x_t with grad enabled, the step itself unchanged under no_grad; the loss
+    sees the top scale.  Eager samplers only.
+    ``pag_scale = s > 0``: perturbed-attention guidance (Ahn et al. 2024).  Every denoiser call carries B more rows,
+    [uncond | cond | perturbed] (``lm_outputs`` stays [uncond | cond], or [cond] at ``guidance_scale == 1``), in which the
+    ``SelfAttention`` layers that ``pag_layers`` selects (``pag.select``: "mid", "deepest", "all", names, a predicate)
+    attend to themselves only, and the step gets  p_u + w (p_c - p_u) + s (p_c - p_hat)  from one combine per scale (GPU
+    tensors: ``ops.pag_combine``, CPU tensors: ``pag_combine``).
+    ``regions = rp`` (a ``mdm_hip.RegionPrompts`` over the conditional rows of ``lm_outputs``): in the ``SelfAttention``
+    layers with text keys that ``region_layers`` selects (the vocabulary of ``pag.select``; default every one) the text
+    logits get rp's bias -- log(token weight) + log(region coverage of the query position); 0 in the unconditional rows;
+    the perturbed block of ``pag_scale`` repeats the conditional rows'.
+    ``freeu = FreeU(b=(b1, b2), s=(s1, s2), structure=False, levels="deepest2")``: FreeU (Si et al. 2024) -- in the up
+    blocks that ``freeu.select`` names, the skip concat multiplies the first half of the backbone channels by b (v2,
+    ``structure=True``: by 1 + (b - 1) x the min-max normalised channel mean) and the 2 x 2 lowest spatial frequencies of
+    the skip by s, for every row of the model batch alike.  No extra denoiser call.
+    ``cfg = CFG(eta=1, norm_threshold=0, momentum=0, rescale=0, interval=None)`` with ``guidance_scale != 1``: the
+    classifier-free guidance combine  p_u + w (p_c - p_u)  is replaced by the projected / rescaled one of
+    ``mdm_hip/guidance.py`` -- adaptive projected guidance (Sadat et al. 2025: the part of the update parallel to the
+    conditional x0 scaled by ``eta``, its RMS in image units capped at ``norm_threshold`` -- the paper's radius over
+    sqrt(C H W), so one value serves every scale --, a ``momentum`` across steps), the std rescale (Lin et al. 2024,
+    ``rescale`` = phi) and the guidance interval (Kynkaanniemi et al. 2024: outside ``interval``, in fractions of
+    ``num_diffusion_steps``, the step takes the conditional prediction).  One combine per scale in front of the unchanged
+    step (GPU tensors: ``ops.cfg_combine``, two launches; CPU tensors: ``guidance.cfg_combine``), which then gets no
+    unconditional prediction and guidance 1.  The momentum history, one buffer per scale, starts empty with every
+    trajectory, wherever it starts, and every denoiser call updates it, the repeats of ``resample`` included.  Nothing
+    changes at ``guidance_scale == 1``.
+
+    The three model switches (perturbed rows, region bias, FreeU) are held around each step's denoiser call only
+    (``switches``), never across a ``yield``, and a switch that is off is not even resolved.  What excludes what
+    (``check``: NotImplementedError): ``guide`` with each of the other four, because their kernels have no backward or, for
+    ``cfg``, no Jacobian; and ``pag_scale`` with ``cfg``.  Everything else composes."""
+
+    guide: object = None
+    pag_scale: float = 0.0
+    pag_layers: object = "mid"
+    regions: object = None
+    region_layers: object = "all"
+    freeu: object = None
+    cfg: object = None
+
+    REFUSED = {
+        ("guide", "pag"): "guide= together with pag_scale != 0: the perturbed rows' attention kernel (mdm_attn_cross_addv) "
+                          "has no backward, so the guide's input gradient cannot pass it",
+        ("guide", "regions"): "guide= together with regions=: the biased cross-attention kernel (mdm_attn_cross_bias) has "
+                              "no backward, so the guide's input gradient cannot pass it",
+        ("guide", "freeu"): "guide= together with freeu=: the fused concat (mdm_freeu_apply) has no backward, so the "
+                            "guide's input gradient cannot pass it",
+        ("guide", "cfg"): "guide= together with cfg=: the guide seeds the two halves of the doubled batch with the weights "
+                          "of the plain combine (w and 1 - w); the projected / rescaled combine depends on per-sample "
+                          "statistics of both predictions, and its Jacobian is not implemented",
+        ("pag", "cfg"): "pag_scale != 0 together with cfg=: mdm_pag_combine adds the perturbed-attention term to the plain "
+                        "combine; projecting, capping and rescaling an update of three predictions is not implemented",
+    }
+
+    @classmethod
+    def pop(cls, keywords):
+        """takes the options' names out of a dict of keywords -> the object (unchecked)"""
+        return cls(**{f.name: keywords.pop(f.name) for f in fields(cls) if f.name in keywords})
+
+    def check(self):
+        """every type and range check, and the pairs of ``REFUSED``; several things wrong: guide, pag, regions, freeu, cfg"""
+        on = dict(guide=self.guide is not None, pag=self.pag_scale != 0, regions=self.regions is not None,
+                  freeu=self.freeu is not None, cfg=self.cfg is not None)
+
+        def refuse(a, b):
+            if on[a] and on[b]:
+                raise NotImplementedError(self.REFUSED[a, b])
+
+        if on["guide"] and not isinstance(self.guide, LossGuide):
+            raise TypeError("guide must be an mdm_hip.LossGuide (got %r)" % (type(self.guide).__name__,))
+        if self.pag_scale < 0:
+            raise ValueError("pag_scale must be >= 0 (got %r); 0 = no perturbed-attention guidance" % (self.pag_scale,))
+        refuse("guide", "pag")
+        refuse("guide", "regions")
+        if on["regions"] and not callable(getattr(self.regions, "rows_for", None)):
+            raise ValueError("regions = %r (wanted a mdm_hip.RegionPrompts)" % (self.regions,))
+        refuse("guide", "freeu")
+        if on["freeu"] and not isinstance(self.freeu, _freeu.FreeU):
+            raise ValueError("freeu = %r (wanted a mdm_hip.FreeU)" % (self.freeu,))
+        if on["cfg"]:
+            if not isinstance(self.cfg, _guidance.CFG):
+                raise ValueError("cfg = %r (wanted a mdm_hip.CFG)" % (self.cfg,))
+            self.cfg.validate()
+        refuse("guide", "cfg")
+        refuse("pag", "cfg")
+        return self
+
+    def blocks(self, guidance_scale):
+        """-> (unconditional block present, perturbed block present) of the model batch [uncond | cond | perturbed]; the
+        conditional block always is, so the rows are 1 + their sum times the images"""
+        return guidance_scale != 1, self.pag_scale != 0
+
+    def cfg_at(self, guidance_scale):
+        """the ``CFG`` that acts at this guidance scale: None at 1, where there is nothing to combine"""
+        return self.cfg if guidance_scale != 1 else None
+
+    def switches(self, model, guidance_scale, B, device=None, names=None, bias=None):
+        """-> the context manager of one denoiser call over ``B`` images: the model switches that are on -- perturbed rows,
+        region bias, FreeU -- as ONE ``unet.switched``.  They touch disjoint attributes, so there is no order among them to
+        get right.  A captured graph body passes the names it resolved (``layer_names``) and its ``StaticBias``; the eager
+        samplers pass neither."""
+        if self.pag_scale == 0 and self.regions is None and self.freeu is None:
+            return _UNCHANGED
+        vision_model = getattr(model, "vision_model", model)
+        pag_layers, region_layers = (self.pag_layers, self.region_layers) if names is None else names
+        on = []
+        if self.pag_scale != 0:
+            on.append(pag.perturbed(vision_model, pag_layers, rows=B))
+        if self.regions is not None:
+            if bias is None:
+                if self.regions.rows != B:
+                    raise ValueError("regions over %d rows for a batch of %d images" % (self.regions.rows, B))
+                bias = self.regions.rows_for(*self.blocks(guidance_scale), device)
+            on.append(_regions.applied(vision_model, bias, region_layers))
+        if self.freeu is not None:
+            on.append(_freeu.applied(vision_model, self.freeu))
+        return switched(s for one in on for s in one.settings)
+
+    def layer_names(self, vision_model):
+        """-> (perturbed layers, biased layers) as tuples of module names: hashable; () where the option is off"""
+        return (pag.layer_names(vision_model, self.pag_layers) if self.pag_scale != 0 else (),
+                _regions.layer_names(vision_model, self.region_layers) if self.regions is not None else ())
+
+    def graph_key(self, vision_model, guidance_scale, names):
+        """the options' part of a ``GraphedSampler`` key, ``names`` being ``layer_names`` of the model: one component per
+        option that is on -- calls that differ in nothing else share a captured graph"""
+        key = ()
+        if self.pag_scale != 0:
+            key += (("pag", float(self.pag_scale), names[0]),)
+        if self.regions is not None:
+            key += (("regions", self.regions.S, self.regions.ld, names[1]),)
+        if self.freeu is not None:
+            key += (_freeu.graph_key(vision_model, self.freeu),)
+        if self.cfg_at(guidance_scale) is not None:
+            key += (self.cfg.key(),)
+        return key
+
+
+_UNCHANGED = contextlib.nullcontext()   # no switch on; the caller's grad mode left alone (stateless: one serves every use)
 
 
 class _frozen_parameters:
@@ -678,32 +785,34 @@ class Sampler(nn.Module):
 
     def forward_model(self, model, x_t, t, lm_outputs, lm_mask, micros={}, guidance_scale=1):
         """classifier-free guidance doubles the batch: [uncond | cond] (:435-459)."""
-        (pc,), (pu,), extras = self._forward_model_raw(model, [x_t], t, lm_outputs, lm_mask, micros, guidance_scale)
+        (pc,), (pu,), extras, _ = self._forward_model_raw(model, [x_t], t, lm_outputs, lm_mask, micros, guidance_scale)
         return (pc if pu is None else pu + guidance_scale * (pc - pu)), extras
 
+    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, opts=SampleOptions()):
+        """The one denoiser call of a step.  ``x_t``: the list of scales -> (conditional predictions, unconditional
+        predictions or Nones, extras, perturbed predictions or None), one entry per scale: the guidance combine itself is
+        folded into the step kernel.  The model runs once, on [uncond | cond | perturbed] -- the blocks ``opts.blocks``
+        names, the perturbed one with the conditional rows' conditioning (``pag_rows``) -- under ``opts.switches``."""
+        uncond, pert = opts.blocks(guidance_scale)
+        B = x_t[0].shape[0]
+        if uncond or pert:
+            assert B * (1 + uncond) == lm_outputs.shape[0]
+        if pert:
+            lm_outputs, lm_mask, micros = pag_rows(B, lm_outputs, lm_mask, micros)
+        reps = 1 + uncond + pert
+        xin, tin = repeat_rows(x_t, t, reps)
+        with opts.switches(model, guidance_scale, B, x_t[0].device):
+            preds, extras = self._call_model(model, xin, tin, lm_outputs, lm_mask, micros)
+        if extras is not None and reps > 1:
+            extras = extras.chunk(reps)[int(uncond)]
+        pcs, pus, pps = split_rows(preds, uncond, pert)
+        return pcs, pus, extras, pps
+
     # ---- what differs between one scale and several: NestedSampler overrides these ----------------------------
-    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, pag_scale=0.0,
-                           pag_layers="mid"):
-        """``x_t``: the list of scales -> (conditional predictions, unconditional predictions or Nones, extras), one entry per
-        scale: the guidance combine itself is folded into the step kernel.  ``pag_scale != 0``: the batch is
-        [uncond | cond | perturbed] ([cond | perturbed] without classifier-free guidance; ``pag_rows``), the model runs once
-        under ``pag.perturbed(..., rows=B)`` and a fourth item, the perturbed predictions, is returned."""
-        if pag_scale != 0:
-            B = x_t[0].shape[0]
-            reps = 3 if guidance_scale != 1 else 2
-            assert B * (reps - 1) == lm_outputs.shape[0]
-            cond, mask, mic = pag_rows(B, lm_outputs, lm_mask, micros)
-            with pag.perturbed(getattr(model, "vision_model", model), pag_layers, rows=B):
-                pred, extras = model(torch.cat([x_t[0]] * reps), torch.cat([t] * reps), cond, mask, micros=mic)
-            parts = pred.chunk(reps)
-            return [parts[-2]], [parts[0] if reps == 3 else None], extras.chunk(reps)[-2], [parts[-1]]
-        if guidance_scale != 1:
-            assert x_t[0].shape[0] * 2 == lm_outputs.shape[0]
-            pred, extras = model(torch.cat([x_t[0]] * 2), torch.cat([t, t]), lm_outputs, lm_mask, micros=micros)
-            pu, pc = pred.chunk(2)
-            return [pc], [pu], extras.chunk(2)[1]
-        pred, extras = model(x_t[0], t, lm_outputs, lm_mask, micros)
-        return [pred], [None], extras
+    def _call_model(self, model, xs, t, lm_outputs, lm_mask, micros):
+        """the model on the list of scales ``xs`` -> (list of predictions, extras)"""
+        pred, extras = model(xs[0], t, lm_outputs, lm_mask, micros)
+        return [pred], extras
 
     def _to_scales(self, model, x_t):
         """what ``get_xt_minus_1`` is given -> the list of scales, hi -> lo"""
@@ -732,34 +841,24 @@ class Sampler(nn.Module):
     # ---- one iteration: denoiser, then the update of every scale -----------------------------------------------
     def get_xt_minus_1(self, model, time_step, x_t, lm_outputs, lm_mask, micros={}, time_step_last=None,
                        guidance_scale=1, ddim_eta=None, return_details=False, solver=None, solver_state=None,
-                       second_order=False, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
-                       freeu=None, cfg=None):
-        """``cfg``: a ``mdm_hip.CFG`` (see ``_sample``) -- with ``guidance_scale != 1`` the step gets the projected / rescaled
-        combine of the two predictions; the momentum history lives in ``solver_state["cfg_run"]`` (one tensor per scale,
-        absent until the first guided step), so without a ``solver_state`` every call starts without history.
-        ``freeu``: a ``mdm_hip.FreeU`` (see ``_sample``), switched on around the denoiser call below, nowhere else.
-        ``pag_scale`` / ``pag_layers``: perturbed-attention guidance (see ``_sample``).  ``regions`` / ``region_layers``:
-        regional prompts and token weights (see ``_sample``): switched on around the denoiser call below, nowhere else.
-        ``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
+                       second_order=False, **options):
+        """``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
         top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
         the caller's dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
-        ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``guide``: a
-        ``LossGuide`` -- the model runs on leaf x_t with grad enabled, the step itself unchanged under no_grad, and the
-        guide's correction is applied to its x_s; its loss sees the top scale."""
+        ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``options``: the keywords
+        of ``SampleOptions`` (``guide``, ``pag_scale``, ``pag_layers``, ``regions``, ``region_layers``, ``freeu``, ``cfg``),
+        checked here.  The momentum history of ``cfg`` lives in ``solver_state["cfg_run"]`` (one tensor per scale, absent
+        until the first guided step), so without a ``solver_state`` every call starts without history."""
         _check_solver(solver, ddim_eta)
-        _check_guide(guide)
-        _check_pag(pag_scale, guide)
-        _check_regions(regions, guide)
-        _check_freeu(freeu, guide)
-        _check_cfg(cfg, guide, pag_scale)
+        return self._step(model, time_step, x_t, lm_outputs, lm_mask, micros, SampleOptions(**options).check(),
+                          time_step_last, guidance_scale, ddim_eta, return_details, solver, solver_state, second_order)
+
+    def _step(self, model, time_step, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=None, guidance_scale=1,
+              ddim_eta=None, return_details=False, solver=None, solver_state=None, second_order=False):
+        """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked once.
+        Denoiser, update of every scale, then the guide's correction if there is one: with a guide the model runs on leaf
+        x_t with grad enabled and the update under no_grad on detached tensors; without, in the caller's grad mode."""
         x_t = self._to_scales(model, x_t)
-        biased = contextlib.nullcontext()
-        scaled = contextlib.nullcontext() if freeu is None else _freeu.applied(getattr(model, "vision_model", model), freeu)
-        if regions is not None:
-            if regions.rows != x_t[0].shape[0]:
-                raise ValueError("regions over %d rows for a batch of %d images" % (regions.rows, x_t[0].shape[0]))
-            biased = _regions.applied(getattr(model, "vision_model", model),
-                                      regions.rows_for(guidance_scale != 1, pag_scale != 0, x_t[0].device), region_layers)
         ones = torch.ones(x_t[0].shape[0], dtype=torch.long, device=self.gammas.device)
         last = time_step - 1 if time_step_last is None else time_step_last
         t = ones * time_step
@@ -771,26 +870,23 @@ class Sampler(nn.Module):
         step_kw = dict(guidance_scale=guidance_scale, ddim_eta=ddim_eta, solver=solver, second_order=second_order,
                        g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
                        need_noise=solver is None and bool(self._noisy_step(time_step, last)))
-        if cfg is not None and guidance_scale != 1:
-            step_kw.update(cfg=cfg, cfg_state=st, cfg_on=cfg.on(time_step, self.n_steps))
-        if pag_scale != 0:
-            with biased, scaled:
-                pcs, pus, _, pps = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
-                                                           pag_scale, pag_layers)
-            x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, pps=pps, pag_scale=pag_scale, **step_kw)
-        elif guide is None:
-            with biased, scaled:
-                pcs, pus, _ = self._forward_model_raw(model, x_t, t - 1, lm_outputs, lm_mask, micros, guidance_scale)  # model sees t-1 (:415)
-            x0, x_s = self._step_scales(x_t, pcs, pus, g_t, g_s, image_scales, **step_kw)
-        else:
+        if opts.cfg is not None and guidance_scale != 1:
+            step_kw.update(cfg_state=st, cfg_on=opts.cfg.on(time_step, self.n_steps))
+        guide = opts.guide
+        x_in, grad, no_grad, thr = x_t, _UNCHANGED, _UNCHANGED, None
+        if guide is not None:
             x_in = [x.detach().requires_grad_(True) for x in x_t]
-            with torch.enable_grad():
-                pcs, pus, _ = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale)
+            grad, no_grad = torch.enable_grad(), torch.no_grad()
             thr = []   # one entry per scale, hi -> lo
-            with torch.no_grad():   # the step itself: unchanged, on detached tensors
-                x0, x_s = self._step_scales([x.detach() for x in x_in], [p.detach() for p in pcs],
-                                            [None if p is None else p.detach() for p in pus], g_t, g_s, image_scales,
-                                            thr_out=thr, **step_kw)
+        with grad:
+            pcs, pus, _, pps = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
+                                                       opts)   # model sees t-1 (:415)
+        outs = (x_in, pcs, pus)
+        if guide is not None:   # the update itself: unchanged, on detached tensors
+            outs = ([None if v is None else v.detach() for v in vs] for vs in outs)
+        with no_grad:
+            x0, x_s = self._step_scales(*outs, g_t, g_s, image_scales, opts, pps=pps, thr_out=thr, **step_kw)
+        if guide is not None:
             x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0], image_scales[0], guidance_scale,
                                      thr[0])
         if solver is not None:
@@ -799,19 +895,20 @@ class Sampler(nn.Module):
             return self._from_scales(x_s)
         return self._from_scales(x0), self._from_scales(x_s), (g_t[-1], g_s[-1])
 
-    def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, need_noise=False, guidance_scale=1, ddim_eta=None,
-                     solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, rng=None, noise_gate=None,
-                     x0_out=None, pps=None, pag_scale=0.0, cfg=None, cfg_state=None, cfg_on=True, cfg_gates=None):
+    def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, opts, need_noise=False, guidance_scale=1, ddim_eta=None,
+                     solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, pps=None, rng=None,
+                     noise_gate=None, x0_out=None, cfg_state=None, cfg_on=True, cfg_gates=None):
         """The update of every scale behind the denoiser call -> (x0 list, x_s list).  All lists hi -> lo, one entry per
         scale; ``g_prev`` / ``x0_prev``: the history of ``solver="dpmpp_2m"``, or None.  This is the one reverse step of the
         eager samplers and of ``GraphedSampler``, whose captured graph passes ``rng``, ``noise_gate``, a device
-        ``second_order`` gate and ``x0_out`` through to the step kernels.  ``pps`` with ``pag_scale != 0``: the perturbed
-        predictions of perturbed-attention guidance -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU tensors:
-        ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1.  ``cfg`` (a
-        ``mdm_hip.CFG``) with ``guidance_scale != 1`` does the same with the projected / rescaled combine (``_cfg_scales``)."""
+        ``second_order`` gate, ``x0_out`` and the cfg state and gates through to the kernels.  ``pps`` with
+        ``opts.pag_scale != 0``: the perturbed predictions -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU
+        tensors: ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1.
+        ``opts.cfg`` with ``guidance_scale != 1`` does the same with the projected / rescaled combine (``_cfg_scales``)."""
         n = len(x_t)
         g_prev, x0_prev, x0_out = (v or [None] * n for v in (g_prev, x0_prev, x0_out))
-        if cfg is not None and guidance_scale != 1:
+        cfg, pag_scale = opts.cfg_at(guidance_scale), opts.pag_scale
+        if cfg is not None:
             pcs = self._cfg_scales(cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, cfg_state, cfg_on, cfg_gates)
             pus, guidance_scale = [None] * n, 1
         if pps is not None and pag_scale != 0:
@@ -874,12 +971,7 @@ class Sampler(nn.Module):
         (``resample_steps=True, num_inference_steps=20..50``)."""
         _check_solver(kwargs.get("solver"), kwargs.get("ddim_eta"))   # here, not at the generator's first next()
         _check_known(kwargs.get("known_images"), kwargs.get("resample", 1), kwargs.get("solver"))
-        guide = kwargs.get("guide")
-        _check_guide(guide)
-        _check_pag(kwargs.get("pag_scale", 0.0), guide)
-        _check_regions(kwargs.get("regions"), guide)
-        _check_freeu(kwargs.get("freeu"), guide)
-        _check_cfg(kwargs.get("cfg"), guide, kwargs.get("pag_scale", 0.0))
+        guide = SampleOptions.pop(dict(kwargs)).check().guide   # the one check of the call: _sample only builds
         gen = self._sample(*args, **kwargs)
         if guide is None:
             return gen if kwargs.get("yield_output", False) else next(gen)
@@ -914,43 +1006,9 @@ class Sampler(nn.Module):
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-                known_noise_fn=None, guide=None, pag_scale=0.0, pag_layers="mid", regions=None, region_layers="all",
-                freeu=None, cfg=None, **post_args):
-        """``cfg = CFG(eta=1, norm_threshold=0, momentum=0, rescale=0, interval=None)`` with ``guidance_scale != 1``: the
-        classifier-free guidance combine  p_u + w (p_c - p_u)  is replaced by the projected / rescaled one of
-        ``mdm_hip/guidance.py`` -- adaptive projected guidance (Sadat et al. 2025: the part of the update parallel to the
-        conditional x0 scaled by ``eta``, its RMS in image units capped at ``norm_threshold`` -- the paper's radius over
-        sqrt(C H W), so one value serves every scale --, a ``momentum`` across steps), the std rescale (Lin et al. 2024,
-        ``rescale`` = phi) and the guidance interval (Kynkaanniemi et al. 2024: outside ``interval``, in fractions of
-        ``num_diffusion_steps``, the step takes the conditional prediction).  One combine per scale in front of the unchanged
-        step (GPU tensors: ``ops.cfg_combine``, two launches; CPU tensors: ``guidance.cfg_combine``), which then gets no
-        unconditional prediction and guidance 1.  The momentum history, one buffer per scale, starts empty with every
-        trajectory, wherever it starts, and every denoiser call updates it, the repeats of ``resample`` included.  Only
-        the prediction handed to the update changes, so it composes with ``ddim_eta``, ``solver=``, ``known_images=``, a late
-        start, ``regions``, ``freeu``, LoRA, MXFP8 and every threshold function; not with ``guide=`` or ``pag_scale != 0``
-        (NotImplementedError).  ``cfg=None``, or ``guidance_scale == 1``, leaves every step as it is.
-        ``freeu = FreeU(b=(b1, b2), s=(s1, s2), structure=False, levels="deepest2")``: FreeU (Si et al. 2024) -- in the up
-        blocks that ``freeu.select`` names, the skip concat multiplies the first half of the backbone channels by b (v2,
-        ``structure=True``: by 1 + (b - 1) x the min-max normalised channel mean) and the 2 x 2 lowest spatial frequencies
-        of the skip by s, for every row of the model batch alike.  No extra denoiser call.  The switch is held around each
-        step's denoiser call only, never across a ``yield``.  Composes with ``solver=``, ``known_images=``, a late start,
-        ``pag_scale``, ``regions``, LoRA and MXFP8; not with ``guide=`` (NotImplementedError).  ``freeu=None`` leaves every
-        step as it is.
-        ``regions = rp`` (a ``mdm_hip.RegionPrompts`` over the conditional rows of ``lm_outputs``): in the
-        ``SelfAttention`` layers with text keys that ``region_layers`` selects (the vocabulary of ``pag.select``; default
-        every one) the text logits get rp's bias -- log(token weight) + log(region coverage of the query position); 0 in the
-        unconditional rows; the perturbed block of ``pag_scale`` repeats the conditional rows'.  The switch is held around
-        each step's denoiser call only, never across a ``yield``.  Composes with ``solver=``, ``known_images=``, a late
-        start, ``pag_scale``, LoRA and MXFP8; not with ``guide=`` (NotImplementedError).  ``regions=None`` leaves every step
-        as it is.
-        ``pag_scale = s > 0``: perturbed-attention guidance (Ahn et al. 2024).  Every denoiser call carries B more rows,
-        [uncond | cond | perturbed] (``lm_outputs`` stays [uncond | cond], or [cond] at ``guidance_scale == 1``), in which the
-        ``SelfAttention`` layers that ``pag_layers`` selects (``pag.select``: "mid", "deepest", "all", names, a predicate)
-        attend to themselves only, and the step gets  p_u + w (p_c - p_u) + s (p_c - p_hat).  Only the prediction handed to
-        the update changes, so it composes with ``solver=``, ``known_images=`` and a late start; not with ``guide=``
-        (NotImplementedError).  ``pag_scale=0`` leaves every step as it is.
-        ``guide``: a ``LossGuide`` -- loss-guided sampling; per step: the update, then the guide's correction, then the
-        known-region blend.  ``guide=None`` leaves every step as it is.
+                known_noise_fn=None, **post_args):
+        """``guide``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers``, ``freeu``, ``cfg``: see ``SampleOptions``;
+        they are taken out of the keywords here (``sample`` has checked them), the rest goes to ``_postprocess``.
         ``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
         whichever update made it, every scale's x_s is replaced where the mask is 1 by the known image diffused to that
         scale's target gamma (``known_blend``; the last step goes to gamma = 1: the known region of the result IS the known
@@ -961,11 +1019,7 @@ class Sampler(nn.Module):
         assert not (yield_output and return_sequence)
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
-        _check_guide(guide)
-        _check_pag(pag_scale, guide)
-        _check_regions(regions, guide)
-        _check_freeu(freeu, guide)
-        _check_cfg(cfg, guide, pag_scale)
+        opts = SampleOptions.pop(post_args)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -985,11 +1039,10 @@ class Sampler(nn.Module):
             second = solver is not None and bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)
             reps = resample if i < len(steps) - 2 else 1
             for rep in range(reps):
-                x0, x_t, extra = self.get_xt_minus_1(
-                    model, ts, x_t, lm_outputs, lm_mask, micros, time_step_last=steps[i + 1] if resample_steps else None,
+                x0, x_t, extra = self._step(
+                    model, ts, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
-                    solver_state=history, second_order=second, guide=guide, pag_scale=pag_scale, pag_layers=pag_layers,
-                    regions=regions, region_layers=region_layers, freeu=freeu, cfg=cfg)
+                    solver_state=history, second_order=second)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
@@ -1056,28 +1109,12 @@ class NestedSampler(Sampler):
                 for x, s, e, gi, gl in zip(x0, scales, eps, g, g_last)]
 
     def forward_model(self, model, x_t, t, lm_outputs, lm_mask, micros={}, guidance_scale=1):
-        pcs, pus, _ = self._forward_model_raw(model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
+        pcs, pus, _, _ = self._forward_model_raw(model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
         return [pc if pu is None else pu + guidance_scale * (pc - pu) for pc, pu in zip(pcs, pus)]
 
-    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, pag_scale=0.0,
-                           pag_layers="mid"):
-        """(:777-790); the nested model returns no extras"""
-        if pag_scale != 0:   # as Sampler._forward_model_raw, every scale repeated
-            B = x_t[0].shape[0]
-            reps = 3 if guidance_scale != 1 else 2
-            assert B * (reps - 1) == lm_outputs.shape[0]
-            cond, mask, mic = pag_rows(B, lm_outputs, lm_mask, micros)
-            with pag.perturbed(getattr(model, "vision_model", model), pag_layers, rows=B):
-                p_t = model([torch.cat([x] * reps) for x in x_t], torch.cat([t] * reps), cond, mask, mic)
-            parts = [p.chunk(reps) for p in p_t]
-            return ([p[-2] for p in parts], [p[0] if reps == 3 else None for p in parts], None, [p[-1] for p in parts])
-        if guidance_scale != 1:
-            assert x_t[0].shape[0] * 2 == lm_outputs.shape[0]
-            p_t = model([torch.cat([x] * 2) for x in x_t], torch.cat([t] * 2), lm_outputs, lm_mask, micros)
-            halves = [p.chunk(2) for p in p_t]
-            return [h[1] for h in halves], [h[0] for h in halves], None
-        p_t = model(x_t, t, lm_outputs, lm_mask, micros)
-        return list(p_t), [None] * len(p_t), None
+    def _call_model(self, model, xs, t, lm_outputs, lm_mask, micros):
+        """(:777-790); the nested model takes and returns lists, and no extras"""
+        return list(model(xs, t, lm_outputs, lm_mask, micros)), None
 
     def _postprocess(self, x_t, x0=None, extra=None, yield_full=False, clip=False, output_inner=False, **unused):
         scales = [1 if self._config.schedule_shifted else x.size(-1) / x_t[-1].size(-1) for x in x_t]

@@ -394,6 +394,51 @@ class ResNetBlock(nn.Module):
 
 
 # --------------------------------------------------------------------------------------
+# The sampling switches: the class attributes above that an instance attribute overrides for the duration of a ``with``
+# block (``pag.perturbed``: _pag_rows; ``regions.applied``: _cross_bias; ``freeu.applied``: _freeu, _freeu_name).
+# --------------------------------------------------------------------------------------
+SWITCHES = ("_pag_rows", "_cross_bias", "_freeu")   # what changes the launches of a forward (_freeu_name only names a block)
+
+
+class switched:
+    """``with switched([(module, {attribute: value, ...}), ...]):`` -- inside, every module has the given instance
+    attributes; on exit (also by an exception) it has what it had before: the outer value where the block is nested in
+    another one, no instance attribute at all -- the class attribute again -- where it had none."""
+
+    _UNSET = object()
+
+    def __init__(self, settings):
+        self.settings = list(settings)
+
+    def __enter__(self):
+        self.saved = [{a: m.__dict__.get(a, self._UNSET) for a in values} for m, values in self.settings]
+        for m, values in self.settings:
+            for a, v in values.items():
+                setattr(m, a, v)
+        return self
+
+    def __exit__(self, *exc):
+        for (m, _), before in zip(self.settings, self.saved):
+            for a, v in before.items():
+                if v is self._UNSET:
+                    m.__dict__.pop(a, None)
+                else:
+                    setattr(m, a, v)
+        return False
+
+
+def switchable(model):
+    """every module that carries a sampling switch, in ``modules()`` order"""
+    return [m for m in model.modules() if isinstance(m, (SelfAttention, ResNetBlock))]
+
+
+def switch_state(modules):
+    """{switch: its value on every module of ``modules`` that has it, in order} -- what a cache of captured forwards
+    (``GraphedDenoiser``) keys on beside the shapes"""
+    return {a: tuple(getattr(m, a) for m in modules if hasattr(type(m), a)) for a in SWITCHES}
+
+
+# --------------------------------------------------------------------------------------
 # LM head: self-attention blocks over the text states (reference unet.py:316-387, 425-446; ``num_lm_head_layers`` > 0).
 # Off the denoiser's hot path -- B x 32 tokens, once per sampling run / train step -- and no shipped config enables it:
 # LayerNorm and the linear layers are this package's kernels, the S x S token attention and the GELU are torch ops on the

@@ -308,6 +308,7 @@ def test_refusals():
 
     import mdm_hip
     from mdm_hip.graph import GraphedSampler
+    from mdm_hip.samplers import SampleOptions
 
     pipe = _pipe(False)
     smp, model = pipe.sampler, pipe.get_model()
@@ -328,8 +329,9 @@ def test_refusals():
     c.rescale = 2.0   # changed after construction: caught where it is used
     with pytest.raises(ValueError, match="rescale"):
         smp.sample(model, xs, lm, mask, {}, cfg=c, **kw)
+    # the keyword reaches GraphedSampler.sample through its **options: the fields of SampleOptions, with their defaults
     sig = inspect.signature(GraphedSampler.sample).parameters
-    assert sig["cfg"].default is None
+    assert sig["options"].kind is inspect.Parameter.VAR_KEYWORD and SampleOptions().cfg is None
     with pytest.raises(NotImplementedError, match="perturbed-attention"):
         GraphedSampler(pipe).sample(B, {"lm_outputs": lm, "lm_mask": mask}, 16, torch.device("cpu"), guidance_scale=W,
                                     pag_scale=1.0, cfg=mdm_hip.CFG())

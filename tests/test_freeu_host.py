@@ -231,6 +231,7 @@ def test_refusals_of_the_samplers_and_the_op():
 
     from mdm_hip import LossGuide, _lib, ops
     from mdm_hip.graph import GraphedSampler
+    from mdm_hip.samplers import SampleOptions
 
     smp, stub = _sampler(), FC.RecordingStub()
     x, lm, mask = _inputs(2.0)
@@ -244,7 +245,9 @@ def test_refusals_of_the_samplers_and_the_op():
     with pytest.raises(ValueError, match="wanted a mdm_hip.FreeU"):
         smp.sample(stub, x, lm, mask, {}, freeu=(1.4, 0.2), **kw)
     assert not stub.calls
-    assert inspect.signature(GraphedSampler.sample).parameters["freeu"].default is None
+    # the keyword reaches GraphedSampler.sample through its **options: the fields of SampleOptions, with their defaults
+    sig = inspect.signature(GraphedSampler.sample).parameters
+    assert sig["options"].kind is inspect.Parameter.VAR_KEYWORD and SampleOptions().freeu is None
     h, r = torch.randn(1, 4, 4, 16), torch.randn(1, 4, 4, 8)
     with pytest.raises(_lib.MdmHipError, match="no CPU fallback"):
         ops.concat_freeu(h, r, 1.4, 0.2, False)

@@ -241,8 +241,12 @@ def test_refusals():
         smp.sample(stub, x, lm, mask, micros, pag_scale=1.0, pag_layers="deepest", **kw)
     import inspect
 
+    from mdm_hip.samplers import SampleOptions
+
+    # the keywords reach GraphedSampler.sample through its **options: the fields of SampleOptions, with their defaults
     sig = inspect.signature(GraphedSampler.sample).parameters
-    assert sig["pag_scale"].default == 0.0 and sig["pag_layers"].default == "mid"
+    assert sig["options"].kind is inspect.Parameter.VAR_KEYWORD
+    assert SampleOptions().pag_scale == 0.0 and SampleOptions().pag_layers == "mid"
 
 
 def test_new_entries_are_declared_and_exported():

@@ -313,11 +313,12 @@ def test_refusals():
     with pytest.raises(ValueError, match="selects no attention layer"):
         smp.sample(stub, x, lm, mask, micros, regions=rp, region_layers=lambda n: False, **kw)
     assert not stub.calls
-    sig = inspect.signature(GraphedSampler.sample).parameters
-    assert sig["regions"].default is None and sig["region_layers"].default == "all"
-    for fn in (smp._sample, smp.get_xt_minus_1):
-        sig = inspect.signature(fn).parameters
-        assert sig["regions"].default is None and sig["region_layers"].default == "all"
+    # the keywords reach these through their ** keywords: the fields of SampleOptions, with their defaults
+    from mdm_hip.samplers import SampleOptions
+
+    for fn, name in ((GraphedSampler.sample, "options"), (smp._sample, "post_args"), (smp.get_xt_minus_1, "options")):
+        assert inspect.signature(fn).parameters[name].kind is inspect.Parameter.VAR_KEYWORD
+    assert SampleOptions().regions is None and SampleOptions().region_layers == "all"
     assert "eager" in GraphedDenoiser.__doc__.lower()
 
 
