@@ -87,6 +87,27 @@ int mdm_cfg_combine(const float* x_t, const float* pred, const float* pred_uncon
                     const float* w_gate, const void* ws, size_t ws_bytes, float* out, float guidance, float eta,
                     float norm_threshold, float rescale, float image_scale, int B, size_t chw, int pred_type, void* stream);
 
+/* Tiled sampling (MultiDiffusion, Bar-Tal et al., ICML 2023): the denoiser of a step runs on overlapping windows of a canvas
+ * larger than its training size, and the windows' predictions are averaged where they overlap.  fp32 NCHW tensors.
+ * Geometry, per axis (canvas L, window win, stride s): n = ceil((L - win) / s) + 1 windows at offsets min(i s, L - win) --
+ * the last one is clamped to the border.  ny x nx windows, window k = i nx + j, T = ny nx.
+ * mdm_tiles_gather: x [B, C, H, W] -> out [reps, B, T, C, h, w]; row (rep B + b) T + k is window k of image b, the same for
+ *   every rep (the blocks [uncond | cond | perturbed] of the model batch).  Every element is a copy, bit for bit.
+ * mdm_tiles_merge: p [R, T, C, h, w] -> out [R, C, H, W],
+ *     out[r, c, y, x] = sum_k wt_k p[r, k, c, y - oy_k, x - ox_k] / sum_k wt_k     over the windows k that contain (y, x),
+ *   accumulated in fp32 in window order (i ascending, then j).  blend 0 (uniform): wt = 1.  blend 1 (ramp): at position
+ *   (a, b) of the window wt = min(a + 1, h - a) min(b + 1, w - b), a tent; needs ceil(h / 2) ceil(w / 2) <= 2^24.  A pixel
+ *   under exactly one window gets that window's value bit for bit.  out must not alias p.  R is the whole model batch.
+ * Both: 1 <= h <= H, 1 <= w <= W, 1 <= sy <= h, 1 <= sx <= w (so every pixel lies under a window), reps >= 1, B, R, T <=
+ * 65535, C H W < 2^31.  The windows over a pixel are found by arithmetic on (y, x, h, w, sy, sx, H, W): no offset table.
+ * 16-byte accesses where w, W, sx and W - w are multiples of 4 and both tensors are 16-byte aligned, 4-byte ones otherwise.
+ * No allocation, no workspace, no host sync, no atomics: capturable, two runs are bit-identical, and a row's bits do not
+ * depend on the rows beside it.  Invalid arguments: a negative status, nothing launched.  Forward only. */
+int mdm_tiles_gather(const float* x, float* out, int B, int C, int H, int W, int h, int w, int sy, int sx, int reps,
+                     void* stream);
+int mdm_tiles_merge(const float* p, float* out, int R, int C, int H, int W, int h, int w, int sy, int sx, int blend,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

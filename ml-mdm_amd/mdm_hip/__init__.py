@@ -22,6 +22,8 @@ Layout of the package
   freeu.py        FreeU on the up path's skip concat: FreeU / select / applied (the samplers' freeu)
   guidance.py     projected and rescaled classifier-free guidance (APG, CFG rescale, guidance interval): CFG / cfg_combine
                   (the samplers' cfg)
+  tiling.py       tiled (MultiDiffusion) sampling of canvases larger than the model's window: Tiles / gather / merge (the
+                  samplers' tiles)
 """
 import os as _os
 
@@ -54,8 +56,12 @@ from . import freeu  # noqa: F401,E402
 from .freeu import FreeU  # noqa: F401,E402
 from . import guidance  # noqa: F401,E402
 from .guidance import CFG  # noqa: F401,E402
+from . import tiling  # noqa: F401,E402
+from .tiling import Tiles  # noqa: F401,E402
 
 __all__ = [
+    "tiling",
+    "Tiles",
     "guidance",
     "CFG",
     "freeu",

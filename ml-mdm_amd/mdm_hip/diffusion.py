@@ -140,11 +140,14 @@ class Diffusion(nn.Module):
         return loss, time, x_t, means, tgt, weights
 
     def get_noise(self, num_examples, input_channels, image_side, device):
-        return torch.randn(num_examples, input_channels, image_side, image_side).to(device)  # CPU RNG, as the reference (:177)
+        """``image_side``: an int (a square, as the reference), or (H, W) -- the canvas of tiled sampling"""
+        H, W = image_side if isinstance(image_side, (tuple, list)) else (image_side, image_side)
+        return torch.randn(num_examples, input_channels, H, W).to(device)  # CPU RNG, as the reference (:177)
 
     def sample(self, num_examples, sample, image_side, device, **kwargs):
         """keywords go to the sampler's ``sample`` (``guidance_scale``, ``solver``, ``known_images`` ..., and the options of
-        ``samplers.SampleOptions``)"""
+        ``samplers.SampleOptions``).  ``image_side``: an int, or (H, W) with ``tiles=`` (a nested model's lower-scale start
+        noise follows the canvas)"""
         self.eval()
         noise = self.get_noise(num_examples, self.get_model().input_channels, image_side, device)
         return self.sampler.sample(self.get_model(), noise, sample["lm_outputs"], sample["lm_mask"],

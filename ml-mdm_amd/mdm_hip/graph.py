@@ -21,7 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import ops, regions as _regions
-from .samplers import SampleOptions, _check_known, _check_solver, pag_rows, repeat_rows, split_rows
+from . import tiling as _tiling
+from .samplers import (SampleOptions, _check_known, _check_solver, gather_windows, merge_windows, model_rows, repeat_rows,
+                       split_rows)
 from .unet import switch_state, switchable
 
 
@@ -167,7 +169,11 @@ class GraphedSampler:
         vm = model.vision_model
         dev = xs[0].device
         B = xs[0].shape[0]
-        image_scales = smp._scale_info(model)[1]
+        ratios, image_scales = smp._scale_info(model)
+        # tiles: every block of the model batch holds the T windows of every image (cond, mask and micros came repeated)
+        tiles = opts.tiles
+        canvases = [tuple(x.shape[2:]) for x in xs]
+        T = 1 if tiles is None else tiles.count(*canvases[0])
         (tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump), t_host = self._tables(n_steps, dev, resample)
         idx = torch.zeros(1, dtype=torch.long, device=dev)
         rng = ops.DeviceRng(self._seed, dev)
@@ -212,12 +218,18 @@ class GraphedSampler:
             # the model's batch: [uncond | cond] under classifier-free guidance, + [perturbed] under perturbed-attention
             # guidance (the static conditioning and micros buffers hold that many rows)
             uncond, pert = opts.blocks(guidance)
-            xin, tin = repeat_rows(x_static, times, 1 + uncond + pert)
-            with opts.switches(vm, guidance, B, names=names, bias=bias_s):
+            reps = 1 + uncond + pert
+            if tiles is None:
+                xin, tin = repeat_rows(x_static, times, reps)
+            else:   # one gather per scale in place of the repeat; the merge below hands the step whole canvases
+                xin, tin = gather_windows(x_static, tiles, ratios, reps), _tiling.time_rows(times, T, reps)
+            with opts.switches(vm, guidance, B * T, names=names, bias=bias_s):
                 preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
             preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
                 preds = [torch.tanh(p / out_scale) * out_scale for p in preds]
+            if tiles is not None:
+                preds = merge_windows(preds, tiles, ratios, canvases)
             preds, pus, pps = split_rows(preds, uncond, pert)
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> torch.quantile, a
             # sort + lerp on the device, -> update kernel, all captured).  Every row draws and advances the generator in
@@ -289,6 +301,9 @@ class GraphedSampler:
         replay the same graph, another S or layer set captures anew.
         ``pag_scale`` / ``pag_layers``: the static conditioning and micros buffers carry the perturbed block's rows and one
         combine kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
+        ``tiles``: ``image_side`` may be (H, W).  The static conditioning and micros buffers carry every row once per
+        window, the body gathers the windows in place of the row repeat and merges the predictions in front of the
+        combines and the step (one launch per scale each), and the graph key holds ("tiles", window, stride, blend).
         -> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
         guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
         drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on).
@@ -318,9 +333,9 @@ class GraphedSampler:
         smp = self.sampler
         model = self.pipe.get_model()
         if start_noise is None:
-            x = self.pipe.get_noise(num_examples, model.input_channels, image_side, device)
+            x = self.pipe.get_noise(num_examples, model.input_channels, image_side, device)   # an int, or (H, W)
             # independent noise at every lower resolution (:669-676)
-            xs = [x] + [torch.randn(num_examples, x.shape[1], image_side // r, image_side // r, device=x.device)
+            xs = [x] + [torch.randn(num_examples, x.shape[1], x.shape[2] // r, x.shape[3] // r, device=x.device)
                         for r in smp._scale_info(model)[0][1:]]
         else:
             xs = [t.to(device).float() for t in (start_noise if isinstance(start_noise, (list, tuple)) else [start_noise])]
@@ -336,8 +351,12 @@ class GraphedSampler:
             raise ValueError("regions over %d rows of %d tokens for a batch of %d images with %d tokens"
                              % (regions.rows, regions.S, xs[0].shape[0], cond.shape[1]))
         names = opts.layer_names(model.vision_model)
-        if opts.pag_scale != 0:   # the perturbed block repeats the conditional rows of everything per-row
-            cond, mask, micros = pag_rows(xs[0].shape[0], cond, mask, micros)
+        # the perturbed block repeats the conditional rows of everything per-row; tiles repeat every row once per window
+        T = 1
+        if opts.tiles is not None:
+            T = opts.tiles.check(*xs[0].shape[2:], smp._scale_info(model)[0]).count(*xs[0].shape[2:])
+        if opts.pag_scale != 0 or opts.tiles is not None:
+            cond, mask, micros = model_rows(opts, guidance_scale, xs[0].shape[0], T, cond, mask, micros)
         key = (tuple(tuple(x.shape) for x in xs), tuple(cond.shape), int(num_inference_steps), ddim_eta, float(guidance_scale),
                torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
                ops.fp32_split_enabled(),   # a captured graph keeps the arithmetic it was captured with

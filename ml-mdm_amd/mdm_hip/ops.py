@@ -14,6 +14,7 @@ import weakref
 import torch
 
 from . import _lib
+from . import tiling as _tiling
 
 F32, BF16, F32_SPLIT, F32_SPLIT_W = 0, 1, 2, 3
 
@@ -2738,6 +2739,62 @@ def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1.0, pag_scale=0.0,
     out = torch.empty_like(pred) if out is None else _inplace_img(out, pred, "pag_combine: out")
     _lib.check(_lib.lib().mdm_pag_combine(_p(pred), _p(pu), _p(pp), float(guidance_scale), float(pag_scale), _p(out),
                                           pred.numel(), _stream()), "mdm_pag_combine")
+    return out
+
+
+def _tile_count(H, W, window, stride):
+    (h, w), (sy, sx) = window, stride
+    if not (1 <= h <= H and 1 <= w <= W and 1 <= sy <= h and 1 <= sx <= w):
+        raise _lib.MdmHipError("tiles: window %r, stride %r on a canvas %d x %d (wanted 1 <= stride <= window <= canvas per axis)"
+                               % (tuple(window), tuple(stride), H, W))
+    return _tiling.axis_count(H, h, sy) * _tiling.axis_count(W, w, sx)
+
+
+def _tiles_out(out, shape, device, what):
+    """the output of a tiles kernel: a new fp32 tensor of ``shape``, or the caller's, checked"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != tuple(shape):
+        raise _lib.MdmHipError("%s must be a contiguous fp32 tensor of shape %s" % (what, tuple(shape)))
+    _require_gpu(out)
+    return out.detach()
+
+
+def tiles_gather(x, window, stride, reps=1, out=None):
+    """The windows of tiled sampling (include/mdm_hip_ext.h mdm_tiles_gather) as ONE kernel: x [B, C, H, W] -> the model's
+    rows [reps B T, C, h, w], row (rep B + b) T + k window k of image b -- the ``reps`` blocks of the model batch are
+    written by the same launch.  ``window`` = (h, w), ``stride`` = (sy, sx).  -> out"""
+    x = _img(x)
+    if x.dim() != 4:
+        raise _lib.MdmHipError("tiles_gather: x must be [B, C, H, W] (got %s)" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    (h, w), (sy, sx) = window, stride
+    T = _tile_count(H, W, window, stride)
+    if int(reps) < 1:
+        raise _lib.MdmHipError("tiles_gather: reps must be >= 1 (got %r)" % (reps,))
+    out = _tiles_out(out, (int(reps) * B * T, C, h, w), x.device, "tiles_gather: out")
+    n = float(B * T * C * h * w * 4)
+    _prof_wrap("tiles_gather", n * (1 + int(reps)), lambda: _lib.check(
+        _lib.lib().mdm_tiles_gather(_p(x), _p(out), B, C, H, W, h, w, sy, sx, int(reps), _stream()), "mdm_tiles_gather"),
+        kind="hbm")
+    return out
+
+
+def tiles_merge(p, H, W, window, stride, blend="uniform", out=None):
+    """The weighted mean of the windows' predictions over every canvas pixel (include/mdm_hip_ext.h mdm_tiles_merge) as
+    ONE kernel: p [R T, C, h, w] -> [R, C, H, W], R the whole model batch.  ``blend``: "uniform" | "ramp".  -> out"""
+    p = _img(p)
+    (h, w), (sy, sx) = window, stride
+    T = _tile_count(H, W, window, stride)
+    if p.dim() != 4 or p.shape[0] % T or tuple(p.shape[2:]) != (h, w):
+        raise _lib.MdmHipError("tiles_merge: predictions %s are not rows of %d windows of %d x %d" % (tuple(p.shape), T, h, w))
+    R, C = p.shape[0] // T, p.shape[1]
+    if blend not in _tiling.BLENDS:
+        raise _lib.MdmHipError("tiles_merge: unknown blend %r (known: %s)" % (blend, ", ".join(_tiling.BLENDS)))
+    bl = _tiling.BLENDS.index(blend)
+    out = _tiles_out(out, (R, C, H, W), p.device, "tiles_merge: out")
+    _prof_wrap("tiles_merge", float(p.numel() * 4 + out.numel() * 4), lambda: _lib.check(
+        _lib.lib().mdm_tiles_merge(_p(p), _p(out), R, C, H, W, h, w, sy, sx, bl, _stream()), "mdm_tiles_merge"), kind="hbm")
     return out
 
 

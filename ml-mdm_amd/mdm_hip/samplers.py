@@ -20,10 +20,11 @@ same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.
 ``sample(..., known_images=, known_mask=, resample=, known_seed=)`` holds a region of every trajectory on a given image
 (the replacement method of RePaint, Lugmayr et al. 2022, with its resampling jumps; ``KnownRegion`` ->
 ``ops.sampler_known_blend`` / ``ops.sampler_jump``), and ``Diffusion.partial_diffusion`` starts a trajectory late from a
-noised image (SDEdit, Meng et al. 2022).  Five options act on the denoiser call or on the prediction handed to the update
+noised image (SDEdit, Meng et al. 2022).  Six options act on the denoiser call or on the prediction handed to the update
 and leave the update alone -- loss guidance (``guide``), perturbed-attention guidance (``pag_scale`` / ``pag_layers``), regional
-prompts and token weights (``regions`` / ``region_layers``), FreeU (``freeu``) and projected / rescaled classifier-free
-guidance (``cfg``): ``SampleOptions`` says what each does, holds their checks and is what travels from ``sample`` to the step.
+prompts and token weights (``regions`` / ``region_layers``), FreeU (``freeu``), projected / rescaled classifier-free
+guidance (``cfg``) and tiled sampling of a canvas larger than the model's window (``tiles``): ``SampleOptions`` says what each
+does, holds their checks and is what travels from ``sample`` to the step.
 """
 import contextlib
 import math
@@ -39,6 +40,7 @@ from . import freeu as _freeu
 from . import guidance as _guidance
 from . import ops, pag
 from . import regions as _regions
+from . import tiling as _tiling
 from .unet import switched
 
 
@@ -168,6 +170,41 @@ def split_rows(preds, uncond, pert):
     parts = [p.chunk(1 + uncond + pert) for p in preds]
     return ([p[int(uncond)] for p in parts], [p[0] if uncond else None for p in parts],
             [p[-1] for p in parts] if pert else None)
+
+
+def model_rows(opts, guidance_scale, B, T, lm_outputs, lm_mask, micros):
+    """The conditioning as the model's rows see it, from what ``sample`` was given ([uncond | cond], or [cond]): the
+    perturbed block's rows appended (``pag_rows``), then every row once per window of ``opts.tiles`` (``T`` of them;
+    ``tiling.cond_rows``).  The same for every step of a call.  -> (lm_outputs, lm_mask, micros)"""
+    uncond, pert = opts.blocks(guidance_scale)
+    if uncond or pert:
+        assert B * (1 + uncond) == lm_outputs.shape[0]
+    if pert:
+        lm_outputs, lm_mask, micros = pag_rows(B, lm_outputs, lm_mask, micros)
+    if opts.tiles is not None:
+        lm_outputs, lm_mask, micros = _tiling.cond_rows(T, lm_outputs, lm_mask, micros)
+    return lm_outputs, lm_mask, micros
+
+
+def gather_windows(xs, tiles, ratios, reps):
+    """every scale of ``xs`` (canvases, hi -> lo, ``ratios`` = top side / side) -> the windows of ``tiles`` as rows of the
+    model batch, once per block (``reps``): one ``ops.tiles_gather`` per scale on GPU tensors, ``tiling.gather`` otherwise"""
+    out = []
+    for x, r in zip(xs, ratios):
+        tl = tiles.at(r)
+        out.append(ops.tiles_gather(x.float(), tl.window, tl.stride, reps) if x.is_cuda else _tiling.gather(x, tl, reps))
+    return out
+
+
+def merge_windows(preds, tiles, ratios, canvases):
+    """the model's predictions on such rows -> whole-canvas predictions [reps B, C, H, W] per scale (``canvases``: the
+    (H, W) of every scale): one ``ops.tiles_merge`` per scale on GPU tensors, ``tiling.merge`` otherwise"""
+    out = []
+    for p, r, (H, W) in zip(preds, ratios, canvases):
+        tl = tiles.at(r)
+        out.append(ops.tiles_merge(p.float(), H, W, tl.window, tl.stride, tl.blend) if p.is_cuda
+                   else _tiling.merge(p, tl, H, W))
+    return out
 
 
 def known_blend(x, known, mask, g, inv_scale=1.0, noise=None):
@@ -367,11 +404,22 @@ class SampleOptions:
     unconditional prediction and guidance 1.  The momentum history, one buffer per scale, starts empty with every
     trajectory, wherever it starts, and every denoiser call updates it, the repeats of ``resample`` included.  Nothing
     changes at ``guidance_scale == 1``.
+    ``tiles = Tiles(window, stride=None, blend="uniform")`` (``mdm_hip/tiling.py``): tiled sampling (MultiDiffusion, Bar-Tal
+    et al. 2023) of a canvas larger than the window the model was trained at -- x_T is the canvas (``Diffusion.sample(...,
+    image_side=(H, W))``).  Every denoiser call runs on the overlapping windows of x_t, T per image, B T rows per block
+    [uncond | cond | perturbed] with the conditioning and the times repeated per window (once per ``sample()`` call), and the
+    windows' predictions are averaged where they overlap -- uniformly, or under a tent (``blend="ramp"``) -- into
+    whole-canvas predictions: one gather and one merge per scale (GPU tensors: ``ops.tiles_gather`` / ``ops.tiles_merge``,
+    CPU tensors: ``tiling.gather`` / ``tiling.merge``).  Everything behind the denoiser call -- both guidance combines, the
+    step, the dynamic-threshold quantile, ``known_images``, ``solver=`` -- sees whole canvases; FreeU and the perturbed rows
+    act per window.  A nested model takes window, stride and canvas as multiples of its largest ratio.  One window equal
+    to the canvas changes no bit.  All T windows go through ONE denoiser call: memory grows with the canvas.
 
     The three model switches (perturbed rows, region bias, FreeU) are held around each step's denoiser call only
     (``switches``), never across a ``yield``, and a switch that is off is not even resolved.  What excludes what
     (``check``: NotImplementedError): ``guide`` with each of the other four, because their kernels have no backward or, for
-    ``cfg``, no Jacobian; and ``pag_scale`` with ``cfg``.  Everything else composes."""
+    ``cfg``, no Jacobian; ``pag_scale`` with ``cfg``; ``guide`` with ``tiles`` (no backward); and ``regions`` with ``tiles``
+    (the bias is laid out over the whole canvas).  Everything else composes."""
 
     guide: object = None
     pag_scale: float = 0.0
@@ -380,6 +428,7 @@ class SampleOptions:
     region_layers: object = "all"
     freeu: object = None
     cfg: object = None
+    tiles: object = None
 
     REFUSED = {
         ("guide", "pag"): "guide= together with pag_scale != 0: the perturbed rows' attention kernel (mdm_attn_cross_addv) "
@@ -393,6 +442,10 @@ class SampleOptions:
                           "statistics of both predictions, and its Jacobian is not implemented",
         ("pag", "cfg"): "pag_scale != 0 together with cfg=: mdm_pag_combine adds the perturbed-attention term to the plain "
                         "combine; projecting, capping and rescaling an update of three predictions is not implemented",
+        ("guide", "tiles"): "guide= together with tiles=: the window kernels (mdm_tiles_gather, mdm_tiles_merge) have no "
+                            "backward, so the guide's input gradient cannot pass them",
+        ("regions", "tiles"): "regions= together with tiles=: the bias is laid out per query position of the whole canvas, "
+                              "and cropping it per window is not implemented",
     }
 
     @classmethod
@@ -401,9 +454,10 @@ class SampleOptions:
         return cls(**{f.name: keywords.pop(f.name) for f in fields(cls) if f.name in keywords})
 
     def check(self):
-        """every type and range check, and the pairs of ``REFUSED``; several things wrong: guide, pag, regions, freeu, cfg"""
+        """every type and range check, and the pairs of ``REFUSED``; several things wrong: guide, pag, regions, freeu, cfg,
+        tiles"""
         on = dict(guide=self.guide is not None, pag=self.pag_scale != 0, regions=self.regions is not None,
-                  freeu=self.freeu is not None, cfg=self.cfg is not None)
+                  freeu=self.freeu is not None, cfg=self.cfg is not None, tiles=self.tiles is not None)
 
         def refuse(a, b):
             if on[a] and on[b]:
@@ -426,6 +480,10 @@ class SampleOptions:
             self.cfg.validate()
         refuse("guide", "cfg")
         refuse("pag", "cfg")
+        if on["tiles"] and not isinstance(self.tiles, _tiling.Tiles):
+            raise ValueError("tiles = %r (wanted a mdm_hip.Tiles)" % (self.tiles,))
+        refuse("guide", "tiles")
+        refuse("regions", "tiles")
         return self
 
     def blocks(self, guidance_scale):
@@ -476,6 +534,8 @@ class SampleOptions:
             key += (_freeu.graph_key(vision_model, self.freeu),)
         if self.cfg_at(guidance_scale) is not None:
             key += (self.cfg.key(),)
+        if self.tiles is not None:
+            key += (self.tiles.graph_key(),)
         return key
 
 
@@ -788,21 +848,37 @@ class Sampler(nn.Module):
         (pc,), (pu,), extras, _ = self._forward_model_raw(model, [x_t], t, lm_outputs, lm_mask, micros, guidance_scale)
         return (pc if pu is None else pu + guidance_scale * (pc - pu)), extras
 
-    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, opts=SampleOptions()):
+    def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, opts=SampleOptions(),
+                           rows=None):
         """The one denoiser call of a step.  ``x_t``: the list of scales -> (conditional predictions, unconditional
         predictions or Nones, extras, perturbed predictions or None), one entry per scale: the guidance combine itself is
         folded into the step kernel.  The model runs once, on [uncond | cond | perturbed] -- the blocks ``opts.blocks``
-        names, the perturbed one with the conditional rows' conditioning (``pag_rows``) -- under ``opts.switches``."""
+        names, the perturbed one with the conditional rows' conditioning (``pag_rows``) -- under ``opts.switches``.
+        ``opts.tiles``: every block holds the windows of every image, B T rows (``gather_windows``), the conditioning and
+        the times are repeated per window, and the predictions are merged back to whole canvases (``merge_windows``) before
+        they are split; the extras are those of each image's window 0.  ``rows``: (T, (lm_outputs, lm_mask, micros)) -- the
+        window count of the checked geometry and what ``model_rows`` made for this call; ``_sample`` makes both once, not
+        once per step."""
         uncond, pert = opts.blocks(guidance_scale)
         B = x_t[0].shape[0]
-        if uncond or pert:
-            assert B * (1 + uncond) == lm_outputs.shape[0]
-        if pert:
-            lm_outputs, lm_mask, micros = pag_rows(B, lm_outputs, lm_mask, micros)
+        tiles, T = opts.tiles, 1
+        if tiles is not None:
+            ratios = self._scale_info(model)[0]
+            canvases = [tuple(x.shape[2:]) for x in x_t]
+            T = rows[0] if rows is not None else tiles.check(*canvases[0], ratios).count(*canvases[0])
+        lm_outputs, lm_mask, micros = (rows[1] if rows is not None
+                                       else model_rows(opts, guidance_scale, B, T, lm_outputs, lm_mask, micros))
         reps = 1 + uncond + pert
-        xin, tin = repeat_rows(x_t, t, reps)
-        with opts.switches(model, guidance_scale, B, x_t[0].device):
+        if tiles is None:
+            xin, tin = repeat_rows(x_t, t, reps)
+        else:
+            xin, tin = gather_windows(x_t, tiles, ratios, reps), _tiling.time_rows(t, T, reps)
+        with opts.switches(model, guidance_scale, B * T, x_t[0].device):
             preds, extras = self._call_model(model, xin, tin, lm_outputs, lm_mask, micros)
+        if tiles is not None:
+            preds = merge_windows(preds, tiles, ratios, canvases)
+            if extras is not None:
+                extras = extras[::T]
         if extras is not None and reps > 1:
             extras = extras.chunk(reps)[int(uncond)]
         pcs, pus, pps = split_rows(preds, uncond, pert)
@@ -846,16 +922,17 @@ class Sampler(nn.Module):
         top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
         the caller's dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
         ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``options``: the keywords
-        of ``SampleOptions`` (``guide``, ``pag_scale``, ``pag_layers``, ``regions``, ``region_layers``, ``freeu``, ``cfg``),
-        checked here.  The momentum history of ``cfg`` lives in ``solver_state["cfg_run"]`` (one tensor per scale, absent
-        until the first guided step), so without a ``solver_state`` every call starts without history."""
+        of ``SampleOptions`` (``guide``, ``pag_scale``, ``pag_layers``, ``regions``, ``region_layers``, ``freeu``, ``cfg``,
+        ``tiles``), checked here.  The momentum history of ``cfg`` lives in ``solver_state["cfg_run"]`` (one tensor per
+        scale, absent until the first guided step), so without a ``solver_state`` every call starts without history."""
         _check_solver(solver, ddim_eta)
         return self._step(model, time_step, x_t, lm_outputs, lm_mask, micros, SampleOptions(**options).check(),
                           time_step_last, guidance_scale, ddim_eta, return_details, solver, solver_state, second_order)
 
     def _step(self, model, time_step, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=None, guidance_scale=1,
-              ddim_eta=None, return_details=False, solver=None, solver_state=None, second_order=False):
-        """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked once.
+              ddim_eta=None, return_details=False, solver=None, solver_state=None, second_order=False, rows=None):
+        """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked once (and,
+        under ``opts.tiles``, with the window count and the conditioning it repeated per window once: ``rows``).
         Denoiser, update of every scale, then the guide's correction if there is one: with a guide the model runs on leaf
         x_t with grad enabled and the update under no_grad on detached tensors; without, in the caller's grad mode."""
         x_t = self._to_scales(model, x_t)
@@ -880,7 +957,7 @@ class Sampler(nn.Module):
             thr = []   # one entry per scale, hi -> lo
         with grad:
             pcs, pus, _, pps = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
-                                                       opts)   # model sees t-1 (:415)
+                                                       opts, rows)   # model sees t-1 (:415)
         outs = (x_in, pcs, pus)
         if guide is not None:   # the update itself: unchanged, on detached tensors
             outs = ([None if v is None else v.detach() for v in vs] for vs in outs)
@@ -1007,7 +1084,8 @@ class Sampler(nn.Module):
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
                 known_noise_fn=None, **post_args):
-        """``guide``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers``, ``freeu``, ``cfg``: see ``SampleOptions``;
+        """``guide``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers``, ``freeu``, ``cfg``, ``tiles``: see
+        ``SampleOptions``;
         they are taken out of the keywords here (``sample`` has checked them), the rest goes to ``_postprocess``.
         ``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
         whichever update made it, every scale's x_s is replaced where the mask is 1 by the known image diffused to that
@@ -1033,6 +1111,11 @@ class Sampler(nn.Module):
         seq = [x_t] if return_sequence else []
         x0 = extra = None
         history = {}   # dpmpp_2m: x0 and gamma of the step before, per scale; cfg: the momentum buffers ("cfg_run")
+        rows = None    # tiles: the window count and the conditioning repeated per window, the same for every step
+        if opts.tiles is not None:
+            top = x_t[0] if isinstance(x_t, (list, tuple)) else x_t
+            T = opts.tiles.check(*top.shape[2:], self._scale_info(model)[0]).count(*top.shape[2:])
+            rows = T, model_rows(opts, guidance_scale, top.shape[0], T, lm_outputs, lm_mask, micros)
         for i, ts in enumerate(steps[:-1]):
             # second order needs history (not on the first step of this trajectory, wherever it starts) and a finite
             # step in log-SNR (not on the last one: it goes to gamma = 1)
@@ -1042,7 +1125,7 @@ class Sampler(nn.Module):
                 x0, x_t, extra = self._step(
                     model, ts, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
-                    solver_state=history, second_order=second)
+                    solver_state=history, second_order=second, rows=rows)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
@@ -1124,9 +1207,9 @@ class NestedSampler(Sampler):
         if not output_inner:
             return out
         outs = [out] + [one(i) for i in range(1, len(x_t))]
-        up = lambda x, size: F.interpolate(x, size, mode="bilinear")
+        up = lambda x, size: F.interpolate(x, tuple(size), mode="bilinear")   # (H, W): a canvas need not be square
         if not yield_full:
-            return torch.cat([up(o, outs[0].size(-1)) for o in outs[::-1]], -1)
+            return torch.cat([up(o, outs[0].shape[-2:]) for o in outs[::-1]], -1)
         a, b, e = zip(*outs)
-        return (torch.cat([up(v, a[0].size(-1)) for v in a[::-1]], -1),
-                torch.cat([up(v, b[0].size(-1)) for v in b[::-1]], -1), e[-1])
+        return (torch.cat([up(v, a[0].shape[-2:]) for v in a[::-1]], -1),
+                torch.cat([up(v, b[0].shape[-2:]) for v in b[::-1]], -1), e[-1])
