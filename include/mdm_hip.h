@@ -306,7 +306,8 @@ int mdm_adamw_ema_step(float* p, float* g, float* m, float* v, float* ema, const
  *     p = pred_uncond ? pred_uncond + guidance * (pred - pred_uncond) : pred
  *     x0 = (pred_type == 2 (V)) ? x_t sqrt(g) - p sqrt(1-g) : (x_t - p sqrt(1-g)) / sqrt(g)
  *     clip 0: none; 1: clamp(x0 s, -1, 1) / s; 2: clamp(x0 s, -thr[b], thr[b]) / thr[b] / s (dynamic thresholding, thr
- *       = the clamped quantile of |x0 s|, computed by the caller); 3: write the UNCLIPPED x0 s to x0_out and stop
+ *       = the clamped quantile of |x0 s|: mdm_abs_quantile, include/mdm_hip_ext.h, on the output of a clip = 3 launch);
+ *       3: write the UNCLIPPED x0 s to x0_out and stop
  *     mode 0 (ddim_eta None): x_last = x0 beta sqrt(gl) / (1-g) + x_t sqrt(alpha) (1-gl) / (1-g)
  *     mode 1: eps = (x_t - x0 sqrt(g)) / sqrt(1-g); x_last = x0 sqrt(gl) + eps sqrt(1 - gl - eta^2 beta~) (eta = 0: no noise)
  *     need_noise: x_last += sqrt(beta~) * noise_gate[0] * n, n = noise[] if given, else drawn from rng_state
@@ -324,7 +325,7 @@ int mdm_adamw_ema_step(float* p, float* g, float* m, float* v, float* ema, const
  *   x0_prev is not read, so the last step of a schedule (gl == 1: sigma = 0, h = inf, x_last = x0) is exact whatever
  *   x0_prev holds; the caller clears it on the first step (no history) and on the last.  Second order needs gl < 1 and
  *   gp < g.  x0_out MAY alias x0_prev (every thread reads its elements of x0_prev before it writes them); x_last_out may
- *   alias neither.  Dynamic thresholding: mdm_sampler_step(clip = 3) -> quantile -> this entry with clip = 2 and thr.
+ *   alias neither.  Dynamic thresholding: mdm_sampler_step(clip = 3) -> mdm_abs_quantile -> this entry with clip = 2 and thr.
  * mdm_sampler_known_blend (a pure addition, no reference line: the reference's Diffusion.partial_diffusion is dead code and
  *   it has no known-region sampling): the replacement step of RePaint -- Lugmayr, Danelljan, Romero, Yu, Timofte, Van Gool
  *   2022, "RePaint: Inpainting using Denoising Diffusion Probabilistic Models".  IN PLACE on x [B, C, H, W], the state at

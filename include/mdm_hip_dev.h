@@ -40,6 +40,10 @@ int mdm_dev_ffn_aux_bytes(void);
 /* phase time stamps of attn_bwd_small32_kernel: a device buffer of [blocks][8][16] 64-bit words (tools/attn_debug.py), or
  * null (the default) */
 int mdm_dev_set_attn_dbg(void* buf);
+/* one launch of mdm_abs_quantile (include/mdm_hip_ext.h) by itself, for the rate of each level (tools/thr_bench.py): stage 0 =
+ * the zeroing of the workspace, 1 .. 3 = the pass of that level, on a workspace in the state the stages before it left.
+ * Arguments and checks as mdm_abs_quantile. */
+int mdm_dev_abs_quantile_stage(const float* x, void* ws, size_t ws_bytes, int B, size_t n, float q, int stage, void* stream);
 
 #ifdef __cplusplus
 }

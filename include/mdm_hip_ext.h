@@ -108,6 +108,28 @@ int mdm_tiles_gather(const float* x, float* out, int B, int C, int H, int W, int
 int mdm_tiles_merge(const float* p, float* out, int R, int C, int H, int W, int h, int w, int sy, int sx, int blend,
                     void* stream);
 
+/* The per-sample threshold of the dynamic threshold functions: thr[b] = clamp(quantile_q |x[b, :]|, cmin, cmax), the
+ * quantile by torch.quantile's rule, found exactly by a radix select on the bit patterns of the magnitudes -- no sort, and
+ * no limit of 2^24 values per row.  x: fp32 [B, n], contiguous.  For a row, with a = |x| sorted ascending:
+ *   rank = q (n - 1) IN FP32 ;  lo = floor(rank) ;  hi = min(ceil(rank), n - 1) ;  w = rank - lo
+ *   quant = w < 0.5 ? a[lo] + w (a[hi] - a[lo]) : a[hi] - (a[hi] - a[lo]) (1 - w) ;  thr = clamp(quant, cmin, cmax)
+ * (above 2^24 the fp32 rank is an integer: lo == hi, w == 0; the rule is the same).  A row that holds a NaN: thr = NaN.  +-inf
+ * are ordinary largest values and the interpolation is applied as written (inf - inf: NaN, as torch); -0.0 counts as 0.
+ * cmin = -inf, cmax = +inf: no clamp.  stats [B, 2] or NULL: a[lo] and a[hi] bit for bit (of a NaN, its pattern without the
+ * sign).
+ * The key bits(x) & 0x7fffffff orders as |x| does; the prefix that holds each of the two ranks is refined over three levels
+ * of 12 + 11 + 8 bits, each one pass over x: block-private LDS histograms, merged into the row's histogram in ws with integer
+ * atomics.  Only the first pass counts every element.  16-byte loads where n % 4 == 0 and x is 16-byte aligned, 4-byte loads
+ * otherwise: same result.  Integer counts and an exact selection: a row's thr and stats depend on nothing but the row (not on
+ * B, not on the other rows), and two runs are bit-identical.  No float atomics.
+ * mdm_abs_quantile_plan (host-only): the bytes of ws -- per row 34 880 (the histograms of the three levels).
+ * ws: 16-byte aligned; it may hold anything on entry (the entry zeroes what it needs in a launch of its own) and is free again
+ * when the last launch has run.  Five launches for any B and n; no allocation, no host sync, no memset: capturable.
+ * Limits: 1 <= n < 2^31, 1 <= B <= 65535, 0 <= q <= 1, cmin <= cmax.  Invalid arguments: a negative status, nothing launched. */
+int mdm_abs_quantile_plan(int B, size_t n, size_t* ws_bytes);
+int mdm_abs_quantile(const float* x, void* ws, size_t ws_bytes, int B, size_t n, float q, float cmin, float cmax, float* thr,
+                     float* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,7 +109,8 @@ class GraphedSampler:
 
     Semantics are those of ``Sampler._sample`` with ``resample_steps=True`` (reference samplers.py:516-609, 655-713):
     DDPM (``ddim_eta=None``) or DDIM(eta), classifier-free guidance, CLIP / NONE / DYNAMIC / DYNAMIC_IF thresholding (the
-    dynamic ones: x0 kernel -> ``torch.quantile`` -> update kernel, all inside the graph), or ``solver="dpmpp_2m"``
+    dynamic ones: x0 kernel -> ``ops.abs_quantile``, a radix select of five launches whose workspace -- 35 KB per sample --
+    lives in the graph's pool, -> update kernel, all inside the graph; no sort), or ``solver="dpmpp_2m"``
     (DPM-Solver++(2M): deterministic, the x0 history of every scale lives in a static buffer that the step kernel updates
     in place, the order flag of each step comes from a device table).  The ancestral noise comes
     from the library's counter-based generator (``ops.DeviceRng``, replayable on the host); the START noise is drawn
@@ -231,8 +232,8 @@ class GraphedSampler:
             if tiles is not None:
                 preds = merge_windows(preds, tiles, ratios, canvases)
             preds, pus, pps = split_rows(preds, uncond, pert)
-            # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> torch.quantile, a
-            # sort + lerp on the device, -> update kernel, all captured).  Every row draws and advances the generator in
+            # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> ops.abs_quantile, the
+            # library's radix select, -> update kernel, all captured).  Every row draws and advances the generator in
             # the eager sampler's order (use_device_rng()); the device gate decides whether the noise is added
             if cfg is not None:
                 history.update(cfg_state=cfg_state,

@@ -2577,7 +2577,7 @@ def sampler_step_2m(x_t, pred, g, g_last, prediction_type, g_prev=None, x0_prev=
     -> (x0, x_last).  ``second_order``: False / True, or a device float[1] gate (0 = first order) so that one captured
     graph serves every step.  Second order needs ``x0_prev`` and ``g_prev`` (the x0 of the step before and the gamma
     it was formed at).  ``x0_out`` may be ``x0_prev`` itself: the history is then updated in place.
-    ``clip``: "NONE" | "CLIP" | "DYNAMIC" (needs ``thr`` [B], from ``sampler_step(clip="X0_ONLY")`` + quantile)."""
+    ``clip``: "NONE" | "CLIP" | "DYNAMIC" (needs ``thr`` [B], from ``sampler_step(clip="X0_ONLY")`` + ``abs_quantile``)."""
     x_t, pred = _img(x_t), _img(pred)
     B = x_t.shape[0]
     chw = x_t.numel() // B
@@ -2862,6 +2862,39 @@ def cfg_combine(x_t, pred, pred_uncond, g, prediction_type, guidance_scale, eta=
                           float(eta), float(norm_threshold), rescale, sc, B, chw, pt, _stream()), "mdm_cfg_combine"),
         kind="hbm")
     return out, ro
+
+
+_aq_plans = {}   # (B, n) -> workspace bytes of mdm_abs_quantile_plan
+
+
+def abs_quantile(x, q, cmin=None, cmax=None, return_stats=False):
+    """thr[b] = clamp(quantile_q |x[b]|, cmin, cmax) over everything behind the first axis, by ``torch.quantile``'s rule
+    (fp32 rank, linear interpolation) -- the per-sample threshold of the dynamic threshold functions as a radix select
+    (include/mdm_hip_ext.h mdm_abs_quantile): FIVE launches, no sort, any row length below 2^31.  x: fp32 [B, ...] on the
+    GPU; ``cmin`` / ``cmax`` None: no bound on that side.  -> thr [B], with ``return_stats`` (thr, stats [B, 2]): the two
+    order statistics a[lo], a[hi] the quantile interpolates, bit for bit.  A row with a NaN gives NaN.  The workspace comes
+    from the caching allocator: no host sync, capturable."""
+    x = _img(x)
+    if x.dim() < 2:
+        raise _lib.MdmHipError("abs_quantile: x must be [B, ...] (got %s)" % (tuple(x.shape),))
+    B = x.shape[0]
+    n = x.numel() // B if B else 0
+    L = _lib.lib()
+    key = (B, n)
+    wsb = _aq_plans.get(key)
+    if wsb is None:
+        v = ctypes.c_size_t(0)
+        _lib.check(L.mdm_abs_quantile_plan(B, n, ctypes.byref(v)), "mdm_abs_quantile_plan")
+        wsb = _aq_plans[key] = v.value
+    ws = _f32_ws(wsb, x.device)
+    thr = torch.empty(B, dtype=torch.float32, device=x.device)
+    stats = torch.empty(B, 2, dtype=torch.float32, device=x.device) if return_stats else None
+    lo = float("-inf") if cmin is None else float(cmin)
+    hi = float("inf") if cmax is None else float(cmax)
+    _prof_wrap("abs_quantile", float(x.numel() * 4 * 3), lambda: _lib.check(
+        L.mdm_abs_quantile(_p(x), _p(ws), wsb, B, n, float(q), lo, hi, _p(thr), _p(stats), _stream()), "mdm_abs_quantile"),
+        kind="hbm")
+    return (thr, stats) if return_stats else thr
 
 
 def noise_images(images, g, eps=None, rng=None, rng_stream=0, inv_scale=1.0):

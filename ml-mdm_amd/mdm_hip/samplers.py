@@ -67,6 +67,42 @@ def _enum(cls, v):
     return v if isinstance(v, cls) else cls[str(v).upper()]
 
 
+QUANTILE_ROW_LIMIT = 1 << 24   # torch.quantile refuses a longer row ("input tensor is too large")
+
+
+def dynamic_threshold_ref(x0s, ratio, vmax):
+    """The per-sample threshold [B] of the dynamic threshold functions in torch ops: the ``ratio`` quantile of |x0s| over
+    everything behind the first axis, clamped to [1, vmax] -- ``torch.quantile``'s own rule written out, so that it holds
+    for rows of any length.  With a = |x0s| sorted ascending along a row of n values:
+
+        rank = ratio (n - 1) in the dtype of the data (fp32 data: an fp32 product) ; lo = floor(rank) ;
+        hi = min(ceil(rank), n - 1) ; w = rank - lo ; quantile = lerp(a[lo], a[hi], w)
+
+    A row that holds a NaN gives NaN.  fp32 unless ``x0s`` is fp64.  Up to 2^24 values per row this is ``torch.quantile``
+    bit for bit; ``ops.abs_quantile`` computes the same on the GPU without the sort."""
+    flat = x0s if x0s.dtype == torch.float64 else x0s.float()
+    a = flat.reshape(flat.shape[0], -1).abs().sort(dim=1).values
+    n = a.shape[1]
+    rank = torch.tensor(ratio, dtype=a.dtype) * (n - 1)
+    lo = min(int(rank.floor()), n - 1)
+    hi = min(int(rank.ceil()), n - 1)
+    w = (rank - rank.floor()).to(a.device)
+    quant = torch.lerp(a[:, lo], a[:, hi], w)
+    quant = torch.where(a[:, -1].isnan(), torch.full_like(quant, float("nan")), quant)   # NaN sorts last
+    return quant.clamp(min=1, max=vmax)
+
+
+def _abs_quantile_clamped(flat, ratio, vmax):
+    """clamp(quantile_ratio |flat[b]|, 1, vmax) of a [B, n] tensor.  fp32 on the GPU: the radix select
+    (``ops.abs_quantile``; it has no backward, so a tensor that asks for a gradient keeps the torch ops).  Otherwise
+    ``torch.quantile`` up to its row limit and the same rule by a sort beyond it."""
+    if flat.is_cuda and flat.dtype == torch.float32 and not (flat.requires_grad and torch.is_grad_enabled()):
+        return ops.abs_quantile(flat, ratio, 1, vmax)
+    if flat.shape[1] > QUANTILE_ROW_LIMIT:
+        return dynamic_threshold_ref(flat, ratio, vmax)
+    return torch.quantile(flat.abs(), ratio, dim=1).clamp(min=1, max=vmax)
+
+
 @dataclass
 class SamplerConfig:
     num_diffusion_steps: int = 32
@@ -708,7 +744,7 @@ class Sampler(nn.Module):
                        thr_out, ddim_eta=None):
         """what both step kernels start with -> (fp32 x_t, fp32 pred, their keyword arguments: prediction type, image scale,
         guidance, clip mode and per-sample threshold).  The dynamic thresholds cost one launch for the unclipped x0 and
-        the quantile."""
+        the five of the quantile's radix select (``ops.abs_quantile``)."""
         scale = 1 if image_scale is None else image_scale
         x_t, pred = x_t.float(), pred.float()
         kw = dict(prediction_type=prediction_type or self._config.prediction_type, image_scale=scale,
@@ -738,7 +774,7 @@ class Sampler(nn.Module):
             return None
         ratio, vmax = (0.995, 100) if fn == ThresholdType.DYNAMIC else (0.95, 1.5)
         flat = x0s if x0s.dtype == torch.float64 else x0s.float()
-        return torch.quantile(flat.reshape(flat.shape[0], -1).abs(), ratio, dim=1).clamp(min=1, max=vmax)
+        return _abs_quantile_clamped(flat.reshape(flat.shape[0], -1), ratio, vmax)
 
     # ---- one step of DPM-Solver++(2M) (not in the reference) ------------------------------------------
     def get_prediction_xt_last_2m(self, x_t, pred, g, g_last, g_prev=None, x0_prev=None, second_order=False,
@@ -780,7 +816,7 @@ class Sampler(nn.Module):
         """Imagen dynamic thresholding (:461-498)."""
         shape, dtype = sample.shape, sample.dtype
         flat = (sample if sample.dtype == torch.float64 else sample.float()).reshape(shape[0], -1)   # fp64 stays fp64
-        s = torch.quantile(flat.abs(), ratio, dim=1).clamp(min=1, max=max_value).unsqueeze(1)
+        s = _abs_quantile_clamped(flat, ratio, max_value).unsqueeze(1)
         return (torch.clamp(flat, -s, s) / s).reshape(shape).to(dtype)
 
     def clip_sample(self, pred_x0, image_scale=1):
