@@ -433,7 +433,8 @@ int mdm_dropout(const void* x, void* y, size_t n, float p, unsigned long long se
  *   mdm_t5_attn_fwd    out [T, H d] = softmax(q k^T + bias_table[h][pos_k - pos_q + S - 1]) v per row and head, with NO
  *                      1 / sqrt(d) scaling; qkv [T, 3 H d] = (q | k | v), bias_table [H][2 S - 1] fp32.  d must be 64,
  *                      S <= 512; max_len (<= S) = the longest row (it sizes the grid: S is always a valid value).
- *                      Scores and softmax in fp32; nothing is saved for a backward pass (there is none). */
+ *                      Scores and softmax in fp32; nothing is saved for a backward pass (mdm_t5_attn_fwd_lse and the
+ *                      input gradients of the encoder are declared apart, in mdm_hip_ext.h). */
 int mdm_t5_embed_rms(const int* ids, const float* table, const float* ln_w, float* x, void* h, int T, int D, int vocab,
                      float eps, int dtype, void* stream);
 int mdm_t5_add_rms(float* x, const void* delta, const float* ln_w, void* h, int T, int D, float eps, int dtype,

@@ -130,6 +130,46 @@ int mdm_abs_quantile_plan(int B, size_t n, size_t* ws_bytes);
 int mdm_abs_quantile(const float* x, void* ws, size_t ws_bytes, int B, size_t n, float q, float cmin, float cmax, float* thr,
                      float* stats, void* stream);
 
+/* Input gradients of the frozen T5 encoder (textual inversion: csrc/text_encoder_bwd.hip).  Packed tokens, dtypes and
+ * tensors as the mdm_t5_* forward entries of mdm_hip.h: dtype MDM_F32 or MDM_BF16 is the storage type of the GEMM-operand
+ * tensors (void*); the residual stream, its gradient, lse and the statistics are fp32.  No weight and no bias-table gradient.
+ * No allocation, no workspace, no host sync, NO atomics: two runs are bit-identical, and the gradients of a sequence do not
+ * depend on what else is in the batch.  Invalid arguments: a negative status, nothing launched.
+ *   mdm_t5_attn_fwd_lse   mdm_t5_attn_fwd with one more output, lse fp32 [H, T]: the log of the softmax denominator per
+ *                      (head, packed query), running max included.  out: the bits of mdm_t5_attn_fwd.
+ *   mdm_t5_attn_bwd    qkv [T, 3 H 64], out and dout [T, H 64], lse -> dqkv [T, 3 H 64], every element written.  Per
+ *                      (sequence, head):  P = exp(q k^T + bias[h][pos_k - pos_q + S - 1] - lse),  delta = rowsum(dout o out),
+ *                      dV = P^T dout,  dS = P o (dout V^T - delta),  dQ = dS K,  dK = dS^T Q.  No 1 / sqrt(d).  Two launches
+ *                      (a wave per 16 queries for dQ, a wave per 16 keys for dK and dV, each recomputing the scores);
+ *                      products on MFMA, bf16 16x16x32 or exact fp32.  d == 64, S <= 512, rows of any length from 0 to S.
+ *   mdm_t5_gated_gelu_bwd  u [T, 2F], dy [T, F] -> du [T, 2F]:  du[:, :F] = dy u[:, F:] gelu_new'(u[:, :F]),
+ *                      du[:, F:] = dy gelu_new(u[:, :F])  (tanh form, the forward's constants).  F % 8 == 0.
+ *   mdm_t5_rms_bwd     the input gradient of h = w o x rsqrt(mean(x^2) + eps), ADDED into the fp32 stream gradient:
+ *                      dx[t] += rs (w o dh) - x rs^3 / D sum(w o dh o x), x the saved fp32 row [T, D], dh [T, D] of dtype.
+ *                      dx_lo (dtype [T, D], or NULL): a copy of the updated dx, the operand of the next GEMM.
+ *   mdm_t5_final_rms_bwd   the same for mdm_t5_final_rms: x + delta (delta may be NULL) is the normed row, the gradient of
+ *                      packed row t is row flat[t] of dout fp32 [B S, D] (a gather), and dx[t] is WRITTEN.
+ *   mdm_t5_embed_rms_slots  mdm_t5_embed_rms with an override: slot_of_id (int32 [n_ids], -1 or a row of learned fp32
+ *                      [P, D]) is looked up first; a hit reads learned[slot] instead of table[id].  n_ids >= vocab; ids in
+ *                      [vocab, n_ids) must hit a slot.  With no hit: the bits of mdm_t5_embed_rms.
+ *   mdm_t5_embed_bwd   dlearned[j] = sum over k in [slot_start[j], slot_start[j + 1]) of dx0[tokens[k]], sequentially in
+ *                      that order (the host lists a slot's packed tokens ascending); dx0 fp32 [T, D], tokens int32 [n],
+ *                      slot_start int32 [P + 1].  Every slot is written, one without tokens with zeros.  D % 4 == 0. */
+int mdm_t5_attn_fwd_lse(const void* qkv, const int* seq_start, const int* pos, const float* bias_table, void* out, float* lse,
+                        int B, int T, int S, int max_len, int H, int d, int dtype, void* stream);
+int mdm_t5_attn_bwd(const void* qkv, const void* out, const float* lse, const void* dout, const int* seq_start, const int* pos,
+                    const float* bias_table, void* dqkv, int B, int T, int S, int max_len, int H, int d, int dtype,
+                    void* stream);
+int mdm_t5_gated_gelu_bwd(const void* u, const void* dy, void* du, int T, int F, int dtype, void* stream);
+int mdm_t5_rms_bwd(const float* x, const float* ln_w, const void* dh, float* dx, void* dx_lo, int T, int D, float eps,
+                   int dtype, void* stream);
+int mdm_t5_final_rms_bwd(const float* x, const void* delta, const float* ln_w, const float* dout, const int* flat, float* dx,
+                         void* dx_lo, int T, int D, float eps, int dtype, void* stream);
+int mdm_t5_embed_rms_slots(const int* ids, const float* table, const int* slot_of_id, const float* learned, const float* ln_w,
+                           float* x, void* h, int T, int D, int vocab, int n_ids, int P, float eps, int dtype, void* stream);
+int mdm_t5_embed_bwd(const float* dx0, const int* slot_start, const int* tokens, float* dlearned, int P, int D, int n, int T,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

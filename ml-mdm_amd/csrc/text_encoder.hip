@@ -3,11 +3,13 @@
 // row, each with its original position.  Everything between the seven projections (the existing GEMM) lives here:
 //   t5_rms_kernel      embedding gather + first RMSNorm | residual add + RMSNorm | final RMSNorm + scatter to [B, S, D]
 //   t5_gated_gelu_kernel   gelu_new(u[:, :F]) * u[:, F:]
-//   t5_attn_kernel     softmax(q k^T + bias[h, pos_k - pos_q]) v per (sequence, head), no 1/sqrt(d), no backward
+//   t5_attn_kernel     softmax(q k^T + bias[h, pos_k - pos_q]) v per (sequence, head), no 1/sqrt(d); the input
+//                      gradients are in text_encoder_bwd.hip
 // The residual stream is fp32 (the reference's autocast leaves the residual adds in fp32); T is the storage type of the
 // GEMM operands.  Norm statistics, scores and the softmax are fp32.
 #include "common.hpp"
 #include "../../include/mdm_hip.h"
+#include "../../include/mdm_hip_ext.h"
 
 namespace mdm {
 
@@ -137,10 +139,13 @@ __global__ void t5_gated_gelu_kernel(const T* __restrict__ u, T* __restrict__ y,
 //        spreads the 16 channel rows of a fragment read over the banks.
 // Q and K fragments are read straight from global memory (8 consecutive channels per lane = one 16 / 32-byte load).
 // Loads of keys beyond the row's end are clamped to its last token (finite data) and their scores set to -inf.
-template <typename T>
+// LSE: also write lse[h, query] = running max + log(running sum), what the backward (text_encoder_bwd.hip) recomputes the
+// probabilities from; `out` is the same bits either way.
+template <typename T, bool LSE>
 __global__ __launch_bounds__(256) void t5_attn_kernel(const T* __restrict__ qkv, const int* __restrict__ seq_start,
                                                       const int* __restrict__ pos, const float* __restrict__ bias,
-                                                      T* __restrict__ out, int B, int Ttot, int S, int qtiles, int H) {
+                                                      T* __restrict__ out, float* __restrict__ lse, int B, int Ttot, int S,
+                                                      int qtiles, int H) {
   constexpr int D = 64, KT = 32;
   constexpr int VS = KT + 16 / (int)sizeof(T);          // slots per channel row of the V^T image, padded by 16 bytes
   __shared__ float tab[1024];
@@ -265,6 +270,9 @@ __global__ __launch_bounds__(256) void t5_attn_kernel(const T* __restrict__ qkv,
     T* orow = out + (size_t)(t0 + qi) * H * D + (size_t)h * D;
 #pragma unroll
     for (int n = 0; n < 4; ++n) store4(orow + n * 16 + g * 4, o[n] * inv);
+    if constexpr (LSE) {
+      if (g == 0) lse[(size_t)h * Ttot + t0 + qi] = m + logf(l);
+    }
   }
 }
 
@@ -329,7 +337,23 @@ extern "C" int mdm_t5_attn_fwd(const void* qkv, const int* seq_start, const int*
   const int qtiles = (max_len + 15) / 16;
   const long long items = (long long)B * qtiles;
   MDM_CHECK_ARG(items < (1ll << 30));
-  MDM_T5_DISPATCH(dtype, hipLaunchKernelGGL(t5_attn_kernel<TT>, dim3((unsigned)((items + 3) / 4), H), dim3(256), 0, st, (const TT*)qkv,
-                                            seq_start, pos, bias_table, (TT*)out, B, T, S, qtiles, H));
+  MDM_T5_DISPATCH(dtype, hipLaunchKernelGGL((t5_attn_kernel<TT, false>), dim3((unsigned)((items + 3) / 4), H), dim3(256), 0, st,
+                                            (const TT*)qkv, seq_start, pos, bias_table, (TT*)out, (float*)nullptr, B, T, S, qtiles,
+                                            H));
+  MDM_LAUNCH_STATUS();
+}
+
+extern "C" int mdm_t5_attn_fwd_lse(const void* qkv, const int* seq_start, const int* pos, const float* bias_table, void* out,
+                                   float* lse, int B, int T, int S, int max_len, int H, int d, int dtype, void* stream) {
+  MDM_CHECK_ARG(qkv && seq_start && pos && bias_table && out && lse);
+  MDM_CHECK_ARG(d == 64);
+  MDM_CHECK_ARG(B > 0 && T > 0 && H > 0 && H <= 65535);
+  MDM_CHECK_ARG(S >= 1 && S <= 512 && max_len >= 1 && max_len <= S);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int qtiles = (max_len + 15) / 16;
+  const long long items = (long long)B * qtiles;
+  MDM_CHECK_ARG(items < (1ll << 30));
+  MDM_T5_DISPATCH(dtype, hipLaunchKernelGGL((t5_attn_kernel<TT, true>), dim3((unsigned)((items + 3) / 4), H), dim3(256), 0, st,
+                                            (const TT*)qkv, seq_start, pos, bias_table, (TT*)out, lse, B, T, S, qtiles, H));
   MDM_LAUNCH_STATUS();
 }

@@ -14,6 +14,7 @@ Layout of the package
   text_encoder.py T5Encoder / LanguageModel: the frozen flan-T5 text encoder on packed tokens (mirror of
                   ml_mdm.language_models.factory)
   lora.py         LoRA adapters on the attention projections: attach / merge / unmerge / detach
+  textual_inversion.py  learnable placeholder-token embeddings through the frozen text encoder: attach / merge / detach
   fp8.py          opt-in MXFP8 (weights and activations) sampling path of the attention-layer 1x1 GEMMs and, with
                   conv_targets, of the ResNet convolutions (3x3 implicit GEMM): attach / detach
   pag.py          perturbed-attention guidance: select / perturbed (the samplers' pag_scale / pag_layers)
@@ -58,8 +59,10 @@ from . import guidance  # noqa: F401,E402
 from .guidance import CFG  # noqa: F401,E402
 from . import tiling  # noqa: F401,E402
 from .tiling import Tiles  # noqa: F401,E402
+from . import textual_inversion  # noqa: F401,E402
 
 __all__ = [
+    "textual_inversion",
     "tiling",
     "Tiles",
     "guidance",

@@ -6,7 +6,9 @@ never influence valid ones (keys are masked, and factory.py:101 zeroes the padde
 on the PACKED valid tokens of a batch -- each token keeps its original position for the relative bias, which makes
 the packing exact, masks with holes included.  Per layer: 4 GEMMs (the library's existing kernel; Wq|Wk|Wv and
 Wi0|Wi1 concatenated), one attention launch, two residual-add + RMSNorm launches, one gated-GELU launch
-(csrc/text_encoder.hip).  Inference only: always ``no_grad``, parameters frozen, forward-only weight packs.
+(csrc/text_encoder.hip).  Parameters frozen, forward-only weight packs and ``no_grad`` -- except with a textual
+inversion attached (textual_inversion.py): then the forward is one autograd node, and its backward is the chain of INPUT
+gradients down to the learned embedding rows (csrc/text_encoder_bwd.hip; input-gradient packs built on first use).
 
 The tokenizer and ``from_pretrained`` stay the user's: build a ``T5EncoderConfig.from_hf(hf_model.config)``, then
 ``load_state_dict(hf_model.state_dict(), strict=False)``.  Nothing here imports ``transformers``.
@@ -149,6 +151,8 @@ class T5Encoder(nn.Module):
         self._packs = {}        # dtype -> (signature of the masters, [(Wqkv, Wo, Wi, Wo_ff) per layer])
         self._tables = {}       # S -> (signature of the bias weight, [H, 2S-1] fp32 table)
         self._released = None   # the dtype the masters were released for
+        self._dpacks = {}       # dtype -> (signature, [input-gradient packs per layer]): only after a differentiable forward
+        self.__dict__["_adapter"] = None   # the attached TextualInversion (not a submodule: it owns its parameter)
 
     # ---- reference call surface ---------------------------------------------------------------------------------
     @property
@@ -192,10 +196,40 @@ class T5Encoder(nn.Module):
         self._packs[dtype] = (sig, packs)
         return packs
 
+    def _layer_dpacks(self, dtype):
+        """[(Wqkv, Wo, Wi, Wo_ff) per layer] in the input-gradient layout of the GEMM, for the concatenations the forward
+        packs: a second copy of the projection weights (2.4 GB for flan-t5-xl in bf16), built on the first differentiable
+        forward and never otherwise."""
+        if self._released is not None:
+            raise _lib.MdmHipError("release_masters() dropped the fp32 projection weights of this T5Encoder: a differentiable "
+                                   "forward (textual inversion) needs them for its input-gradient packs -- reload the checkpoint")
+        L = self.config.num_layers
+        sig = tuple((w._version, w.data_ptr()) for l in range(L) for w in self._masters(l))
+        ent = self._dpacks.get(dtype)
+        if ent is not None and ent[0] == sig:
+            return ent[1]
+
+        def pack(*ws):   # a temporary tensor each time: the forward copy packed_weight builds beside it dies with it
+            w = ws[0].detach() if len(ws) == 1 else torch.cat(ws, 0)
+            wd = ops.packed_weight(w, None, dtype, forward_only=False)[1]
+            if wd is None:
+                raise _lib.MdmHipError("no input-gradient pack for a projection of shape %s" % (tuple(w.shape),))
+            return wd
+
+        packs = []
+        for l in range(L):
+            q, k, v, o, wi0, wi1, wo = self._masters(l)
+            packs.append((pack(q, k, v), pack(o), pack(wi0, wi1), pack(wo)))
+        self._dpacks[dtype] = (sig, packs)
+        return packs
+
     def release_masters(self, dtype=None):
         """Drop the fp32 copies of the projection weights once they are packed for ``dtype`` (default: the current
         compute dtype): flan-t5-xl keeps 2.4 GB of packed bf16 weights instead of 4.9 GB more of masters.  The
         embedding, the norms and the bias table stay.  Afterwards only that dtype runs and ``state_dict()`` raises."""
+        if self._dpacks:
+            raise _lib.MdmHipError("this T5Encoder has run a differentiable forward (textual inversion): its input-gradient "
+                                   "packs are rebuilt from the fp32 projection weights, which release_masters() would drop")
         dtype = dtype or compute_dtype()
         ops._require_gpu(self.shared.weight)
         packs = self._layer_packs(dtype)
@@ -219,9 +253,22 @@ class T5Encoder(nn.Module):
         return ent[1]
 
     # ---- forward ------------------------------------------------------------------------------------------------
-    @torch.no_grad()
     def forward(self, input_ids, attention_mask=None, return_dict=None, return_penultimate=None, *args, **kwargs):
+        """Inference (``no_grad``, nothing saved) unless a textual-inversion adapter is attached, its parameter requires
+        grad and grad mode is on: then one autograd node runs the same launches, saves what the backward needs and
+        returns the input gradient of the learned rows (textual_inversion.py)."""
+        ti = self._adapter
+        if ti is None or not (torch.is_grad_enabled() and ti.embeddings.requires_grad):
+            with torch.no_grad():
+                plan = self._plan(input_ids, attention_mask)
+                return self._launch(plan, None if ti is None else ti.embeddings.detach(), None)
+        return _T5EncoderGradFn.apply(ti.embeddings, self, input_ids, attention_mask)
+
+    def _plan(self, input_ids, attention_mask, flat=False):
+        """host side of a forward: checks, the packing plan and its one copy to the device.  ``flat``: also upload the
+        packed -> flat index b * S + s of every token (what the backward of the final norm gathers through)"""
         c = self.config
+        ti = self._adapter
         table = self.shared.weight
         ops._require_gpu(table)
         dev = table.device
@@ -242,18 +289,25 @@ class T5Encoder(nn.Module):
         if tuple(mask_h.shape) != (B, S):
             raise ValueError("attention_mask %s does not match input_ids %s" % (mask_h.shape, (B, S)))
         pk = pack_index(mask_h)
-        T, D = pk["T"], c.d_model
-        out = torch.empty(B, S, D, dtype=torch.float32, device=dev)
+        T = pk["T"]
+        plan = {"pk": pk, "B": B, "S": S, "T": T, "dev": dev, "ids_h": None}
         if T == 0:
-            return out.zero_()
+            return plan
 
-        # one pinned host buffer, one asynchronous copy: [ids | seq_start | pos | src]
+        # one pinned host buffer, one asynchronous copy: [ids | seq_start | pos | src | flat]
         ids_on_host = not (isinstance(input_ids, torch.Tensor) and input_ids.is_cuda)
         parts = [pk["seq_start"], pk["pos"], pk["src"]]
+        if flat:
+            parts.append(pk["idx"].astype(np.int32))
         if ids_on_host:
             ids_h = np.asarray(input_ids.numpy() if isinstance(input_ids, torch.Tensor) else input_ids).reshape(-1)[pk["idx"]]
-            if ids_h.min() < 0 or ids_h.max() >= c.vocab_size:
-                raise ValueError("token id outside [0, %d)" % c.vocab_size)
+            bad = (ids_h < 0) | (ids_h >= c.vocab_size)
+            if ti is not None:
+                bad &= ~np.isin(ids_h, ti.token_ids)
+            if bad.any():
+                raise ValueError("token id %d outside [0, %d)%s" % (int(ids_h[bad][0]), c.vocab_size,
+                                 "" if ti is None else " and not a placeholder of the attached textual inversion"))
+            plan["ids_h"] = ids_h
             parts.insert(0, ids_h.astype(np.int32))
         host = torch.from_numpy(np.concatenate(parts)).pin_memory()
         devbuf = host.to(dev, non_blocking=True)
@@ -264,8 +318,23 @@ class T5Encoder(nn.Module):
         else:
             gather = torch.from_numpy(pk["idx"]).pin_memory().to(dev, non_blocking=True)
             ids = input_ids.reshape(-1).index_select(0, gather).to(torch.int32)
-        seq_start, pos, src = devbuf[o:o + B + 1], devbuf[o + B + 1:o + B + 1 + T], devbuf[o + B + 1 + T:]
+        plan["ids"] = ids
+        o1, o2, o3 = o + B + 1, o + B + 1 + T, o + B + 1 + T + B * S
+        plan["seq_start"], plan["pos"], plan["src"], plan["flat"] = devbuf[o:o1], devbuf[o1:o2], devbuf[o2:o3], devbuf[o3:]
+        return plan
 
+    def _launch(self, plan, learned, save):
+        """The launch sequence on a plan.  ``learned`` (fp32 [P, D] or None): the rows of the attached adapter, which
+        override the table.  ``save`` (a dict or None): keep what the backward needs -- per layer the two fp32 stream
+        rows, qkv, the attention output, its log-sum-exp and u -- instead of reusing one set of buffers."""
+        c = self.config
+        table = self.shared.weight
+        pk, B, S, T, dev = plan["pk"], plan["B"], plan["S"], plan["T"], plan["dev"]
+        D = c.d_model
+        out = torch.empty(B, S, D, dtype=torch.float32, device=dev)
+        if T == 0:
+            return out.zero_()
+        ids, seq_start, pos, src = plan["ids"], plan["seq_start"], plan["pos"], plan["src"]
         dtype = compute_dtype()
         dt = ops.F32 if dtype == torch.float32 else ops.BF16
         packs = self._layer_packs(dtype)
@@ -274,22 +343,42 @@ class T5Encoder(nn.Module):
         inner = H * dk
         L, p, st = _lib.lib(), ops._p, ops._stream
         new = lambda n, t=dtype: torch.empty(T, n, dtype=t, device=dev)
-        x, h, qkv, att, delta, u, y = new(D, torch.float32), new(D), new(3 * inner), new(inner), new(D), new(2 * F), new(F)
+        x, h, delta, y = new(D, torch.float32), new(D), new(D), new(F)
+        if save is None:       # one set for every layer; a saving forward allocates these per layer below
+            qkv, att, u = new(3 * inner), new(inner), new(2 * F)
 
         def gemm(a, w, yout, cin, cout):
             ops._conv_launch(a, w, None, None, None, yout, None, T, 1, 1, cin, 1, 1, cout, 1, 1, 0, 0)
 
         blocks = self.encoder.block
-        _lib.check(L.mdm_t5_embed_rms(p(ids), p(table), p(blocks[0].layer[0].layer_norm.weight), p(x), p(h), T, D,
-                                      c.vocab_size, eps, dt, st()), "mdm_t5_embed_rms")
+        if learned is None:
+            _lib.check(L.mdm_t5_embed_rms(p(ids), p(table), p(blocks[0].layer[0].layer_norm.weight), p(x), p(h), T, D,
+                                          c.vocab_size, eps, dt, st()), "mdm_t5_embed_rms")
+        else:
+            if learned.device != dev or learned.dtype != torch.float32 or not learned.is_contiguous():
+                raise _lib.MdmHipError("the textual-inversion embeddings must be contiguous fp32 on the encoder's device (%s), "
+                                       "got %s on %s" % (dev, learned.dtype, learned.device))
+            slot_of_id = self._adapter._slot_table(dev)
+            _lib.check(L.mdm_t5_embed_rms_slots(p(ids), p(table), p(slot_of_id), p(learned), p(blocks[0].layer[0].layer_norm.weight),
+                                                p(x), p(h), T, D, c.vocab_size, int(slot_of_id.numel()), int(learned.shape[0]),
+                                                eps, dt, st()), "mdm_t5_embed_rms_slots")
+        layers = []
         for l in range(c.num_layers):
             wqkv, wo, wi, wo_ff = packs[l]
+            if save is not None:
+                xa, qkv, att, u, lse = x.clone(), new(3 * inner), new(inner), new(2 * F), torch.empty(H, T, device=dev)
             gemm(h, wqkv, qkv, D, 3 * inner)
-            _lib.check(L.mdm_t5_attn_fwd(p(qkv), p(seq_start), p(pos), p(bias), p(att), B, T, S, pk["max_len"], H, dk, dt,
-                                         st()), "mdm_t5_attn_fwd")
+            if save is None:
+                _lib.check(L.mdm_t5_attn_fwd(p(qkv), p(seq_start), p(pos), p(bias), p(att), B, T, S, pk["max_len"], H, dk, dt,
+                                             st()), "mdm_t5_attn_fwd")
+            else:
+                _lib.check(L.mdm_t5_attn_fwd_lse(p(qkv), p(seq_start), p(pos), p(bias), p(att), p(lse), B, T, S, pk["max_len"],
+                                                 H, dk, dt, st()), "mdm_t5_attn_fwd_lse")
             gemm(att, wo, delta, inner, D)
             _lib.check(L.mdm_t5_add_rms(p(x), p(delta), p(blocks[l].layer[1].layer_norm.weight), p(h), T, D, eps, dt, st()),
                        "mdm_t5_add_rms")
+            if save is not None:
+                layers.append((xa, x.clone(), qkv, att, lse, u))
             gemm(h, wi, u, D, 2 * F)
             _lib.check(L.mdm_t5_gated_gelu(p(u), p(y), T, F, dt, st()), "mdm_t5_gated_gelu")
             gemm(y, wo_ff, delta, F, D)
@@ -298,7 +387,97 @@ class T5Encoder(nn.Module):
                                             st()), "mdm_t5_add_rms")
         _lib.check(L.mdm_t5_final_rms(p(x), p(delta), p(self.encoder.final_layer_norm.weight), p(src), p(out), B * S, D, eps,
                                       dt, st()), "mdm_t5_final_rms")
+        if save is not None:
+            save.update(dtype=dtype, layers=layers, delta=delta, bias=bias)
         return out
+
+    def _backward(self, plan, saved, dout):
+        """d loss / d learned [P, D] from d loss / d out [B, S, D]: the reverse chain of ``_launch``, input gradients only
+        (per layer four GEMMs on the input-gradient packs -- one for each of the forward's, which packs Wq|Wk|Wv and
+        Wi0|Wi1 as one weight each -- and the attention, gated GELU and RMS backward of csrc/text_encoder_bwd.hip)"""
+        c = self.config
+        ti = self._adapter
+        pk, B, S, T, dev = plan["pk"], plan["B"], plan["S"], plan["T"], plan["dev"]
+        D, H, dk, F, eps = c.d_model, c.num_heads, c.d_kv, c.d_ff, float(c.layer_norm_epsilon)
+        inner = H * dk
+        dtype = saved["dtype"]
+        dt = ops.F32 if dtype == torch.float32 else ops.BF16
+        dpacks = self._layer_dpacks(dtype)
+        L, p, st = _lib.lib(), ops._p, ops._stream
+        dout = ops._c(dout.float())
+        new = lambda n, t=dtype: torch.empty(T, n, dtype=t, device=dev)
+        dx = new(D, torch.float32)
+        # the stream gradient as a GEMM operand: dx itself in fp32, a storage-type copy written by the norm kernels in bf16
+        g = dx if dtype == torch.float32 else new(D)
+        glo = None if dtype == torch.float32 else g
+        dh, dy, du, datt, dqkv = new(D), new(F), new(2 * F), new(inner), new(3 * inner)
+        flat = plan["flat"]
+
+        def dgemm(a, w, yout, k, n):     # yout [T, n] = a [T, k] @ W [k, n], W the forward's weight as the dgrad pack holds it
+            ops._conv_launch(a, w, None, None, None, yout, None, T, 1, 1, k, 1, 1, n, 1, 1, 0, 0)
+
+        blocks = self.encoder.block
+        layers = saved["layers"]
+        _lib.check(L.mdm_t5_final_rms_bwd(p(layers[-1][1]), p(saved["delta"]), p(self.encoder.final_layer_norm.weight), p(dout),
+                                          p(flat), p(dx), p(glo), T, D, eps, dt, st()), "mdm_t5_final_rms_bwd")
+        for l in reversed(range(c.num_layers)):
+            xa, xb, qkv, att, lse, u = layers[l]
+            dwqkv, dwo, dwi, dwo_ff = dpacks[l]
+            dgemm(g, dwo_ff, dy, D, F)
+            _lib.check(L.mdm_t5_gated_gelu_bwd(p(u), p(dy), p(du), T, F, dt, st()), "mdm_t5_gated_gelu_bwd")
+            dgemm(du, dwi, dh, 2 * F, D)
+            _lib.check(L.mdm_t5_rms_bwd(p(xb), p(blocks[l].layer[1].layer_norm.weight), p(dh), p(dx), p(glo), T, D, eps, dt,
+                                        st()), "mdm_t5_rms_bwd")
+            dgemm(g, dwo, datt, D, inner)
+            _lib.check(L.mdm_t5_attn_bwd(p(qkv), p(att), p(lse), p(datt), p(plan["seq_start"]), p(plan["pos"]), p(saved["bias"]),
+                                         p(dqkv), B, T, S, pk["max_len"], H, dk, dt, st()), "mdm_t5_attn_bwd")
+            dgemm(dqkv, dwqkv, dh, 3 * inner, D)
+            _lib.check(L.mdm_t5_rms_bwd(p(xa), p(blocks[l].layer[0].layer_norm.weight), p(dh), p(dx), p(glo), T, D, eps, dt,
+                                        st()), "mdm_t5_rms_bwd")
+        slot_start, tokens = ti._slot_index(plan, dev)
+        P = len(ti.token_ids)
+        dlearned = torch.empty(P, D, dtype=torch.float32, device=dev)
+        _lib.check(L.mdm_t5_embed_bwd(p(dx), p(slot_start), p(tokens), p(dlearned), P, D, int(tokens.numel()), T, st()),
+                   "mdm_t5_embed_bwd")
+        return dlearned
+
+
+class _T5EncoderGradFn(torch.autograd.Function):
+    """The encoder as ONE autograd node whose only differentiable input is the [P, D] parameter of the attached textual
+    inversion: the forward is the inference launch sequence (same bits), the backward ``T5Encoder._backward``."""
+
+    @staticmethod
+    def forward(ctx, embeddings, enc, input_ids, attention_mask):
+        plan = enc._plan(input_ids, attention_mask, flat=True)
+        saved = {}
+        if plan["T"]:
+            enc._layer_dpacks(compute_dtype())     # the input-gradient packs: built on the first differentiable forward
+        out = enc._launch(plan, ops._c(embeddings.detach()), saved)
+        ti = enc._adapter
+        # the plan and the slot index of the backward are built from the adapter as it is now: remember which it was
+        ctx.enc, ctx.plan, ctx.saved, ctx.adapter, ctx.token_ids = enc, plan, saved, ti, tuple(ti.token_ids)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        enc, plan, saved = ctx.enc, ctx.plan, ctx.saved
+        ti = enc._adapter
+        if ti is not ctx.adapter:
+            raise _lib.MdmHipError("the textual inversion was detached (or another attached) between this forward and its "
+                                   "backward")
+        if tuple(ti.token_ids) != ctx.token_ids:
+            raise _lib.MdmHipError("the token_ids of the textual inversion changed between this forward and its backward "
+                                   "(load_state_dict?): %s then, %s now -- run the forward again"
+                                   % (list(ctx.token_ids), list(ti.token_ids)))
+        if saved is None:
+            raise _lib.MdmHipError("this forward of the T5Encoder was already backpropagated through: its saved activations "
+                                   "are freed after the first backward, retain_graph=True or not -- run the forward again")
+        ctx.saved = None
+        if plan["T"] == 0:
+            return torch.zeros_like(ti.embeddings), None, None, None
+        return enc._backward(plan, saved, dout), None, None, None
+
 
 
 class LanguageModel(nn.Module):
