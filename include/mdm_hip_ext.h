@@ -170,6 +170,45 @@ int mdm_t5_embed_rms_slots(const int* ids, const float* table, const int* slot_o
 int mdm_t5_embed_bwd(const float* dx0, const int* slot_start, const int* tokens, float* dlearned, int P, int D, int n, int T,
                      void* stream);
 
+/* mdm_sampler_step_sa -- one step of SA-Solver (Xue et al., NeurIPS 2023, "SA-Solver: Stochastic Adams Solver for Fast
+ * Sampling of Diffusion Models") on fp32 NCHW [B, chw] images, per scale and per sample: an exponential Adams-Bashforth
+ * predictor and an Adams-Moulton corrector on the data prediction, with a noise level tau between the probability-flow ODE
+ * (tau = 0) and the reverse SDE (tau = 1).  alpha = sqrt(gamma), sigma = sqrt(1 - gamma), lambda = log(alpha / sigma); a step
+ * from node a (gamma) to node b (gamma_last), h = lambda_b - lambda_a > 0, kappa = 1 + tau^2; m_j the guided, thresholded x0
+ * formed at node j (guidance combine, x0 and clip 0 / 1 / 2 exactly as mdm_sampler_step_2m); l_j the Lagrange basis over the
+ * nodes' offsets s_j = lambda_j - lambda_a:
+ *   x_b = (sigma_b / sigma_a) e^{-tau^2 h} x_a + alpha_b sum_j c_j m_j + sigma_b sqrt(-expm1(-2 tau^2 h)) z
+ *   c_j = kappa int_0^h e^{-kappa (h - s)} l_j(s) ds                       (sum_j c_j = -expm1(-kappa h))
+ * Predictor of order p <= 3: nodes a, a-1, .., a-p+1.  Corrector of order k <= 3: the step a-1 -> a once more, now that m_a
+ * is known, over nodes a, .., a-k+1 with the same x_{a-1} term and the same noise -- so it is a difference,
+ *   x_a <- x_a - psum_a + alpha_a sum_j c^c_j m_j,      psum_a = alpha_a sum_j c^p_j m_j  stored by the launch before,
+ * and whatever was done to x_a after that launch (a known-region blend) survives it.  One launch at node a:
+ *   m_a from (x_t, pred) ; correct x_t ; predict x_b -> x_last_out ; psum <- psum_b ; h1 <- h0, h0 <- m_a ; x0_out <- m_a
+ * h0 / h1: m_{a-1} / m_{a-2}, formed at gamma_h0 / gamma_h1 ([B] each).  h0, h1 and psum are updated IN PLACE; a thread reads
+ * its elements before it writes them, and x0_out may be h0 itself.  x_last_out aliases nothing.
+ * gate: DEVICE float[4] = {predictor order, corrector order, tau, tau of the step the corrector redoes}, so that one captured
+ * graph serves every step.  (The fourth entry is there because tau may differ between neighbouring steps, tau_interval, and the
+ * corrector's coefficients belong to the step before.)  The orders are clamped to [1, max_predictor] and [0, max_corrector],
+ * the host's ceilings, which also say which buffers must be given: gamma_h0 for max_predictor >= 2 or max_corrector >= 1, h0
+ * for either >= 2, h1 and gamma_h1 for either >= 3, psum for max_corrector >= 1 (NULL otherwise: then not written either).
+ * The gate SELECTS: history and gammas behind an order that is off are not read, NaN in them reaches no output.
+ * A sample with gamma_last == 1 (the last step, h = inf) takes predictor order 1, tau = 0 and no corrector whatever the gate
+ * says: x_last_out = x0_out = m_a bit for bit, no logarithm is evaluated, no history is read, no normal is drawn.
+ * z: noise[] if given, else drawn in the kernel from rng_state / rng_stream (Philox, element i as mdm_sampler_step and
+ * mdm_randn; the caller advances the state); with neither, tau counts as 0.  With tau == 0 neither is read.
+ * Coefficients: on the device, in fp64, once per block (a block works on one sample): lambda differences as
+ * log1p((g_b - g_a) / (g_a (1 - g_b))) / 2, the moments of the integral by their series below kappa h = 1 and by the recurrence
+ * phi_n = 1 - (n / x) phi_{n-1} above -- 1e-6 relative or better against quadrature for h in [1e-4, 8].
+ * chw % 4 == 0, 16-byte accesses, no allocation, no workspace, no host sync, no atomics: capturable, two runs are bit-identical,
+ * and a row's bits do not depend on the rows beside it.  Invalid host arguments (a ceiling outside 1..3 / 0..3, a missing or
+ * aliased buffer): a negative status, nothing launched.  What lives on the device is not checked: gamma_last > gamma is the
+ * caller's to keep wherever the sample is not on its last step. */
+int mdm_sampler_step_sa(const float* x_t, const float* pred, const float* pred_uncond, float guidance, const float* gamma,
+                        const float* gamma_last, const float* gamma_h0, const float* gamma_h1, const float* gate,
+                        const float* thr, const float* noise, const unsigned long long* rng_state, int rng_stream, float* h0,
+                        float* h1, float* psum, float* x0_out, float* x_last_out, int B, size_t chw, int pred_type, int clip,
+                        float image_scale, int max_predictor, int max_corrector, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

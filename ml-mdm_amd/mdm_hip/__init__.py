@@ -6,7 +6,7 @@ Layout of the package
   unet.py         UNet, config dataclasses (mirror of ml_mdm.models.unet)
   nested_unet.py  NestedUNet (mirror of ml_mdm.models.nested_unet)
   diffusion.py    Diffusion / NestedDiffusion train-step + sampling call surface
-  samplers.py     noise schedules + DDPM/DDIM updates; LossGuide: loss-guided (DPS) sampling through the model's input gradient;
+  samplers.py     noise schedules + DDPM/DDIM updates, DPM-Solver++(2M), SASolver (SA-Solver: predictor-corrector); LossGuide: loss-guided (DPS) sampling through the model's input gradient;
                   SampleOptions: the sampling options beyond the reference, their checks and what they compose with
   configs.py      the three shipped architectures (cc12m 64 / 256 / 1024)
   distributed.py  one-process-per-GPU data parallel gradient reducer over RCCL
@@ -49,7 +49,7 @@ from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
 from . import lora  # noqa: F401,E402
 from . import fp8  # noqa: F401,E402
 from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
-from .samplers import LossGuide  # noqa: F401,E402
+from .samplers import LossGuide, SASolver  # noqa: F401,E402
 from . import pag  # noqa: F401,E402
 from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
@@ -88,4 +88,5 @@ __all__ = [
     "enable_activation_recompute",
     "activation_recompute_enabled",
     "LossGuide",
+    "SASolver",
 ]

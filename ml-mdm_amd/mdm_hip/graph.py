@@ -22,8 +22,8 @@ import torch.nn as nn
 
 from . import ops, regions as _regions
 from . import tiling as _tiling
-from .samplers import (SampleOptions, _check_known, _check_solver, gather_windows, merge_windows, model_rows, repeat_rows,
-                       split_rows)
+from .samplers import (SASolver, SampleOptions, _check_known, _check_solver, _solver_of, gather_windows, merge_windows,
+                       model_rows, repeat_rows, split_rows)
 from .unet import switch_state, switchable
 
 
@@ -112,7 +112,11 @@ class GraphedSampler:
     dynamic ones: x0 kernel -> ``ops.abs_quantile``, a radix select of five launches whose workspace -- 35 KB per sample --
     lives in the graph's pool, -> update kernel, all inside the graph; no sort), or ``solver="dpmpp_2m"``
     (DPM-Solver++(2M): deterministic, the x0 history of every scale lives in a static buffer that the step kernel updates
-    in place, the order flag of each step comes from a device table).  The ancestral noise comes
+    in place, the order flag of each step comes from a device table), or ``solver=SASolver(...)`` / ``"sa"`` (SA-Solver: the
+    gate {predictor order, corrector order, tau, tau of the step before} of every step and the times of the two steps before
+    come from device tables, h0 / h1 / psum of every scale live in static buffers the step kernel updates in place; with
+    tau == 0 nothing is drawn and the generator is never touched, with tau > 0 every row draws from it and advances it, the
+    gate deciding whether the noise is added -- as the DDPM path does with its noise gate).  The ancestral noise comes
     from the library's counter-based generator (``ops.DeviceRng``, replayable on the host); the START noise is drawn
     like the eager path (CPU generator for the top scale, reference diffusion.py:177), or passed in.
 
@@ -187,7 +191,20 @@ class GraphedSampler:
         x_static = [x.clone() for x in xs]
         # dpmpp_2m: the x0 of the step before, per scale.  Read only where the order gate is on, so what a warm-up pass or
         # an earlier sample() call left in it is never seen: step 0 (gate off) rewrites it
-        x0_prev = [torch.zeros_like(x) for x in xs] if solver is not None else None
+        x0_prev = [torch.zeros_like(x) for x in xs] if solver == "dpmpp_2m" else None
+        # an SASolver: h0 / h1 / psum per scale, updated in place by the step kernel and read only where the gate's orders
+        # are on; the gate {predictor order, corrector order, tau, tau of the step before} of every row (sample() fills the
+        # rows it replays; until then first order without corrector, what the warm-up passes run with) and the time two
+        # steps back.  Noise is drawn from the generator, and the generator advanced, only if the solver's tau > 0
+        sa = solver if isinstance(solver, SASolver) else None
+        sa_bufs = tab_sa = tab_p1 = None
+        if sa is not None:
+            top = max(sa.predictor, sa.corrector)
+            sa_bufs = dict(h0=[torch.zeros_like(x) for x in xs],
+                           h1=[torch.zeros_like(x) if top >= 3 else None for x in xs],
+                           psum=[torch.zeros_like(x) if sa.corrector >= 1 else None for x in xs])
+            tab_sa = torch.tensor([[1.0, 0.0, 0.0, 0.0]] * len(t_host), dtype=torch.float32, device=dev)
+            tab_p1 = torch.as_tensor(np.concatenate((t_host[:1], t_host[:1], t_host[:-2]))[:len(t_host)].copy()).to(dev)
         # cfg: the momentum history per scale and the two gate tables, one row per replay; sample() fills the tables for
         # the rows it replays.  Until then: guidance on, no history -- what the warm-up passes (row 0) run with
         cfg_state = cfg_run_gate = cfg_w_gate = None
@@ -212,7 +229,11 @@ class GraphedSampler:
             gammas = lambda time: smp._gammas_of_scales(model, smp.gammas.index_select(0, time).expand(B))
             g_t, g_s = gammas(t), gammas(s)
             history = {}
-            if solver is not None:   # the history lives in x0_prev: the step kernel updates it in place
+            if sa is not None:   # x0 goes straight into h0 (the kernel reads its elements of h0 before it writes them)
+                history = dict(sa_gate=tab_sa.index_select(0, idx), x0_out=sa_bufs["h0"],
+                               sa_state=dict(sa_bufs, g0=gammas(tab_p.index_select(0, idx)),
+                                             g1=gammas(tab_p1.index_select(0, idx))))
+            elif solver is not None:   # the history lives in x0_prev: the step kernel updates it in place
                 history = dict(second_order=tab_order.index_select(0, idx), g_prev=gammas(tab_p.index_select(0, idx)),
                                x0_prev=x0_prev, x0_out=x0_prev)
             times = (t - 1).expand(B)
@@ -279,8 +300,8 @@ class GraphedSampler:
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
                    t_host=t_host, order=tab_order, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
-                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate,
-                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev, cfg_state))
+                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, sa_gate=tab_sa,
+                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev, cfg_state, sa_bufs, tab_p1))
         self._graphs[key] = ent
         return ent
 
@@ -311,7 +332,10 @@ class GraphedSampler:
         ``known_images`` / ``known_mask`` / ``resample`` / ``known_seed``: as ``Sampler._sample``; whether a scale has a
         known image, and ``resample``, are part of the graph key.  ``start_step=t``: replay only the rows whose time is
         <= t, from ``start_noise`` = the image noised to the first of them (``Diffusion.partial_diffusion(...,
-        graphed=self)`` does the noising); the first replayed row of ``dpmpp_2m`` is first order, as in the eager sampler."""
+        graphed=self)`` does the noising); the first replayed row of ``dpmpp_2m`` is first order, as in the eager sampler.
+        ``solver=SASolver(...)`` (``"sa"``: the defaults): its fields are part of the graph key; every call writes the gate
+        table for the rows it replays, counted from its first row, so a late start restarts the orders; with ``tau > 0``
+        ``seed`` seeds the noise."""
         opts = SampleOptions(**options)
         if opts.guide is not None:
             raise NotImplementedError("GraphedSampler does not take guide=: loss-guided sampling calls an arbitrary user "
@@ -320,6 +344,11 @@ class GraphedSampler:
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
         opts.check()
+        solver = _solver_of(solver)
+        sa = solver if isinstance(solver, SASolver) else None
+        if sa is not None:   # a schedule with a repeated time has a step of h = 0: refused before anything is captured
+            st = self.sampler.set_timesteps(int(num_inference_steps))
+            sa.gates(st[:-1], st[1:], self.sampler.n_steps)
         cfg = opts.cfg_at(guidance_scale)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
@@ -401,10 +430,17 @@ class GraphedSampler:
             run_on[first:] = seen > 0
             ent["cfg_w_gate"].copy_(torch.from_numpy(w_on))
             ent["cfg_run_gate"].copy_(torch.from_numpy(run_on))
+        if sa is not None and first < ent["n"]:
+            # the gate of every row this call replays, counted from its first row: a late start restarts the orders
+            th = ent["t_host"]
+            gates = np.zeros((ent["n"], 4), dtype="float32")
+            gates[:, 0] = 1
+            gates[first:] = sa.gates(th[first:], np.concatenate((th[1:], [0]))[first:], smp.n_steps)
+            ent["sa_gate"].copy_(torch.from_numpy(gates))
         if seed is not None:
             ent["rng"].state.copy_(torch.tensor([seed & (2**63 - 1), 0], dtype=torch.int64))
         # dpmpp_2m from a late start: there is no history at the first replayed row -- its order gate is off for this call
-        order_row = ent["order"][first:first + 1] if (solver is not None and first > 0) else None
+        order_row = ent["order"][first:first + 1] if (solver == "dpmpp_2m" and first > 0) else None
         if order_row is not None:
             saved = order_row.clone()
             order_row.zero_()

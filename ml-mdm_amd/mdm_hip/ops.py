@@ -2616,6 +2616,69 @@ def sampler_step_2m(x_t, pred, g, g_last, prediction_type, g_prev=None, x0_prev=
     return x0, xl
 
 
+_SA_GATES = {}   # (device, (p, c, tau, tau_corr)) -> device float[4]: an eager trajectory meets a handful of them
+
+
+def sa_gate(device, predictor, corrector, tau=0.0, tau_corr=0.0):
+    """the device float[4] gate of ``sampler_step_sa`` for host values, checked and cached per device"""
+    if int(predictor) != predictor or not 1 <= predictor <= 3:
+        raise ValueError("sampler_step_sa: predictor order %r (wanted 1, 2 or 3)" % (predictor,))
+    if int(corrector) != corrector or not 0 <= corrector <= 3:
+        raise ValueError("sampler_step_sa: corrector order %r (wanted 0 .. 3)" % (corrector,))
+    if not (tau >= 0 and tau_corr >= 0):
+        raise ValueError("sampler_step_sa: tau = %r, %r (wanted >= 0)" % (tau, tau_corr))
+    key = (torch.device(device), (int(predictor), int(corrector), float(tau), float(tau_corr)))
+    gate = _SA_GATES.get(key)
+    if gate is None:
+        gate = _SA_GATES[key] = torch.tensor(key[1], dtype=torch.float32, device=device)
+    return gate
+
+
+def sampler_step_sa(x_t, pred, g, g_last, prediction_type, gate, h0=None, h1=None, psum=None, g_h0=None, g_h1=None,
+                    max_predictor=3, max_corrector=3, noise=None, rng=None, rng_stream=0, clip="CLIP", image_scale=1.0,
+                    pred_uncond=None, guidance_scale=1.0, thr=None, x0_out=None):
+    """One SA-Solver update (Xue et al. 2023; include/mdm_hip_ext.h has the definition) as ONE kernel -> (x0, x_last).
+    ``gate``: (predictor order, corrector order, tau, tau of the corrected step) as host numbers, or a device float[4]
+    so that one captured graph serves every step; the orders are clamped to ``max_predictor`` / ``max_corrector``, which
+    also say which of the state the call needs.  ``h0`` / ``h1``: the x0 of the two steps before, formed at ``g_h0`` /
+    ``g_h1``; ``psum``: the predictor's sum the launch before stored.  All three are updated IN PLACE (h1 <- h0,
+    h0 <- x0, psum <- this launch's sum).  ``x0_out`` may be ``h0`` itself.  ``noise``, or ``rng`` (drawn in the kernel;
+    the caller advances it by ``x_t.numel()``): the z of tau > 0; with neither, tau counts as 0.
+    ``clip``: as ``sampler_step_2m``."""
+    x_t, pred = _img(x_t), _img(pred)
+    B = x_t.shape[0]
+    chw = x_t.numel() // B
+    g, gl = _vec(g, B), _vec(g_last, B)
+    pu = _img(pred_uncond) if pred_uncond is not None else None
+    nz = _img(noise) if noise is not None else None
+    th = _vec(thr, B) if thr is not None else None
+    cm = {"NONE": 0, "CLIP": 1, "DYNAMIC": 2}[clip]
+    if int(max_predictor) != max_predictor or int(max_corrector) != max_corrector:
+        raise _lib.MdmHipError("sampler_step_sa: orders are integers (got %r, %r)" % (max_predictor, max_corrector))
+    if torch.is_tensor(gate):
+        gate = _c(gate.detach().reshape(-1).float())
+        _require_gpu(gate)
+        if gate.numel() != 4:
+            raise _lib.MdmHipError("sampler_step_sa: the gate is a device float[4] (got %d values)" % gate.numel())
+    else:
+        gate = sa_gate(x_t.device, *gate)
+    state = lambda t, what: None if t is None else _inplace_img(t, x_t, "sampler_step_sa: " + what)
+    h0, h1, psum = state(h0, "h0"), state(h1, "h1"), state(psum, "psum")
+    g0 = _vec(g_h0, B) if g_h0 is not None else None
+    g1 = _vec(g_h1, B) if g_h1 is not None else None
+    x0 = torch.empty_like(x_t) if x0_out is None else _inplace_img(x0_out, x_t, "sampler_step_sa: x0_out")
+    xl = torch.empty_like(x_t)
+    _lib.check(
+        _lib.lib().mdm_sampler_step_sa(_p(x_t), _p(pred), _p(pu), float(guidance_scale), _p(g), _p(gl), _p(g0), _p(g1),
+                                       _p(gate), _p(th), _p(nz), _p(rng.state) if rng is not None else None,
+                                       int(rng_stream), _p(h0), _p(h1), _p(psum), _p(x0), _p(xl), B, chw,
+                                       _ptype(prediction_type), cm, float(image_scale) if image_scale else 1.0,
+                                       int(max_predictor), int(max_corrector), _stream()),
+        "mdm_sampler_step_sa",
+    )
+    return x0, xl
+
+
 def _inplace_img(t, like, what):
     """an fp32, contiguous GPU tensor shaped like ``like`` that a kernel writes through its own pointer (no copy made)"""
     if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != like.shape:

@@ -16,7 +16,9 @@ tensors, broadcast, instead of being materialised at full image size (:196-199).
 
 Beyond the reference: ``sample(..., solver="dpmpp_2m")`` replaces the first-order update by
 DPM-Solver++(2M) (Lu et al. 2022; ``get_prediction_xt_last_2m`` -> ``ops.sampler_step_2m``),
-same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors.  So does image conditioning:
+same structure -- one kernel per scale on GPU tensors, torch ops on CPU tensors; ``solver=SASolver(...)`` / ``"sa"`` by
+SA-Solver (Xue et al. 2023; ``get_prediction_xt_last_sa`` -> ``ops.sampler_step_sa``), a stochastic Adams
+predictor-corrector of up to third order, the same way.  So does image conditioning:
 ``sample(..., known_images=, known_mask=, resample=, known_seed=)`` holds a region of every trajectory on a given image
 (the replacement method of RePaint, Lugmayr et al. 2022, with its resampling jumps; ``KnownRegion`` ->
 ``ops.sampler_known_blend`` / ``ops.sampler_jump``), and ``Diffusion.partial_diffusion`` starts a trajectory late from a
@@ -153,16 +155,160 @@ def _b(v):
     return v.reshape(-1, 1, 1, 1)
 
 
-SOLVERS = ("dpmpp_2m",)
+SOLVERS = ("dpmpp_2m", "sa")
+
+
+@dataclass(frozen=True)
+class SASolver:
+    """``solver=SASolver(predictor=3, corrector=3, tau=0.0, tau_interval=None)``: SA-Solver (Xue et al., NeurIPS 2023,
+    "SA-Solver: Stochastic Adams Solver for Fast Sampling of Diffusion Models"); ``solver="sa"`` means the defaults.
+
+    On the data prediction, per scale and per sample, with alpha = sqrt(gamma), sigma = sqrt(1 - gamma), lambda =
+    log(alpha / sigma), a step from node a to node b of h = lambda_b - lambda_a, kappa = 1 + tau^2, m_j the guided,
+    thresholded x0 formed at node j and l_j the Lagrange basis over the offsets s_j = lambda_j - lambda_a:
+
+        x_b = (sigma_b / sigma_a) e^{-tau^2 h} x_a + alpha_b sum_j c_j m_j + sigma_b sqrt(-expm1(-2 tau^2 h)) z
+        c_j = kappa int_0^h e^{-kappa (h - s)} l_j(s) ds
+
+    ``predictor`` = P in 1..3: exponential Adams-Bashforth over nodes a, a-1, .., of order min(P, i + 1) at launch i of a
+    trajectory.  ``corrector`` = C in 0..3 (0 = none): Adams-Moulton -- the step a-1 -> a redone over nodes a, a-1, ..
+    once m_a is known, which is the denoiser call the next step makes anyway: no extra evaluation.  Off at i = 0, order
+    min(C, i + 1) afterwards.  It shares the x_{a-1} term and the noise with the predictor, so it is applied as a
+    difference and whatever was done to x_a after the step (the known-region blend) survives it.
+    ``tau`` >= 0: 0 is the probability-flow ODE, 1 the reverse SDE (first order: DDIM(eta = 0) and DDIM(eta = 1)).
+    ``tau_interval = (lo, hi)`` in fractions of ``num_diffusion_steps``: tau acts where lo <= t / T <= hi for the time t
+    the step starts from, 0 outside; None = everywhere.
+    The last step (to gamma = 1) is first order with tau = 0 and no corrector: x = x0.  A late start restarts the count."""
+
+    predictor: int = 3
+    corrector: int = 3
+    tau: float = 0.0
+    tau_interval: object = None
+
+    def __post_init__(self):
+        if isinstance(self.predictor, bool) or int(self.predictor) != self.predictor or not 1 <= self.predictor <= 3:
+            raise ValueError("SASolver: predictor = %r (wanted 1, 2 or 3)" % (self.predictor,))
+        if isinstance(self.corrector, bool) or int(self.corrector) != self.corrector or not 0 <= self.corrector <= 3:
+            raise ValueError("SASolver: corrector = %r (wanted 0 .. 3; 0 = no corrector)" % (self.corrector,))
+        if not (math.isfinite(self.tau) and self.tau >= 0):
+            raise ValueError("SASolver: tau = %r (wanted a finite number >= 0)" % (self.tau,))
+        object.__setattr__(self, "predictor", int(self.predictor))
+        object.__setattr__(self, "corrector", int(self.corrector))
+        object.__setattr__(self, "tau", float(self.tau))
+        if self.tau_interval is not None:
+            try:
+                lo, hi = self.tau_interval
+                lo, hi = float(lo), float(hi)
+            except (TypeError, ValueError):
+                raise ValueError("SASolver: tau_interval = %r (wanted (lo, hi) in fractions of the schedule, or None)"
+                                 % (self.tau_interval,))
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+                raise ValueError("SASolver: tau_interval = %r (wanted finite lo <= hi)" % (self.tau_interval,))
+            object.__setattr__(self, "tau_interval", (lo, hi))
+
+    def tau_at(self, time_step, num_diffusion_steps):
+        """tau of the step that starts at schedule time ``time_step``"""
+        if self.tau_interval is None:
+            return self.tau
+        inside = self.tau_interval[0] <= float(time_step) / float(num_diffusion_steps) <= self.tau_interval[1]
+        return self.tau if inside else 0.0
+
+    def gate(self, count, time_step, time_step_last, num_diffusion_steps, tau_prev=0.0):
+        """-> (predictor order, corrector order, tau, tau of the step before) of launch ``count`` (0 = the first of this
+        trajectory), a step from ``time_step`` to ``time_step_last`` (0: the last step)"""
+        if int(time_step_last) >= int(time_step):
+            raise ValueError("SASolver: a step from time %d to time %d has no positive step in log-SNR (more inference "
+                             "steps than the schedule has?)" % (int(time_step), int(time_step_last)))
+        if int(time_step_last) == 0:
+            return (1, 0, 0.0, 0.0)
+        c = 0 if count == 0 else min(self.corrector, count + 1)
+        return (min(self.predictor, count + 1), c, self.tau_at(time_step, num_diffusion_steps), float(tau_prev) if c else 0.0)
+
+    def gates(self, times, times_last, num_diffusion_steps):
+        """the gates of a whole trajectory over the steps ``times`` -> ``times_last`` (host arrays): a list of 4-tuples"""
+        out, tau_prev = [], 0.0
+        for i, (t, s) in enumerate(zip(times, times_last)):
+            out.append(self.gate(i, int(t), int(s), num_diffusion_steps, tau_prev))
+            tau_prev = out[-1][2]
+        return out
+
+
+def _solver_of(solver):
+    """``solver=`` as given -> None, "dpmpp_2m" or an ``SASolver`` ("sa": the defaults)"""
+    return SASolver() if isinstance(solver, str) and solver == "sa" else solver
 
 
 def _check_solver(solver, ddim_eta):
     if solver is None:
         return
-    if solver not in SOLVERS:
-        raise ValueError("unknown solver %r (known: %s; None = DDPM / DDIM)" % (solver, ", ".join(SOLVERS)))
+    if not isinstance(solver, SASolver) and (not isinstance(solver, str) or solver not in SOLVERS):
+        raise ValueError("unknown solver %r (known: %s, or an SASolver; None = DDPM / DDIM)" % (solver, ", ".join(SOLVERS)))
     if ddim_eta is not None:
-        raise ValueError("solver=%r is deterministic and takes no ddim_eta (got %r)" % (solver, ddim_eta))
+        raise ValueError("solver=%r has no ddim_eta (got %r): dpmpp_2m is deterministic, SASolver takes tau="
+                         % (solver, ddim_eta))
+
+
+def _check_sa(solver, opts):
+    if isinstance(_solver_of(solver), SASolver) and opts.guide is not None:
+        raise NotImplementedError("guide= together with an SA solver: the guide's correction of x_s between the predictor "
+                                  "and the corrector that redoes the step is not implemented")
+
+
+def _dlambda(ga, gb):
+    """lambda(gb) - lambda(ga) for lambda = log(sqrt(g) / sqrt(1 - g)), without cancellation (as the 2M update takes it)"""
+    return 0.5 * torch.log1p((gb - ga) / (ga * (1 - gb)))
+
+
+def _sa_phi(x):
+    """phi_n(x) = x int_0^1 e^{-x (1 - u)} u^n du for n = 0, 1, 2 (x > 0): the moments of the SA-Solver integral in units
+    of h^n.  Below x = 1 the series n! sum_k (-1)^k x^(k+1) / (n + k + 1)! in nested form (20 terms, no cancellation),
+    from there on phi_0 = -expm1(-x), phi_n = 1 - (n / x) phi_{n-1} -- what the kernel does in fp64."""
+    small = x < 1
+    xs = torch.where(small, x, torch.ones_like(x))
+    series = []
+    for n in range(3):
+        s = torch.ones_like(xs)
+        for k in range(19, 0, -1):
+            s = 1 - xs * s / (n + k + 1)
+        series.append(xs * s / (n + 1))
+    xl = torch.where(small, torch.ones_like(x), x)
+    p0 = -torch.expm1(-xl)
+    p1 = 1 - p0 / xl
+    p2 = 1 - 2 * p1 / xl
+    return [torch.where(small, a, b) for a, b in zip(series, (p0, p1, p2))]
+
+
+def sa_predictor_coeffs(h, tau, order, h1=None, h2=None):
+    """c_j of the SA-Solver predictor for a step of ``h`` in lambda from node a: (c_a, c_{a-1}, c_{a-2}) (zeros beyond
+    ``order``), ``h1`` = lambda_a - lambda_{a-1}, ``h2`` = lambda_{a-1} - lambda_{a-2}.  Tensors of one shape, fp64 for
+    full accuracy; ``tau`` and ``order`` host numbers."""
+    phi = _sa_phi((1 + tau * tau) * h)
+    zero = torch.zeros_like(h)
+    if order == 1:
+        return phi[0], zero, zero
+    u1 = -h1 / h
+    if order == 2:
+        c1 = phi[1] / u1
+        return phi[0] - c1, c1, zero
+    u2 = u1 - h2 / h
+    c1 = (phi[2] - u2 * phi[1]) / (u1 * (u1 - u2))
+    c2 = (phi[2] - u1 * phi[1]) / (u2 * (u2 - u1))
+    return phi[0] - c1 - c2, c1, c2
+
+
+def sa_corrector_coeffs(h, tau, order, h2=None):
+    """c_j of the SA-Solver corrector for the step of ``h`` in lambda from node a-1 to node a, taken at ``tau``:
+    (c_a, c_{a-1}, c_{a-2}) (zeros beyond ``order``), ``h2`` = lambda_{a-1} - lambda_{a-2}"""
+    phi = _sa_phi((1 + tau * tau) * h)
+    zero = torch.zeros_like(h)
+    if order == 1:
+        return phi[0], zero, zero
+    if order == 2:
+        return phi[1], phi[0] - phi[1], zero
+    u2 = -h2 / h
+    ca = (phi[2] - u2 * phi[1]) / (1 - u2)
+    c2 = (phi[2] - phi[1]) / (u2 * (u2 - 1))
+    return ca, phi[0] - ca - c2, c2
 
 
 def _check_known(known_images, resample, solver):
@@ -812,6 +958,77 @@ class Sampler(nn.Module):
         x_last = ratio * x_t + (g_last.sqrt() - ratio * g.sqrt()) * D
         return x0, x_last
 
+    # ---- one step of SA-Solver (not in the reference) -------------------------------------------------
+    def get_prediction_xt_last_sa(self, x_t, pred, g, g_last, gate=(1, 0, 0.0, 0.0), h0=None, h1=None, psum=None, g_h0=None,
+                                  g_h1=None, max_order=(3, 3), input_noise=None, rng=None, stochastic=None,
+                                  prediction_type=None, clip_fn=None, image_scale=None, pred_uncond=None, guidance_scale=1,
+                                  thr_out=None, x0_out=None):
+        """One launch of SA-Solver (``SASolver`` has the definition) at the node of ``g`` -> (x0, x_last, (h0, h1, psum)).
+
+        Guidance combine, x0 and threshold as ``get_prediction_xt_last``; then the corrector on ``x_t`` (the step from
+        ``h0``'s node redone: x_t - psum + alpha sum c^c_j m_j), the predictor to ``g_last``, the predictor's sum for the
+        next launch's corrector, and the history moved on: the returned state is (x0, the h0 given, the new sum).
+        ``gate`` = (predictor order, corrector order, tau, tau of the corrected step) -- ``SASolver.gate`` makes it; on the
+        last step (``g_last == 1``) it must be (1, 0, 0, .): x_last = x0.  ``h0`` / ``h1``: the x0 of the two launches before,
+        formed at ``g_h0`` / ``g_h1``; ``psum``: the sum the launch before returned.  Gammas are per-sample tensors and
+        need not lie on the schedule.  tau > 0 takes ``input_noise``, else ``torch.randn_like``.
+        GPU tensors take ``ops.sampler_step_sa``: ``h0`` / ``h1`` / ``psum`` are then updated IN PLACE (and returned),
+        ``gate`` may be a device float[4] and ``max_order`` = (P, C) its ceilings, ``x0_out`` the buffer x0 is written to
+        (``h0`` itself is allowed), ``rng`` an ``ops.DeviceRng`` to draw from in the kernel (default ``self.device_rng``),
+        which is advanced by ``x_t.numel()`` where ``stochastic`` is on (default: tau > 0 in a host gate) -- on every
+        launch, whatever its tau, so that a captured graph and the eager loop draw the same numbers.
+        CPU tensors take the torch ops below, in the dtype of ``x_t`` with the coefficients formed in fp64."""
+        if self._on_hip(x_t, clip_fn):
+            x_t, pred, kw = self._hip_step_args(x_t, pred, g, g_last, prediction_type, clip_fn, image_scale, pred_uncond,
+                                                guidance_scale, thr_out)
+            if stochastic is None:
+                stochastic = (not torch.is_tensor(gate)) and gate[2] > 0
+            rng = self.device_rng if rng is None else rng
+            noise = input_noise
+            if stochastic and noise is None and rng is None:
+                noise = torch.randn_like(x_t)
+            x0, x_last = ops.sampler_step_sa(x_t, pred, g, g_last, gate=gate, h0=h0, h1=h1, psum=psum, g_h0=g_h0, g_h1=g_h1,
+                                             max_predictor=max_order[0], max_corrector=max_order[1], noise=noise,
+                                             rng=rng if (stochastic and noise is None) else None, x0_out=x0_out, **kw)
+            if stochastic and noise is None:
+                rng.advance(x_t.numel())
+            return x0, x_last, (h0, h1, psum)
+        if x0_out is not None or rng is not None or torch.is_tensor(gate):
+            raise ValueError("x0_out=, rng= and a device gate belong to the step kernel: GPU tensors only")
+        p, c, tau, tau_c = gate
+        x0 = self._x0_thresholded(x_t, pred, g, prediction_type, clip_fn, image_scale, pred_uncond, guidance_scale, thr_out)
+        last = g_last >= 1
+        if bool(last.all()):
+            return x0, x0, (x0, h0, psum)
+        gd = g.double()
+        gl = torch.where(last, 0.5 * (1 + gd), g_last.double())   # a finite stand-in where the sample is on its last step
+        to = lambda v: v.to(x_t.dtype)
+        x_a = x_t
+        if c >= 1:
+            g0 = g_h0.double()
+            cc = sa_corrector_coeffs(_dlambda(g0, gd), tau_c, c, _dlambda(g_h1.double(), g0) if c >= 3 else None)
+            s = to(gd.sqrt() * cc[0]) * x0
+            if c >= 2:
+                s = s + to(gd.sqrt() * cc[1]) * h0
+            if c >= 3:
+                s = s + to(gd.sqrt() * cc[2]) * h1
+            x_a = x_t - psum + s
+        h = _dlambda(gd, gl)
+        cp = sa_predictor_coeffs(h, tau, p, _dlambda(g_h0.double(), gd) if p >= 2 else None,
+                                 _dlambda(g_h1.double(), g_h0.double()) if p >= 3 else None)
+        s = to(gl.sqrt() * cp[0]) * x0
+        if p >= 2:
+            s = s + to(gl.sqrt() * cp[1]) * h0
+        if p >= 3:
+            s = s + to(gl.sqrt() * cp[2]) * h1
+        x_last = to(((1 - gl) / (1 - gd)).sqrt() * torch.exp(-tau * tau * h)) * x_a + s
+        if tau > 0:
+            noise = torch.randn_like(x_t) if input_noise is None else input_noise
+            x_last = x_last + to((1 - gl).sqrt() * (-torch.expm1(-2 * tau * tau * h)).sqrt()) * noise
+        if bool(last.any()):
+            x_last = torch.where(last, x0, x_last)
+        return x0, x_last, (x0, h0, s)
+
     def _threshold_sample(self, sample, ratio=0.995, max_value=100):
         """Imagen dynamic thresholding (:461-498)."""
         shape, dtype = sample.shape, sample.dtype
@@ -957,16 +1174,22 @@ class Sampler(nn.Module):
         """``x_t`` and what is returned: tensors here, hi -> lo lists in ``NestedSampler`` (whose first step may be given the
         top scale alone).  ``solver="dpmpp_2m"``: the DPM-Solver++(2M) update instead of DDPM / DDIM.  ``solver_state`` is
         the caller's dict of history, updated in place: {"x0": x0 of the step before, "g": the gamma it was formed at};
-        ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``options``: the keywords
+        ``second_order`` (decided by the caller: off on the first and on the last step) uses it.  ``solver=SASolver(...)`` /
+        ``"sa"``: SA-Solver; ``solver_state`` then carries "h0", "h1", "psum" (the x0 of the two launches before and the
+        predictor's sum), "g0", "g1" (their gammas), "count" (launches so far: the orders follow it, an empty dict restarts
+        them) and "tau" (of the step before), and ``second_order`` is not used.  ``options``: the keywords
         of ``SampleOptions`` (``guide``, ``pag_scale``, ``pag_layers``, ``regions``, ``region_layers``, ``freeu``, ``cfg``,
         ``tiles``), checked here.  The momentum history of ``cfg`` lives in ``solver_state["cfg_run"]`` (one tensor per
         scale, absent until the first guided step), so without a ``solver_state`` every call starts without history."""
         _check_solver(solver, ddim_eta)
-        return self._step(model, time_step, x_t, lm_outputs, lm_mask, micros, SampleOptions(**options).check(),
-                          time_step_last, guidance_scale, ddim_eta, return_details, solver, solver_state, second_order)
+        opts = SampleOptions(**options).check()
+        _check_sa(solver, opts)
+        return self._step(model, time_step, x_t, lm_outputs, lm_mask, micros, opts, time_step_last, guidance_scale,
+                          ddim_eta, return_details, _solver_of(solver), solver_state, second_order)
 
     def _step(self, model, time_step, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=None, guidance_scale=1,
-              ddim_eta=None, return_details=False, solver=None, solver_state=None, second_order=False, rows=None):
+              ddim_eta=None, return_details=False, solver=None, solver_state=None, second_order=False, rows=None,
+              sa_gate=None, sa_noise_fn=None):
         """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked once (and,
         under ``opts.tiles``, with the window count and the conditioning it repeated per window once: ``rows``).
         Denoiser, update of every scale, then the guide's correction if there is one: with a guide the model runs on leaf
@@ -983,6 +1206,15 @@ class Sampler(nn.Module):
         step_kw = dict(guidance_scale=guidance_scale, ddim_eta=ddim_eta, solver=solver, second_order=second_order,
                        g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
                        need_noise=solver is None and bool(self._noisy_step(time_step, last)))
+        sa = solver if isinstance(solver, SASolver) else None
+        if sa is not None:
+            # the state of SA-Solver in the caller's dict: "h0" / "h1" (the x0 of the two launches before) and "psum" (the
+            # predictor's sum), "g0" / "g1" (the gammas h0 / h1 were formed at), "count" (launches so far) and "tau" (of
+            # the step before); every entry in the form x_t has (a tensor, or a hi -> lo list)
+            if sa_gate is None:
+                sa_gate = sa.gate(st.get("count", 0), time_step, last, self.n_steps, st.get("tau", 0.0))
+            sa_state = {k: listed(st.get(k)) for k in ("h0", "h1", "psum", "g0", "g1")}
+            step_kw.update(g_prev=None, x0_prev=None, sa_gate=sa_gate, sa_state=sa_state, sa_noise_fn=sa_noise_fn)
         if opts.cfg is not None and guidance_scale != 1:
             step_kw.update(cfg_state=st, cfg_on=opts.cfg.on(time_step, self.n_steps))
         guide = opts.guide
@@ -1002,7 +1234,12 @@ class Sampler(nn.Module):
         if guide is not None:
             x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0], image_scales[0], guidance_scale,
                                      thr[0])
-        if solver is not None:
+        if sa is not None:
+            for k in ("h0", "h1", "psum"):
+                st[k] = self._from_scales(sa_state[k])
+            st["g1"], st["g0"] = st.get("g0"), self._from_scales(g_t)
+            st["count"], st["tau"] = st.get("count", 0) + 1, sa_gate[2]
+        elif solver is not None:
             st["x0"], st["g"] = self._from_scales(x0), self._from_scales(g_t)
         if not return_details:
             return self._from_scales(x_s)
@@ -1010,14 +1247,19 @@ class Sampler(nn.Module):
 
     def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, opts, need_noise=False, guidance_scale=1, ddim_eta=None,
                      solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, pps=None, rng=None,
-                     noise_gate=None, x0_out=None, cfg_state=None, cfg_on=True, cfg_gates=None):
+                     noise_gate=None, x0_out=None, cfg_state=None, cfg_on=True, cfg_gates=None, sa_gate=None, sa_state=None,
+                     sa_noise_fn=None):
         """The update of every scale behind the denoiser call -> (x0 list, x_s list).  All lists hi -> lo, one entry per
         scale; ``g_prev`` / ``x0_prev``: the history of ``solver="dpmpp_2m"``, or None.  This is the one reverse step of the
         eager samplers and of ``GraphedSampler``, whose captured graph passes ``rng``, ``noise_gate``, a device
         ``second_order`` gate, ``x0_out`` and the cfg state and gates through to the kernels.  ``pps`` with
         ``opts.pag_scale != 0``: the perturbed predictions -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU
         tensors: ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1.
-        ``opts.cfg`` with ``guidance_scale != 1`` does the same with the projected / rescaled combine (``_cfg_scales``)."""
+        ``opts.cfg`` with ``guidance_scale != 1`` does the same with the projected / rescaled combine (``_cfg_scales``).
+        ``solver`` an ``SASolver``: ``sa_gate`` (host 4-tuple or device float[4]) and ``sa_state``, a dict of hi -> lo lists
+        "h0", "h1", "psum", "g0", "g1" (or Nones before the first launch), whose first three are replaced by what the
+        launch returns; ``rng`` is drawn from and advanced where the solver's tau > 0; ``sa_noise_fn(x)``, if given, makes the
+        noise of a launch whose (host) gate has tau > 0 instead."""
         n = len(x_t)
         g_prev, x0_prev, x0_out = (v or [None] * n for v in (g_prev, x0_prev, x0_out))
         cfg, pag_scale = opts.cfg_at(guidance_scale), opts.pag_scale
@@ -1031,8 +1273,20 @@ class Sampler(nn.Module):
         kw = dict(prediction_type=self._config.prediction_type, clip_fn=self.clip_sample, guidance_scale=guidance_scale,
                   thr_out=thr_out)
         x0, x_s = [], []
+        sa = solver if isinstance(solver, SASolver) else None
+        if sa is not None:
+            self._sa_buffers(sa, sa_state, x_t, g_t)
         for i in range(n):
-            if solver is not None:
+            if sa is not None:
+                given = sa_noise_fn is not None and not torch.is_tensor(sa_gate) and sa_gate[2] > 0
+                a, b, new = self.get_prediction_xt_last_sa(
+                    x_t[i], pcs[i], g_t[i], g_s[i], gate=sa_gate, max_order=(sa.predictor, sa.corrector),
+                    rng=rng, stochastic=sa.tau > 0, input_noise=sa_noise_fn(x_t[i]) if given else None, image_scale=image_scales[i], pred_uncond=pus[i], x0_out=x0_out[i],
+                    **{k: sa_state[k][i] for k in ("h0", "h1", "psum")}, g_h0=sa_state["g0"][i], g_h1=sa_state["g1"][i],
+                    **kw)
+                for k, v in zip(("h0", "h1", "psum"), new):
+                    sa_state[k][i] = v
+            elif solver is not None:
                 a, b = self.get_prediction_xt_last_2m(
                     x_t[i], pcs[i], g_t[i], g_s[i], g_prev=g_prev[i], x0_prev=x0_prev[i], second_order=second_order,
                     image_scale=image_scales[i], pred_uncond=pus[i], x0_out=x0_out[i], **kw)
@@ -1043,6 +1297,21 @@ class Sampler(nn.Module):
             x0.append(a)
             x_s.append(b)
         return x0, x_s
+
+    @staticmethod
+    def _sa_buffers(sa, state, x_t, g_t):
+        """Completes the SA-Solver state of ``_step_scales`` (a dict of hi -> lo lists, or of Nones before the first
+        launch): on GPU tensors the buffers the kernel updates in place, fp32, as far as the orders of ``sa`` ask for
+        them; and a stand-in for the gammas there is no history for yet (this step's own: the gate keeps them unread)."""
+        n, top = len(x_t), max(sa.predictor, sa.corrector)
+        need = dict(h0=top >= 2, h1=top >= 3, psum=sa.corrector >= 1)
+        for k in ("h0", "h1", "psum"):
+            if state.get(k) is None:
+                state[k] = [torch.zeros_like(x, dtype=torch.float32) if x.is_cuda and need[k] else None for x in x_t]
+        if state.get("g0") is None:
+            state["g0"] = list(g_t)
+        if state.get("g1") is None:
+            state["g1"] = list(state["g0"])
 
     def _cfg_scales(self, cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, state=None, on=True, gates=None):
         """The projected / rescaled guidance combine of every scale (``mdm_hip/guidance.py``) -> the guided predictions.
@@ -1081,10 +1350,15 @@ class Sampler(nn.Module):
     def sample(self, *args, **kwargs):
         """``solver=None``: ancestral DDPM, or DDIM with ``ddim_eta`` (the reference's two).  ``solver="dpmpp_2m"``:
         DPM-Solver++(2M), deterministic, second order, one denoiser call per step -- made for few steps
-        (``resample_steps=True, num_inference_steps=20..50``)."""
+        (``resample_steps=True, num_inference_steps=20..50``).  ``solver=SASolver(predictor, corrector, tau,
+        tau_interval)`` (``"sa"``: the defaults): SA-Solver, a predictor-corrector of up to third order with a noise level
+        between the probability-flow ODE and the reverse SDE, one denoiser call per step too; its noise comes from
+        ``use_device_rng`` if set, else from ``torch.randn_like``.  It takes no ``guide=`` and no ``resample > 1``."""
         _check_solver(kwargs.get("solver"), kwargs.get("ddim_eta"))   # here, not at the generator's first next()
         _check_known(kwargs.get("known_images"), kwargs.get("resample", 1), kwargs.get("solver"))
-        guide = SampleOptions.pop(dict(kwargs)).check().guide   # the one check of the call: _sample only builds
+        opts = SampleOptions.pop(dict(kwargs)).check()   # the one check of the call: _sample only builds
+        _check_sa(kwargs.get("solver"), opts)
+        guide = opts.guide
         gen = self._sample(*args, **kwargs)
         if guide is None:
             return gen if kwargs.get("yield_output", False) else next(gen)
@@ -1119,7 +1393,7 @@ class Sampler(nn.Module):
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-                known_noise_fn=None, **post_args):
+                known_noise_fn=None, solver_noise_fn=None, **post_args):
         """``guide``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers``, ``freeu``, ``cfg``, ``tiles``: see
         ``SampleOptions``;
         they are taken out of the keywords here (``sample`` has checked them), the rest goes to ``_postprocess``.
@@ -1129,18 +1403,27 @@ class Sampler(nn.Module):
         image).  ``resample = r > 1`` (RePaint's jumps of length 1): every step but the last is taken r times, with the
         forward transition s -> t (``jump``) in between, so that the free region can follow the known one --
         (n - 1) r + 1 denoiser calls.  The noise of both comes from ``known_seed`` (see ``KnownRegion``).  One top-scale
-        tensor each, or hi -> lo lists for a nested model (``[None, low]``: super-resolution of a given image)."""
+        tensor each, or hi -> lo lists for a nested model (``[None, low]``: super-resolution of a given image).
+        ``solver_noise_fn(x)``: with an ``SASolver`` of tau > 0, the noise of every launch that adds some (called per scale,
+        hi -> lo) instead of the device generator / ``torch.randn_like``."""
         assert not (yield_output and return_sequence)
         _check_solver(solver, ddim_eta)
         _check_known(known_images, resample, solver)
         opts = SampleOptions.pop(post_args)
+        solver = _solver_of(solver)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
             num_inference_steps = self.n_steps
-        steps = torch.from_numpy(self.set_timesteps(num_inference_steps)).to(self.gammas.device)
+        steps_host = self.set_timesteps(num_inference_steps)
         if t > -1:
-            steps = steps[steps <= t]
+            steps_host = steps_host[steps_host <= t]
+        steps = torch.from_numpy(steps_host).to(self.gammas.device)
+        # an SASolver: the gate of every launch -- orders 1, 2, .., P and corrector off, 2, .., C counted from the first step
+        # of THIS trajectory, the last step first order without corrector, tau per step
+        sa_gates = None
+        if isinstance(solver, SASolver):
+            sa_gates = solver.gates(steps_host[:-1], steps_host[1:] if resample_steps else steps_host[:-1] - 1, self.n_steps)
         known = None
         if known_images is not None:
             known = self._known_region(model, x_t, known_images, known_mask, known_seed, known_noise_fn)
@@ -1155,13 +1438,14 @@ class Sampler(nn.Module):
         for i, ts in enumerate(steps[:-1]):
             # second order needs history (not on the first step of this trajectory, wherever it starts) and a finite
             # step in log-SNR (not on the last one: it goes to gamma = 1)
-            second = solver is not None and bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)
+            second = solver == "dpmpp_2m" and bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)
             reps = resample if i < len(steps) - 2 else 1
             for rep in range(reps):
                 x0, x_t, extra = self._step(
                     model, ts, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=steps[i + 1] if resample_steps else None,
                     guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
-                    solver_state=history, second_order=second, rows=rows)
+                    solver_state=history, second_order=second, rows=rows,
+                    sa_gate=None if sa_gates is None else sa_gates[i], sa_noise_fn=solver_noise_fn)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]

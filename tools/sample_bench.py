@@ -9,6 +9,10 @@ and DPM-Solver++(2M), alternated call by call in ONE process (device events arou
 the wall time of one ``--few``-step (25) 2M ``sample()`` next to one ``--many``-step (250) ancestral DDPM ``sample()``.
    python tools/sample_bench.py nested1024 4 8 --solver dpmpp_2m [--calls 20] [--warmup 3] [--out FILE]
    rocprofv3 --kernel-trace --stats -d DIR -- python tools/sample_bench.py unet64 4 8 --solver dpmpp_2m --calls 3 --many 0
+With ``--solver sa [--tau 1]``: the same two-leg measurement with graphed DPM-Solver++(2M) and graphed SA-Solver
+(``SASolver(3, 3, tau)``: one launch per scale that reads three fp32 images more than 2M's) as the legs; the result line is
+appended to profiles/sa_sampling.jsonl unless ``--out`` names another file.
+   python tools/sample_bench.py nested256 4 8 --solver sa [--tau 1] [--calls 20] [--warmup 3] [--many 0]
 
 With ``--known``: known-region sampling against the path it sits beside.  Two graphed legs of ancestral DDPM, without known
 images (the captured graph of before: no launch more) and with a half-image mask (one ``mdm_sampler_known_blend`` launch per
@@ -33,9 +37,13 @@ from mdm_hip.testing import randomize_zero_params  # noqa: E402
 
 
 def solver_legs(pipe, smp, batch, side, dev, n_it, a):
-    """graphed DDIM(0) and graphed ``a.solver``, alternated; then few-step solver vs many-step DDPM wall time"""
+    """graphed DDIM(0) and graphed ``a.solver`` -- for ``sa``: graphed 2M and graphed SA-Solver --, alternated; then
+    few-step solver vs many-step DDPM wall time"""
     gs = GraphedSampler(pipe, seed=7)
-    legs = {"ddim_eta0": dict(ddim_eta=0), a.solver: dict(solver=a.solver)}
+    if a.solver == "sa":
+        base, legs = "dpmpp_2m", {"dpmpp_2m": dict(solver="dpmpp_2m"), "sa": dict(solver=samplers.SASolver(3, 3, tau=a.tau))}
+    else:
+        base, legs = "ddim_eta0", {"ddim_eta0": dict(ddim_eta=0), a.solver: dict(solver=a.solver)}
 
     def timed(**kw):
         torch.cuda.synchronize()
@@ -56,11 +64,16 @@ def solver_legs(pipe, smp, batch, side, dev, n_it, a):
     pct = lambda ts, q: sorted(ts)[min(len(ts) - 1, int(round(q * (len(ts) - 1))))]
     res = {"ms_per_iteration": {k: {"median": round(statistics.median(ts), 4), "min": round(min(ts), 4), "max": round(max(ts), 4),
                                     "p10_p90": [round(pct(ts, 0.1), 4), round(pct(ts, 0.9), 4)]} for k, ts in times.items()}}
-    lo, hi = res["ms_per_iteration"]["ddim_eta0"]["p10_p90"]
-    res["solver_median_inside_ddim_p10_p90"] = bool(lo <= res["ms_per_iteration"][a.solver]["median"] <= hi)
+    lo, hi = res["ms_per_iteration"][base]["p10_p90"]
+    if a.solver == "sa":
+        res["tau"] = a.tau
+        res["sa_minus_2m_median_ms"] = round(res["ms_per_iteration"]["sa"]["median"] - res["ms_per_iteration"][base]["median"], 4)
+        res["sa_median_inside_2m_p10_p90"] = bool(lo <= res["ms_per_iteration"]["sa"]["median"] <= hi)
+    else:
+        res["solver_median_inside_ddim_p10_p90"] = bool(lo <= res["ms_per_iteration"][a.solver]["median"] <= hi)
     if a.many > 0:
         wall = {}
-        for tag, kw in (("%s_%d_steps" % (a.solver, a.few), dict(solver=a.solver, num_inference_steps=a.few)),
+        for tag, kw in (("%s_%d_steps" % (a.solver, a.few), dict(legs[a.solver], num_inference_steps=a.few)),
                         ("ddpm_%d_steps" % a.many, dict(num_inference_steps=a.many))):
             timed(**kw)   # builds and warms the graph of this step count
             ms, out = timed(**kw)
@@ -112,6 +125,7 @@ def main():
     ap.add_argument("batch", nargs="?", type=int, default=4)
     ap.add_argument("steps", nargs="?", type=int, default=8)
     ap.add_argument("--solver", default=None, choices=list(samplers.SOLVERS))
+    ap.add_argument("--tau", type=float, default=0.0, help="with --solver sa: the noise level of SASolver(3, 3, tau)")
     ap.add_argument("--known", action="store_true", help="graphed DDPM with and without a half-image mask, alternated")
     ap.add_argument("--free-only", action="store_true", help="with --known: the leg without known images alone")
     ap.add_argument("--calls", type=int, default=20)
@@ -152,7 +166,7 @@ def main():
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
             res.update(solver_legs(pipe, smp, batch, side, dev, n_it, a))
         res["max_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2**30, 2)
-        emit(res, a.out)
+        emit(res, a.out or (os.path.join(ROOT, "profiles", "sa_sampling.jsonl") if a.solver == "sa" else None))
         return
     res = {"model": which, "batch": batch, "timed_steps": n_it, "sampler": "DDPM (ddim_eta=None), CFG off, bf16"}
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
