@@ -22,8 +22,7 @@ import torch.nn as nn
 
 from . import ops, regions as _regions
 from . import tiling as _tiling
-from .samplers import (SASolver, SampleOptions, _check_known, _check_solver, _solver_of, gather_windows, merge_windows,
-                       model_rows, repeat_rows, split_rows)
+from .samplers import SampleOptions, _checked_rule, gather_windows, merge_windows, model_rows, repeat_rows, split_rows
 from .unet import switch_state, switchable
 
 
@@ -110,15 +109,12 @@ class GraphedSampler:
     Semantics are those of ``Sampler._sample`` with ``resample_steps=True`` (reference samplers.py:516-609, 655-713):
     DDPM (``ddim_eta=None``) or DDIM(eta), classifier-free guidance, CLIP / NONE / DYNAMIC / DYNAMIC_IF thresholding (the
     dynamic ones: x0 kernel -> ``ops.abs_quantile``, a radix select of five launches whose workspace -- 35 KB per sample --
-    lives in the graph's pool, -> update kernel, all inside the graph; no sort), or ``solver="dpmpp_2m"``
-    (DPM-Solver++(2M): deterministic, the x0 history of every scale lives in a static buffer that the step kernel updates
-    in place, the order flag of each step comes from a device table), or ``solver=SASolver(...)`` / ``"sa"`` (SA-Solver: the
-    gate {predictor order, corrector order, tau, tau of the step before} of every step and the times of the two steps before
-    come from device tables, h0 / h1 / psum of every scale live in static buffers the step kernel updates in place; with
-    tau == 0 nothing is drawn and the generator is never touched, with tau > 0 every row draws from it and advances it, the
-    gate deciding whether the noise is added -- as the DDPM path does with its noise gate).  The ancestral noise comes
-    from the library's counter-based generator (``ops.DeviceRng``, replayable on the host); the START noise is drawn
-    like the eager path (CPU generator for the top scale, reference diffusion.py:177), or passed in.
+    lives in the graph's pool, -> update kernel, all inside the graph; no sort), or any other ``solver=``: the update rule
+    is a ``samplers.StepRule``, whose rows (noise gate, order gate, SA gate) and the times of the nodes it reads gammas of
+    are device tables and whose history lives in static buffers that the step kernel updates in place.  Noise after x_T
+    comes from the library's counter-based generator (``ops.DeviceRng``, replayable on the host): a rule that draws
+    advances it on every row and its row decides whether the noise is added; one that never draws never touches it.
+    The START noise is drawn like the eager path (CPU generator for the top scale, reference diffusion.py:177), or passed in.
 
     Image conditioning as in ``Sampler._sample``: ``known_images`` / ``known_mask`` live in static buffers and the body
     ends with the blend kernel of every scale that has one, drawing from a second static generator; ``resample = r > 1``
@@ -144,30 +140,24 @@ class GraphedSampler:
         self._graphs.clear()
 
     # ---- host-side schedule ------------------------------------------------------------------------------
-    def _tables(self, n_steps, device, resample=1):
+    def _tables(self, n_steps, device, resample, rule):
+        """-> device tables (time, target time, jump gate, the ``rule.history`` earlier nodes' times, the rule's rows), host times"""
         steps = self.sampler.set_timesteps(n_steps)                 # n+1 entries, descending, last = 0
-        t, s = steps[:-1], steps[1:]
-        gate = self.sampler._noisy_step(t, s)   # the last step adds no noise
-        mk = lambda a, dt: torch.as_tensor(a.copy()).to(device=device, dtype=dt)
-        # dpmpp_2m: the time of the step before (step 0 has none: its own, never used) and the order gate -- second order
-        # wherever there is history and a finite step in log-SNR, i.e. not on the first and not on the last step
-        # (0, 1, ..., 1, 0; all zeros for n <= 2)
-        p = np.concatenate((t[:1], t[:-1]))
-        order = np.zeros(len(t), dtype="float32")
-        order[1:-1] = (p[1:-1] > t[1:-1])
+        mk = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=device, dtype=dt)
         # resample = r: every row but the last r times; the jump gate is on wherever the same row follows
-        reps = np.full(len(t), int(resample))
+        reps = np.full(n_steps, int(resample))
         reps[-1] = 1
         jump = np.ones(int(reps.sum()), dtype="float32")
         jump[np.cumsum(reps) - 1] = 0
-        t, s, gate, p, order = (np.repeat(a, reps) for a in (t, s, gate, p, order))
-        return (mk(t, torch.long), mk(s, torch.long), mk(gate.astype("float32"), torch.float32), mk(p, torch.long),
-                mk(order, torch.float32), mk(jump, torch.float32)), t
+        t, s = np.repeat(steps[:-1], reps), np.repeat(steps[1:], reps)
+        # the node j steps back (a rule with history takes no resample); before the first: its own time, never read
+        prev = [mk(np.concatenate((np.repeat(t[:1], j), t))[:len(t)], torch.long) for j in range(1, rule.history + 1)]
+        return (mk(t, torch.long), mk(s, torch.long), mk(jump, torch.float32), prev,
+                mk(rule.rows(self.sampler, t, s), torch.float32)), (t, s)
 
-    def _build(self, key, xs, cond, mask, n_steps, ddim_eta, guidance, micros, solver, known, resample, opts, names,
-               bias_source):
-        """``opts``: the call's ``SampleOptions``, with what ``sample`` resolved of them for this model: ``names``, its
-        ``layer_names``, and the caller's bias handle (None without ``regions``)"""
+    def _build(self, key, xs, cond, mask, n_steps, guidance, micros, rule, known, resample, opts, names, bias_source):
+        """``rule``: the call's ``StepRule``; ``opts``: its ``SampleOptions``, with what ``sample`` resolved of them for this
+        model: ``names``, its ``layer_names``, and the caller's bias handle (None without ``regions``)"""
         smp = self.sampler
         cfg = opts.cfg_at(guidance)
         model = self.pipe.get_model()
@@ -179,7 +169,7 @@ class GraphedSampler:
         tiles = opts.tiles
         canvases = [tuple(x.shape[2:]) for x in xs]
         T = 1 if tiles is None else tiles.count(*canvases[0])
-        (tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump), t_host = self._tables(n_steps, dev, resample)
+        (tab_t, tab_s, tab_jump, tab_prev, tab_rule), (t_host, s_host) = self._tables(n_steps, dev, resample, rule)
         idx = torch.zeros(1, dtype=torch.long, device=dev)
         rng = ops.DeviceRng(self._seed, dev)
         # known-region sampling: static image / mask per scale that has one, and a generator of its own
@@ -189,22 +179,10 @@ class GraphedSampler:
             kn_mask = [None if m is None else m.clone() for m in known.masks]
             kn_inv, kn_rng = known.inv_scales, ops.DeviceRng(0, dev)
         x_static = [x.clone() for x in xs]
-        # dpmpp_2m: the x0 of the step before, per scale.  Read only where the order gate is on, so what a warm-up pass or
-        # an earlier sample() call left in it is never seen: step 0 (gate off) rewrites it
-        x0_prev = [torch.zeros_like(x) for x in xs] if solver == "dpmpp_2m" else None
-        # an SASolver: h0 / h1 / psum per scale, updated in place by the step kernel and read only where the gate's orders
-        # are on; the gate {predictor order, corrector order, tau, tau of the step before} of every row (sample() fills the
-        # rows it replays; until then first order without corrector, what the warm-up passes run with) and the time two
-        # steps back.  Noise is drawn from the generator, and the generator advanced, only if the solver's tau > 0
-        sa = solver if isinstance(solver, SASolver) else None
-        sa_bufs = tab_sa = tab_p1 = None
-        if sa is not None:
-            top = max(sa.predictor, sa.corrector)
-            sa_bufs = dict(h0=[torch.zeros_like(x) for x in xs],
-                           h1=[torch.zeros_like(x) if top >= 3 else None for x in xs],
-                           psum=[torch.zeros_like(x) if sa.corrector >= 1 else None for x in xs])
-            tab_sa = torch.tensor([[1.0, 0.0, 0.0, 0.0]] * len(t_host), dtype=torch.float32, device=dev)
-            tab_p1 = torch.as_tensor(np.concatenate((t_host[:1], t_host[:1], t_host[:-2]))[:len(t_host)].copy()).to(dev)
+        # the rule's history, updated in place by the step kernel and read only where its row says there is some: what a
+        # warm-up pass or an earlier call left is never seen.  ``tab_rule`` holds the full schedule's rows until a call
+        # writes those it replays; the warm-up passes run row 0
+        state = rule.buffers(x_static)
         # cfg: the momentum history per scale and the two gate tables, one row per replay; sample() fills the tables for
         # the rows it replays.  Until then: guidance on, no history -- what the warm-up passes (row 0) run with
         cfg_state = cfg_run_gate = cfg_w_gate = None
@@ -225,17 +203,10 @@ class GraphedSampler:
         def body():
             t = tab_t.index_select(0, idx)
             s = tab_s.index_select(0, idx)
-            gate = tab_gate.index_select(0, idx)
+            row = tab_rule.index_select(0, idx)
             gammas = lambda time: smp._gammas_of_scales(model, smp.gammas.index_select(0, time).expand(B))
             g_t, g_s = gammas(t), gammas(s)
-            history = {}
-            if sa is not None:   # x0 goes straight into h0 (the kernel reads its elements of h0 before it writes them)
-                history = dict(sa_gate=tab_sa.index_select(0, idx), x0_out=sa_bufs["h0"],
-                               sa_state=dict(sa_bufs, g0=gammas(tab_p.index_select(0, idx)),
-                                             g1=gammas(tab_p1.index_select(0, idx))))
-            elif solver is not None:   # the history lives in x0_prev: the step kernel updates it in place
-                history = dict(second_order=tab_order.index_select(0, idx), g_prev=gammas(tab_p.index_select(0, idx)),
-                               x0_prev=x0_prev, x0_out=x0_prev)
+            g_hist = [gammas(p.index_select(0, idx)) for p in tab_prev]
             times = (t - 1).expand(B)
             # the model's batch: [uncond | cond] under classifier-free guidance, + [perturbed] under perturbed-attention
             # guidance (the static conditioning and micros buffers hold that many rows)
@@ -254,14 +225,11 @@ class GraphedSampler:
                 preds = merge_windows(preds, tiles, ratios, canvases)
             preds, pus, pps = split_rows(preds, uncond, pert)
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> ops.abs_quantile, the
-            # library's radix select, -> update kernel, all captured).  Every row draws and advances the generator in
-            # the eager sampler's order (use_device_rng()); the device gate decides whether the noise is added
-            if cfg is not None:
-                history.update(cfg_state=cfg_state,
-                               cfg_gates=(cfg_run_gate.index_select(0, idx), cfg_w_gate.index_select(0, idx)))
-            _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, opts, need_noise=True,
-                                         guidance_scale=guidance, ddim_eta=ddim_eta, solver=solver, rng=rng, noise_gate=gate,
-                                         pps=pps, **history)
+            # library's radix select, -> update kernel, all captured), drawing in its order (use_device_rng())
+            cfg_kw = {} if cfg is None else dict(cfg_state=cfg_state, cfg_gates=(cfg_run_gate.index_select(0, idx),
+                                                                                  cfg_w_gate.index_select(0, idx)))
+            _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, opts, rule, row, state, g_hist,
+                                         guidance_scale=guidance, rng=rng, pps=pps, **cfg_kw)
             for x, xl in zip(x_static, x_last):
                 x.copy_(xl)
             if known is not None:   # blends hi -> lo, then jumps hi -> lo: the draw order of KnownRegion
@@ -299,9 +267,8 @@ class GraphedSampler:
         # function; once freed, a later allocation reuses their memory and the replayed index_select reads garbage
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
-                   t_host=t_host, order=tab_order, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
-                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, sa_gate=tab_sa,
-                   keep=(tab_t, tab_s, tab_gate, tab_p, tab_order, tab_jump, x0_prev, cfg_state, sa_bufs, tab_p1))
+                   t_host=t_host, s_host=s_host, rows=tab_rule, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
+                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, keep=(tab_t, tab_s, tab_jump, tab_prev, state, cfg_state))
         self._graphs[key] = ent
         return ent
 
@@ -328,27 +295,18 @@ class GraphedSampler:
         combines and the step (one launch per scale each), and the graph key holds ("tiles", window, stride, blend).
         -> images like ``Diffusion.sample(..., resample_steps=True, num_inference_steps=n, ddim_eta=eta,
         guidance_scale=w, solver=solver)``.  ``start_noise`` (tensor, or hi->lo list for a nested model) replaces the
-        drawn x_T.  ``solver="dpmpp_2m"`` draws no noise after x_T (``seed`` has nothing to act on).
+        drawn x_T.
         ``known_images`` / ``known_mask`` / ``resample`` / ``known_seed``: as ``Sampler._sample``; whether a scale has a
         known image, and ``resample``, are part of the graph key.  ``start_step=t``: replay only the rows whose time is
         <= t, from ``start_noise`` = the image noised to the first of them (``Diffusion.partial_diffusion(...,
-        graphed=self)`` does the noising); the first replayed row of ``dpmpp_2m`` is first order, as in the eager sampler.
-        ``solver=SASolver(...)`` (``"sa"``: the defaults): its fields are part of the graph key; every call writes the gate
-        table for the rows it replays, counted from its first row, so a late start restarts the orders; with ``tau > 0``
-        ``seed`` seeds the noise."""
+        graphed=self)`` does the noising).  ``solver=``: ``rule.key`` is part of the graph key (an ``SASolver``: its fields); every
+        call writes the rule's rows from its first replayed row on, counted from it: a late start restarts the orders."""
         opts = SampleOptions(**options)
         if opts.guide is not None:
             raise NotImplementedError("GraphedSampler does not take guide=: loss-guided sampling calls an arbitrary user "
                                       "function and an autograd pass through the denoiser every step, and neither can be "
                                       "captured in a hipGraph; use the eager Sampler.sample(..., guide=...)")
-        _check_solver(solver, ddim_eta)
-        _check_known(known_images, resample, solver)
-        opts.check()
-        solver = _solver_of(solver)
-        sa = solver if isinstance(solver, SASolver) else None
-        if sa is not None:   # a schedule with a repeated time has a step of h = 0: refused before anything is captured
-            st = self.sampler.set_timesteps(int(num_inference_steps))
-            sa.gates(st[:-1], st[1:], self.sampler.n_steps)
+        rule = _checked_rule(solver, ddim_eta, opts.check(), known_images, resample)
         cfg = opts.cfg_at(guidance_scale)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
@@ -387,18 +345,18 @@ class GraphedSampler:
             T = opts.tiles.check(*xs[0].shape[2:], smp._scale_info(model)[0]).count(*xs[0].shape[2:])
         if opts.pag_scale != 0 or opts.tiles is not None:
             cond, mask, micros = model_rows(opts, guidance_scale, xs[0].shape[0], T, cond, mask, micros)
-        key = (tuple(tuple(x.shape) for x in xs), tuple(cond.shape), int(num_inference_steps), ddim_eta, float(guidance_scale),
+        key = (tuple(tuple(x.shape) for x in xs), tuple(cond.shape), int(num_inference_steps), rule.key, float(guidance_scale),
                torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
                ops.fp32_split_enabled(),   # a captured graph keeps the arithmetic it was captured with
-               tuple(sorted((k, tuple(v.shape)) for k, v in micros.items())), solver)
+               tuple(sorted((k, tuple(v.shape)) for k, v in micros.items())))
         known = None
         if known_images is not None:
             known = smp._known_region(model, xs, known_images, known_mask, known_seed, None)
             key = key + (tuple(k is not None for k in known.images), int(resample))
         key = key + opts.graph_key(model.vision_model, guidance_scale, names)
         bias_source = None if regions is None else regions.rows_for(*opts.blocks(guidance_scale), xs[0].device)
-        ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), ddim_eta, float(guidance_scale), micros,
-                                                   solver, known, int(resample), opts, names, bias_source)
+        ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), float(guidance_scale), micros,
+                                                   rule, known, int(resample), opts, names, bias_source)
         if bias_source is not None:
             ent["bias"].fill(bias_source)
         for sx, x in zip(ent["x"], xs):
@@ -430,23 +388,11 @@ class GraphedSampler:
             run_on[first:] = seen > 0
             ent["cfg_w_gate"].copy_(torch.from_numpy(w_on))
             ent["cfg_run_gate"].copy_(torch.from_numpy(run_on))
-        if sa is not None and first < ent["n"]:
-            # the gate of every row this call replays, counted from its first row: a late start restarts the orders
-            th = ent["t_host"]
-            gates = np.zeros((ent["n"], 4), dtype="float32")
-            gates[:, 0] = 1
-            gates[first:] = sa.gates(th[first:], np.concatenate((th[1:], [0]))[first:], smp.n_steps)
-            ent["sa_gate"].copy_(torch.from_numpy(gates))
+        # the rule's rows of this call, counted from its first row: a late start is a trajectory of its own
+        ent["rows"][first:].copy_(torch.from_numpy(rule.rows(smp, ent["t_host"][first:], ent["s_host"][first:])))
         if seed is not None:
             ent["rng"].state.copy_(torch.tensor([seed & (2**63 - 1), 0], dtype=torch.int64))
-        # dpmpp_2m from a late start: there is no history at the first replayed row -- its order gate is off for this call
-        order_row = ent["order"][first:first + 1] if (solver == "dpmpp_2m" and first > 0) else None
-        if order_row is not None:
-            saved = order_row.clone()
-            order_row.zero_()
         for _ in range(ent["n"] - first):
             ent["graph"].replay()
-        if order_row is not None:
-            order_row.copy_(saved)
         out = [x.clone() for x in ent["x"]]
         return smp._postprocess(smp._from_scales(out), clip=True)

@@ -158,8 +158,94 @@ def _b(v):
 SOLVERS = ("dpmpp_2m", "sa")
 
 
+# an entry of a trajectory dict, in the form x_t has (a tensor, or a hi -> lo list) -> the list, or None
+_listed = lambda v: v if v is None or isinstance(v, (list, tuple)) else [v]
+
+
+class StepRule:
+    """The update rule of a trajectory: what ``solver=`` resolves to (``_rule_of``), once, at the entry points.  The eager
+    loop and ``GraphedSampler`` consume it alike, from the host the one, from device tables the other.  A rule of one's
+    own subclasses this and gives ``key``, ``rows`` and ``step``.
+    ``key``: hashable, the rule's part of a graph key.  ``history``: how many earlier nodes' gammas ``step`` reads (0 .. 2).
+    ``check(ddim_eta, opts, known_images, resample)``: what the rule refuses of a call.  ``rows(sampler, times, times_last)``
+    -> host float32 [len(times), width]: all that varies from step to step over the steps ``times`` -> ``times_last`` (host
+    arrays), counted from ``times[0]``, the first step of a trajectory wherever on the schedule it starts.  ``buffers(xs)``
+    -> the per-scale fp32 state the step kernels update in place, a dict of hi -> lo lists.  ``step(sampler, k, x_t, pred,
+    g_t, g_s, row, g_hist, state, **common)`` -> (x0, x_s) of scale ``k``; ``row``: one row of ``rows``, host numbers in the
+    eager loop and a device float[1, width] in a captured graph; ``g_hist[j][k]``: the gamma of the node j + 1 steps back;
+    ``state``: what ``buffers`` (graph) or ``load`` (eager) made; ``common``: what every rule hands on to
+    ``get_prediction_xt_last*`` (prediction_type, clip_fn, image_scale, pred_uncond, guidance_scale, thr_out, rng) and
+    ``noise_fn``, the caller's ``solver_noise_fn``.  The eager trajectory dict ``st`` (``solver_state`` of ``get_xt_minus_1``):
+    ``row`` makes the row of one such call from it and from what the ``caller`` decides (``second_order``), ``load`` makes
+    (g_hist, state) from it, ``store`` leaves the step's results in it."""
+
+    history = 0
+
+    def check(self, ddim_eta, opts, known_images, resample):
+        if ddim_eta is not None:
+            raise ValueError("solver=%r has no ddim_eta (got %r): dpmpp_2m is deterministic, SASolver takes tau=" % (self.key, ddim_eta))
+        if resample > 1:
+            raise ValueError("resample=%d with solver=%r: the multistep history is void after a jump" % (resample, self.key))
+
+    def row(self, sampler, st, time_step, last, **caller):
+        return self.rows(sampler, np.array([int(time_step)]), np.array([int(last)]))[0]
+
+    buffers = lambda self, xs: {}                               # a rule without history: nothing to keep,
+    load = lambda self, sampler, st, xs, g_t: ([], {})          # nothing to load
+    store = lambda self, sampler, st, state, x0, g_t, row: None   # and nothing to store
+
+
+class Ancestral(StepRule):
+    """``solver=None``: the reference's two, the ancestral DDPM posterior or DDIM(``ddim_eta``).  Row: the noise gate."""
+
+    def __init__(self, ddim_eta=None):
+        self.ddim_eta, self.key = ddim_eta, ("ancestral", ddim_eta)
+
+    check = lambda self, *call: None   # it refuses nothing
+
+    def rows(self, sampler, times, times_last):
+        return np.asarray(sampler._noisy_step(times, times_last), dtype="float32").reshape(-1, 1)
+
+    def step(self, sampler, k, x_t, pred, g_t, g_s, row, g_hist, state, noise_fn=None, **common):
+        gate = row if torch.is_tensor(row) else None   # a captured graph draws on every row; the device gate decides
+        x0, x_s, _ = sampler.get_prediction_xt_last(x_t, pred, g_t, g_s, need_noise=gate is not None or bool(row[0]),
+                                                    ddim_eta=self.ddim_eta, return_eps=False, noise_gate=gate, **common)
+        return x0, x_s
+
+
+class DPMpp2M(StepRule):
+    """``solver="dpmpp_2m"``.  Row: the order gate -- second order where there is history and a finite step in log-SNR: not on
+    the first and not on the last step of a trajectory (0, 1, .., 1, 0).  State: "x0" of the step before, formed at ``g_hist[0]``."""
+
+    key, history = "dpmpp_2m", 1
+
+    def rows(self, sampler, times, times_last):
+        order = np.zeros((len(times), 1), dtype="float32")
+        order[1:-1, 0] = np.asarray(times[:-2]) > np.asarray(times[1:-1])
+        return order
+
+    def buffers(self, xs):
+        x0 = [torch.zeros_like(x, dtype=torch.float32) for x in xs]
+        return dict(x0=x0, x0_out=x0)
+
+    def row(self, sampler, st, time_step, last, second_order=False):
+        return np.float32([bool(second_order)])   # the caller's decision
+
+    def load(self, sampler, st, xs, g_t):
+        none = [None] * len(xs)
+        return [_listed(st.get("g")) or none], dict(x0=_listed(st.get("x0")) or none, x0_out=none)
+
+    def store(self, sampler, st, state, x0, g_t, row):
+        st["x0"], st["g"] = sampler._from_scales(x0), sampler._from_scales(g_t)
+
+    def step(self, sampler, k, x_t, pred, g_t, g_s, row, g_hist, state, rng=None, noise_fn=None, **common):
+        return sampler.get_prediction_xt_last_2m(
+            x_t, pred, g_t, g_s, g_prev=g_hist[0][k], x0_prev=state["x0"][k], x0_out=state["x0_out"][k],
+            second_order=row if torch.is_tensor(row) else bool(row[0]), **common)
+
+
 @dataclass(frozen=True)
-class SASolver:
+class SASolver(StepRule):
     """``solver=SASolver(predictor=3, corrector=3, tau=0.0, tau_interval=None)``: SA-Solver (Xue et al., NeurIPS 2023,
     "SA-Solver: Stochastic Adams Solver for Fast Sampling of Diffusion Models"); ``solver="sa"`` means the defaults.
 
@@ -232,26 +318,72 @@ class SASolver:
             tau_prev = out[-1][2]
         return out
 
+    # ---- the StepRule.  Row: the gate.  State: "h0", "h1" (the x0 of the launches before, formed at ``g_hist``), "psum"
+    history, key = 2, property(lambda self: self)
 
-def _solver_of(solver):
-    """``solver=`` as given -> None, "dpmpp_2m" or an ``SASolver`` ("sa": the defaults)"""
-    return SASolver() if isinstance(solver, str) and solver == "sa" else solver
+    def check(self, ddim_eta, opts, known_images, resample):
+        StepRule.check(self, ddim_eta, opts, known_images, resample)
+        if opts.guide is not None:
+            raise NotImplementedError("guide= together with an SA solver: the guide's correction of x_s between the "
+                                      "predictor and the corrector that redoes the step is not implemented")
+
+    def rows(self, sampler, times, times_last):
+        return np.asarray(self.gates(times, times_last, sampler.n_steps), dtype="float32").reshape(-1, 4)
+
+    def buffers(self, xs):
+        zeros = lambda on: [torch.zeros_like(x, dtype=torch.float32) if on else None for x in xs]
+        h0 = zeros(True)   # x0 goes straight into h0: the kernel reads its elements of h0 before it writes them
+        return dict(h0=h0, h1=zeros(max(self.predictor, self.corrector) >= 3), psum=zeros(self.corrector >= 1), x0_out=h0)
+
+    def _host_gate(self, row):
+        """a host row -> the gate in host numbers, tau as the solver holds it (a float32 row has rounded it)"""
+        tau = lambda v: self.tau if np.float32(v) == np.float32(self.tau) else float(v)
+        return int(row[0]), int(row[1]), tau(row[2]), tau(row[3])
+
+    def row(self, sampler, st, time_step, last, **caller):
+        return self.gate(st.get("count", 0), time_step, last, sampler.n_steps, st.get("tau", 0.0))
+
+    def load(self, sampler, st, xs, g_t):
+        none = [None] * len(xs)
+        fresh = self.buffers(xs) if st.get("h0") is None and xs[0].is_cuda else {}
+        state = {name: list(_listed(st.get(name)) or fresh.get(name, none)) for name in ("h0", "h1", "psum")}
+        g0 = _listed(st.get("g0")) or list(g_t)   # no history yet: this step's own gamma stands in, unread
+        return [g0, _listed(st.get("g1")) or g0], dict(state, x0_out=none)   # eager: x0 is the caller's, a tensor of its own
+
+    def store(self, sampler, st, state, x0, g_t, row):
+        for name in ("h0", "h1", "psum"):
+            st[name] = sampler._from_scales(state[name])
+        st["g1"], st["g0"] = st.get("g0"), sampler._from_scales(g_t)
+        st["count"], st["tau"] = st.get("count", 0) + 1, self._host_gate(row)[2]
+
+    def step(self, sampler, k, x_t, pred, g_t, g_s, row, g_hist, state, rng=None, noise_fn=None, **common):
+        gate = row if torch.is_tensor(row) else self._host_gate(row)
+        given = noise_fn is not None and not torch.is_tensor(row) and gate[2] > 0
+        x0, x_s, new = sampler.get_prediction_xt_last_sa(
+            x_t, pred, g_t, g_s, gate=gate, max_order=(self.predictor, self.corrector), rng=rng, stochastic=self.tau > 0,
+            input_noise=noise_fn(x_t) if given else None, x0_out=state["x0_out"][k], g_h0=g_hist[0][k], g_h1=g_hist[1][k],
+            **{name: state[name][k] for name in ("h0", "h1", "psum")}, **common)
+        state["h0"][k], state["h1"][k], state["psum"][k] = new
+        return x0, x_s
 
 
-def _check_solver(solver, ddim_eta):
+def _rule_of(solver, ddim_eta=None):
+    """``solver=`` as given -> its ``StepRule``: None (DDPM / DDIM(``ddim_eta``)), a name of ``SOLVERS``, or a rule"""
     if solver is None:
-        return
-    if not isinstance(solver, SASolver) and (not isinstance(solver, str) or solver not in SOLVERS):
-        raise ValueError("unknown solver %r (known: %s, or an SASolver; None = DDPM / DDIM)" % (solver, ", ".join(SOLVERS)))
-    if ddim_eta is not None:
-        raise ValueError("solver=%r has no ddim_eta (got %r): dpmpp_2m is deterministic, SASolver takes tau="
-                         % (solver, ddim_eta))
+        return Ancestral(ddim_eta)
+    if isinstance(solver, StepRule):
+        return solver
+    if isinstance(solver, str) and solver in SOLVERS:
+        return DPMpp2M() if solver == "dpmpp_2m" else SASolver()
+    raise ValueError("unknown solver %r (known: %s, or an SASolver; None = DDPM / DDIM)" % (solver, ", ".join(SOLVERS)))
 
 
-def _check_sa(solver, opts):
-    if isinstance(_solver_of(solver), SASolver) and opts.guide is not None:
-        raise NotImplementedError("guide= together with an SA solver: the guide's correction of x_s between the predictor "
-                                  "and the corrector that redoes the step is not implemented")
+def _checked_rule(solver, ddim_eta, opts, known_images=None, resample=1):
+    """what every entry point does with ``solver=``: resolve it, and refuse what the call cannot have -> the rule"""
+    rule = _rule_of(solver, ddim_eta)
+    _check_known(known_images, resample)
+    rule.check(ddim_eta, opts, known_images, resample)
+    return rule
 
 
 def _dlambda(ga, gb):
@@ -311,13 +443,11 @@ def sa_corrector_coeffs(h, tau, order, h2=None):
     return ca, phi[0] - ca - c2, c2
 
 
-def _check_known(known_images, resample, solver):
+def _check_known(known_images, resample):
     if int(resample) != resample or resample < 1:
         raise ValueError("resample must be an integer >= 1 (got %r)" % (resample,))
     if resample > 1 and known_images is None:
         raise ValueError("resample=%d repeats the steps around a known region: it needs known_images" % resample)
-    if resample > 1 and solver is not None:
-        raise ValueError("resample=%d with solver=%r: the multistep history is void after a jump" % (resample, solver))
 
 
 def pag_combine(pred, pred_uncond, pred_pert, guidance_scale=1, pag_scale=0.0):
@@ -1181,42 +1311,29 @@ class Sampler(nn.Module):
         of ``SampleOptions`` (``guide``, ``pag_scale``, ``pag_layers``, ``regions``, ``region_layers``, ``freeu``, ``cfg``,
         ``tiles``), checked here.  The momentum history of ``cfg`` lives in ``solver_state["cfg_run"]`` (one tensor per
         scale, absent until the first guided step), so without a ``solver_state`` every call starts without history."""
-        _check_solver(solver, ddim_eta)
         opts = SampleOptions(**options).check()
-        _check_sa(solver, opts)
-        return self._step(model, time_step, x_t, lm_outputs, lm_mask, micros, opts, time_step_last, guidance_scale,
-                          ddim_eta, return_details, _solver_of(solver), solver_state, second_order)
+        rule = _checked_rule(solver, ddim_eta, opts)
+        last = time_step - 1 if time_step_last is None else time_step_last
+        row = rule.row(self, {} if solver_state is None else solver_state, time_step, last, second_order=second_order)
+        return self._step(model, time_step, x_t, lm_outputs, lm_mask, micros, opts, rule, row, last, guidance_scale,
+                          return_details, solver_state)
 
-    def _step(self, model, time_step, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=None, guidance_scale=1,
-              ddim_eta=None, return_details=False, solver=None, solver_state=None, second_order=False, rows=None,
-              sa_gate=None, sa_noise_fn=None):
-        """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked once (and,
-        under ``opts.tiles``, with the window count and the conditioning it repeated per window once: ``rows``).
-        Denoiser, update of every scale, then the guide's correction if there is one: with a guide the model runs on leaf
-        x_t with grad enabled and the update under no_grad on detached tensors; without, in the caller's grad mode."""
+    def _step(self, model, time_step, x_t, lm_outputs, lm_mask, micros, opts, rule, row, last, guidance_scale=1,
+              return_details=False, solver_state=None, rows=None, noise_fn=None):
+        """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked and the
+        ``StepRule`` it resolved once, that rule's ``row`` of this step and the time ``last`` the step goes to (and, under
+        ``opts.tiles``, with the window count and the conditioning it repeated per window once: ``rows``).  Denoiser, update
+        of every scale, then the guide's correction if there is one: with a guide the model runs on leaf x_t with grad
+        enabled and the update under no_grad on detached tensors; without, in the caller's grad mode."""
         x_t = self._to_scales(model, x_t)
         ones = torch.ones(x_t[0].shape[0], dtype=torch.long, device=self.gammas.device)
-        last = time_step - 1 if time_step_last is None else time_step_last
         t = ones * time_step
         g_t = self._gammas_of_scales(model, self.read_gamma(t))
         g_s = self._gammas_of_scales(model, self.read_gamma(ones * last))
         image_scales = self._scale_info(model)[1]
         st = {} if solver_state is None else solver_state
-        listed = lambda v: v if v is None or isinstance(v, (list, tuple)) else [v]
-        step_kw = dict(guidance_scale=guidance_scale, ddim_eta=ddim_eta, solver=solver, second_order=second_order,
-                       g_prev=listed(st.get("g")), x0_prev=listed(st.get("x0")),
-                       need_noise=solver is None and bool(self._noisy_step(time_step, last)))
-        sa = solver if isinstance(solver, SASolver) else None
-        if sa is not None:
-            # the state of SA-Solver in the caller's dict: "h0" / "h1" (the x0 of the two launches before) and "psum" (the
-            # predictor's sum), "g0" / "g1" (the gammas h0 / h1 were formed at), "count" (launches so far) and "tau" (of
-            # the step before); every entry in the form x_t has (a tensor, or a hi -> lo list)
-            if sa_gate is None:
-                sa_gate = sa.gate(st.get("count", 0), time_step, last, self.n_steps, st.get("tau", 0.0))
-            sa_state = {k: listed(st.get(k)) for k in ("h0", "h1", "psum", "g0", "g1")}
-            step_kw.update(g_prev=None, x0_prev=None, sa_gate=sa_gate, sa_state=sa_state, sa_noise_fn=sa_noise_fn)
-        if opts.cfg is not None and guidance_scale != 1:
-            step_kw.update(cfg_state=st, cfg_on=opts.cfg.on(time_step, self.n_steps))
+        g_hist, state = rule.load(self, st, x_t, g_t)
+        cfg_kw = {} if opts.cfg_at(guidance_scale) is None else dict(cfg_state=st, cfg_on=opts.cfg.on(time_step, self.n_steps))
         guide = opts.guide
         x_in, grad, no_grad, thr = x_t, _UNCHANGED, _UNCHANGED, None
         if guide is not None:
@@ -1230,38 +1347,25 @@ class Sampler(nn.Module):
         if guide is not None:   # the update itself: unchanged, on detached tensors
             outs = ([None if v is None else v.detach() for v in vs] for vs in outs)
         with no_grad:
-            x0, x_s = self._step_scales(*outs, g_t, g_s, image_scales, opts, pps=pps, thr_out=thr, **step_kw)
+            x0, x_s = self._step_scales(*outs, g_t, g_s, image_scales, opts, rule, row, state, g_hist, guidance_scale,
+                                        thr_out=thr, pps=pps, noise_fn=noise_fn, **cfg_kw)
         if guide is not None:
             x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0], image_scales[0], guidance_scale,
                                      thr[0])
-        if sa is not None:
-            for k in ("h0", "h1", "psum"):
-                st[k] = self._from_scales(sa_state[k])
-            st["g1"], st["g0"] = st.get("g0"), self._from_scales(g_t)
-            st["count"], st["tau"] = st.get("count", 0) + 1, sa_gate[2]
-        elif solver is not None:
-            st["x0"], st["g"] = self._from_scales(x0), self._from_scales(g_t)
+        rule.store(self, st, state, x0, g_t, row)
         if not return_details:
             return self._from_scales(x_s)
         return self._from_scales(x0), self._from_scales(x_s), (g_t[-1], g_s[-1])
 
-    def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, opts, need_noise=False, guidance_scale=1, ddim_eta=None,
-                     solver=None, g_prev=None, x0_prev=None, second_order=False, thr_out=None, pps=None, rng=None,
-                     noise_gate=None, x0_out=None, cfg_state=None, cfg_on=True, cfg_gates=None, sa_gate=None, sa_state=None,
-                     sa_noise_fn=None):
-        """The update of every scale behind the denoiser call -> (x0 list, x_s list).  All lists hi -> lo, one entry per
-        scale; ``g_prev`` / ``x0_prev``: the history of ``solver="dpmpp_2m"``, or None.  This is the one reverse step of the
-        eager samplers and of ``GraphedSampler``, whose captured graph passes ``rng``, ``noise_gate``, a device
-        ``second_order`` gate, ``x0_out`` and the cfg state and gates through to the kernels.  ``pps`` with
-        ``opts.pag_scale != 0``: the perturbed predictions -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU
-        tensors: ``pag_combine``) hands the step the guided prediction, with no unconditional one and guidance 1.
-        ``opts.cfg`` with ``guidance_scale != 1`` does the same with the projected / rescaled combine (``_cfg_scales``).
-        ``solver`` an ``SASolver``: ``sa_gate`` (host 4-tuple or device float[4]) and ``sa_state``, a dict of hi -> lo lists
-        "h0", "h1", "psum", "g0", "g1" (or Nones before the first launch), whose first three are replaced by what the
-        launch returns; ``rng`` is drawn from and advanced where the solver's tau > 0; ``sa_noise_fn(x)``, if given, makes the
-        noise of a launch whose (host) gate has tau > 0 instead."""
+    def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, opts, rule, row, state, g_hist=(), guidance_scale=1,
+                     thr_out=None, pps=None, rng=None, cfg_state=None, cfg_on=True, cfg_gates=None, noise_fn=None):
+        """The update of every scale behind the denoiser call -> (x0 list, x_s list), all lists hi -> lo: ``rule.step`` per
+        scale with the rule's ``row``, ``state`` and ``g_hist`` (``StepRule``).  The one reverse step of the eager samplers
+        and of ``GraphedSampler``, whose graph passes a device row, the rule's buffers, its generator ``rng`` and the cfg
+        state and gates through to the kernels.  ``pps`` with ``opts.pag_scale != 0``: the perturbed predictions -- one
+        combine per scale (GPU tensors: ``ops.pag_combine``, CPU tensors: ``pag_combine``) hands the step the guided prediction,
+        with no unconditional one and guidance 1; ``opts.cfg`` with ``guidance_scale != 1``: the same with ``_cfg_scales``."""
         n = len(x_t)
-        g_prev, x0_prev, x0_out = (v or [None] * n for v in (g_prev, x0_prev, x0_out))
         cfg, pag_scale = opts.cfg_at(guidance_scale), opts.pag_scale
         if cfg is not None:
             pcs = self._cfg_scales(cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, cfg_state, cfg_on, cfg_gates)
@@ -1271,47 +1375,10 @@ class Sampler(nn.Module):
                    if pc.is_cuda else pag_combine(pc, pu, pp, guidance_scale, pag_scale) for pc, pu, pp in zip(pcs, pus, pps)]
             pus, guidance_scale = [None] * n, 1
         kw = dict(prediction_type=self._config.prediction_type, clip_fn=self.clip_sample, guidance_scale=guidance_scale,
-                  thr_out=thr_out)
-        x0, x_s = [], []
-        sa = solver if isinstance(solver, SASolver) else None
-        if sa is not None:
-            self._sa_buffers(sa, sa_state, x_t, g_t)
-        for i in range(n):
-            if sa is not None:
-                given = sa_noise_fn is not None and not torch.is_tensor(sa_gate) and sa_gate[2] > 0
-                a, b, new = self.get_prediction_xt_last_sa(
-                    x_t[i], pcs[i], g_t[i], g_s[i], gate=sa_gate, max_order=(sa.predictor, sa.corrector),
-                    rng=rng, stochastic=sa.tau > 0, input_noise=sa_noise_fn(x_t[i]) if given else None, image_scale=image_scales[i], pred_uncond=pus[i], x0_out=x0_out[i],
-                    **{k: sa_state[k][i] for k in ("h0", "h1", "psum")}, g_h0=sa_state["g0"][i], g_h1=sa_state["g1"][i],
-                    **kw)
-                for k, v in zip(("h0", "h1", "psum"), new):
-                    sa_state[k][i] = v
-            elif solver is not None:
-                a, b = self.get_prediction_xt_last_2m(
-                    x_t[i], pcs[i], g_t[i], g_s[i], g_prev=g_prev[i], x0_prev=x0_prev[i], second_order=second_order,
-                    image_scale=image_scales[i], pred_uncond=pus[i], x0_out=x0_out[i], **kw)
-            else:
-                a, b, _ = self.get_prediction_xt_last(
-                    x_t[i], pcs[i], g_t[i], g_s[i], need_noise=need_noise, ddim_eta=ddim_eta, return_eps=False,
-                    image_scale=image_scales[i], pred_uncond=pus[i], rng=rng, noise_gate=noise_gate, **kw)
-            x0.append(a)
-            x_s.append(b)
-        return x0, x_s
-
-    @staticmethod
-    def _sa_buffers(sa, state, x_t, g_t):
-        """Completes the SA-Solver state of ``_step_scales`` (a dict of hi -> lo lists, or of Nones before the first
-        launch): on GPU tensors the buffers the kernel updates in place, fp32, as far as the orders of ``sa`` ask for
-        them; and a stand-in for the gammas there is no history for yet (this step's own: the gate keeps them unread)."""
-        n, top = len(x_t), max(sa.predictor, sa.corrector)
-        need = dict(h0=top >= 2, h1=top >= 3, psum=sa.corrector >= 1)
-        for k in ("h0", "h1", "psum"):
-            if state.get(k) is None:
-                state[k] = [torch.zeros_like(x, dtype=torch.float32) if x.is_cuda and need[k] else None for x in x_t]
-        if state.get("g0") is None:
-            state["g0"] = list(g_t)
-        if state.get("g1") is None:
-            state["g1"] = list(state["g0"])
+                  thr_out=thr_out, rng=rng, noise_fn=noise_fn)
+        x0, x_s = zip(*(rule.step(self, k, x_t[k], pcs[k], g_t[k], g_s[k], row, g_hist, state, image_scale=image_scales[k],
+                                  pred_uncond=pus[k], **kw) for k in range(n)))
+        return list(x0), list(x_s)
 
     def _cfg_scales(self, cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, state=None, on=True, gates=None):
         """The projected / rescaled guidance combine of every scale (``mdm_hip/guidance.py``) -> the guided predictions.
@@ -1354,10 +1421,8 @@ class Sampler(nn.Module):
         tau_interval)`` (``"sa"``: the defaults): SA-Solver, a predictor-corrector of up to third order with a noise level
         between the probability-flow ODE and the reverse SDE, one denoiser call per step too; its noise comes from
         ``use_device_rng`` if set, else from ``torch.randn_like``.  It takes no ``guide=`` and no ``resample > 1``."""
-        _check_solver(kwargs.get("solver"), kwargs.get("ddim_eta"))   # here, not at the generator's first next()
-        _check_known(kwargs.get("known_images"), kwargs.get("resample", 1), kwargs.get("solver"))
-        opts = SampleOptions.pop(dict(kwargs)).check()   # the one check of the call: _sample only builds
-        _check_sa(kwargs.get("solver"), opts)
+        opts = SampleOptions.pop(dict(kwargs)).check()   # the checks of the call, here and not at the generator's first next()
+        _checked_rule(kwargs.get("solver"), kwargs.get("ddim_eta"), opts, kwargs.get("known_images"), kwargs.get("resample", 1))
         guide = opts.guide
         gen = self._sample(*args, **kwargs)
         if guide is None:
@@ -1395,8 +1460,7 @@ class Sampler(nn.Module):
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
                 known_noise_fn=None, solver_noise_fn=None, **post_args):
         """``guide``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers``, ``freeu``, ``cfg``, ``tiles``: see
-        ``SampleOptions``;
-        they are taken out of the keywords here (``sample`` has checked them), the rest goes to ``_postprocess``.
+        ``SampleOptions``; they are taken out of the keywords here (``sample`` has checked them), the rest goes to ``_postprocess``.
         ``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
         whichever update made it, every scale's x_s is replaced where the mask is 1 by the known image diffused to that
         scale's target gamma (``known_blend``; the last step goes to gamma = 1: the known region of the result IS the known
@@ -1407,10 +1471,8 @@ class Sampler(nn.Module):
         ``solver_noise_fn(x)``: with an ``SASolver`` of tau > 0, the noise of every launch that adds some (called per scale,
         hi -> lo) instead of the device generator / ``torch.randn_like``."""
         assert not (yield_output and return_sequence)
-        _check_solver(solver, ddim_eta)
-        _check_known(known_images, resample, solver)
         opts = SampleOptions.pop(post_args)
-        solver = _solver_of(solver)
+        rule = _checked_rule(solver, ddim_eta, opts, known_images, resample)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -1419,33 +1481,25 @@ class Sampler(nn.Module):
         if t > -1:
             steps_host = steps_host[steps_host <= t]
         steps = torch.from_numpy(steps_host).to(self.gammas.device)
-        # an SASolver: the gate of every launch -- orders 1, 2, .., P and corrector off, 2, .., C counted from the first step
-        # of THIS trajectory, the last step first order without corrector, tau per step
-        sa_gates = None
-        if isinstance(solver, SASolver):
-            sa_gates = solver.gates(steps_host[:-1], steps_host[1:] if resample_steps else steps_host[:-1] - 1, self.n_steps)
+        # the rule's row of every step, counted from the first step of THIS trajectory, wherever it starts
+        rule_rows = rule.rows(self, steps_host[:-1], steps_host[1:] if resample_steps else steps_host[:-1] - 1)
         known = None
         if known_images is not None:
             known = self._known_region(model, x_t, known_images, known_mask, known_seed, known_noise_fn)
         seq = [x_t] if return_sequence else []
         x0 = extra = None
-        history = {}   # dpmpp_2m: x0 and gamma of the step before, per scale; cfg: the momentum buffers ("cfg_run")
+        history = {}   # the rule's entries (``StepRule.store``); cfg: the momentum buffers ("cfg_run")
         rows = None    # tiles: the window count and the conditioning repeated per window, the same for every step
         if opts.tiles is not None:
             top = x_t[0] if isinstance(x_t, (list, tuple)) else x_t
             T = opts.tiles.check(*top.shape[2:], self._scale_info(model)[0]).count(*top.shape[2:])
             rows = T, model_rows(opts, guidance_scale, top.shape[0], T, lm_outputs, lm_mask, micros)
         for i, ts in enumerate(steps[:-1]):
-            # second order needs history (not on the first step of this trajectory, wherever it starts) and a finite
-            # step in log-SNR (not on the last one: it goes to gamma = 1)
-            second = solver == "dpmpp_2m" and bool(0 < i < len(steps) - 2 and steps[i - 1] > ts)
             reps = resample if i < len(steps) - 2 else 1
             for rep in range(reps):
                 x0, x_t, extra = self._step(
-                    model, ts, x_t, lm_outputs, lm_mask, micros, opts, time_step_last=steps[i + 1] if resample_steps else None,
-                    guidance_scale=guidance_scale, ddim_eta=ddim_eta, return_details=True, solver=solver,
-                    solver_state=history, second_order=second, rows=rows,
-                    sa_gate=None if sa_gates is None else sa_gates[i], sa_noise_fn=solver_noise_fn)
+                    model, ts, x_t, lm_outputs, lm_mask, micros, opts, rule, rule_rows[i], steps[i + 1] if resample_steps else ts - 1,
+                    guidance_scale, return_details=True, solver_state=history, rows=rows, noise_fn=solver_noise_fn)
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
