@@ -30,6 +30,13 @@ int mdm_dev_set_knob(int idx, int value);
  * one-block-per-head kernel whenever the shape allows (tests), 3 = as 2 but the 16x16x32 one, 4 = the streaming kernels on
  * 32x32x16 MFMAs (csrc/attn32.hpp) whenever the shape allows */
 int mdm_dev_set_attn_bwd(int mode);
+/* names of the kernel(s) the calling thread's last mdm_attn_fwd / mdm_attn_bwd launched, as "attn_fwd_kernel<bf16,96,2>"; a
+ * two-kernel backward is joined with '+'.  Written where the launch is made, so a knob that the shape does not allow shows as
+ * the kernel that ran instead (tests/attn_variant_cases.py) */
+const char* mdm_last_attn_kernel(void);
+/* queries per wave of the bf16 attention forward: 0 = by shape and CU count (the product), 1 = always 16 (QT = 1), 2 = always
+ * 32 (QT = 2).  The fp32 and DT_F32_SPLIT forwards have one instantiation and ignore it.  Any other value is -1 */
+int mdm_dev_set_attn_fwd(int mode);
 /* GroupNorm backward, two-kernel path (images too large for the register-resident kernel): bytes of x + dy, in MiB,
  * above which the batch is walked in chunks of samples so that the second kernel's reads still find them in the Infinity
  * Cache (default 160; 0 = chunk whenever the batch allows it -- the tests; negative = never) */

@@ -21,6 +21,7 @@
 // are read in the permuted order key(kt, r) = (kt>>1)*32 + (r>>2)*8 + (kt&1)*4 + (r&3)
 // so that a lane's 8 probabilities of one PV step are 8 *contiguous* keys of the
 // transposed V tile.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -1262,6 +1263,24 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_small_kernel(AttnArgs p) {
 
 using namespace mdm;
 
+// development aids (mdm_hip_dev.h).  The name of the kernel(s) the calling thread's last mdm_attn_fwd / mdm_attn_bwd launched,
+// written where the launch is made (a fall-through of a knob shows as the kernel that really ran); a two-kernel backward is
+// joined with '+'
+static thread_local char g_last_attn[96] = "";
+extern "C" const char* mdm_last_attn_kernel(void) { return g_last_attn; }
+#define MDM_NOTE_ATTN(...) snprintf(g_last_attn, sizeof(g_last_attn), __VA_ARGS__)
+template <typename T, bool SPLIT = false> static const char* attn_type_name() {
+  return sizeof(T) == 2 ? "bf16" : SPLIT ? "float_split" : "float";
+}
+// queries per wave of the bf16 forward: 0 = by shape (the product), 1 / 2 = force QT; a plain int set from the host thread
+// that drives the experiment, as g_attn_bwd_mode below
+static int g_attn_fwd_mode = 0;
+extern "C" int mdm_dev_set_attn_fwd(int mode) {
+  if (mode < 0 || mode > 2) return -1;
+  g_attn_fwd_mode = mode;
+  return 0;
+}
+
 template <typename T, int D, bool SPLIT = false>
 static int attn_fwd_launch(const AttnArgs& a, hipStream_t st) {
   using G = AttnGeom<T, D>;
@@ -1276,15 +1295,18 @@ static int attn_fwd_launch(const AttnArgs& a, hipStream_t st) {
     const long blocks2 = (long)((a.L + 127) / 128) * a.B * a.H;
     // (not for a training batch at L = 256: 58 against 47-52 us at d = 96, batch 64 -- three blocks per CU instead of two do
     //  not make up for one MFMA per K / V fragment read; profiles/r06_did_not_pay.md)
-    if (blocks2 * 2 <= device_cus() && a.L > 64) {
+    const bool by_shape = blocks2 * 2 <= device_cus() && a.L > 64;
+    if (g_attn_fwd_mode == 1 || (g_attn_fwd_mode == 0 && by_shape)) {
       ensure_dynamic_lds(attn_fwd_kernel<T, D, 1, true, SPLIT>, smem);
       dim3 grid1((a.L + 63) / 64, a.B * a.H);
       hipLaunchKernelGGL((attn_fwd_kernel<T, D, 1, true, SPLIT>), grid1, dim3(256), smem, st, a);
+      MDM_NOTE_ATTN("attn_fwd_kernel<%s,%d,%d>", attn_type_name<T, SPLIT>(), D, 1);
       MDM_LAUNCH_STATUS();
     }
   }
   dim3 grid((a.L + 127) / 128, a.B * a.H);   // 32 queries per wave: every K / V fragment feeds two MFMAs
   hipLaunchKernelGGL((attn_fwd_kernel<T, D, 2, true, SPLIT>), grid, dim3(256), smem, st, a);
+  MDM_NOTE_ATTN("attn_fwd_kernel<%s,%d,%d>", attn_type_name<T, SPLIT>(), D, 2);
   MDM_LAUNCH_STATUS();
 }
 
@@ -1337,6 +1359,7 @@ static int attn_bwd_launch(AttnArgs a, void* dkc, void* dvc, size_t dc_bs, int d
         constexpr int smem32 = attn_bwd_small32_lds<D>();
         ensure_dynamic_lds(attn_bwd_small32_kernel<D>, smem32);
         hipLaunchKernelGGL((attn_bwd_small32_kernel<D>), dim3(a.B * a.H), dim3(512), smem32, st, a);
+        MDM_NOTE_ATTN("attn_bwd_small32_kernel<%d>", D);
         MDM_LAUNCH_STATUS();
       }
     }
@@ -1350,6 +1373,7 @@ static int attn_bwd_launch(AttnArgs a, void* dkc, void* dvc, size_t dc_bs, int d
         const int nb = (a.L + 255) / 256;
         hipLaunchKernelGGL((attn_bwd_dq32_kernel<D>), dim3(nb, a.B * a.H), dim3(512), smem_dq, st, a);
         hipLaunchKernelGGL((attn_bwd_dkv32_kernel<D>), dim3(nb + (a.kc ? 1 : 0), a.B * a.H), dim3(512), smem_dkv, st, a);
+        MDM_NOTE_ATTN("attn_bwd_dq32_kernel<%d>+attn_bwd_dkv32_kernel<%d>", D, D);
         MDM_LAUNCH_STATUS();
       }
     }
@@ -1359,12 +1383,14 @@ static int attn_bwd_launch(AttnArgs a, void* dkc, void* dvc, size_t dc_bs, int d
       constexpr int smem_small = 8 * G::NAT_BYTES + 4096;
       ensure_dynamic_lds(attn_bwd_small_kernel<D>, smem_small);
       hipLaunchKernelGGL((attn_bwd_small_kernel<D>), dim3(a.B * a.H), dim3(512), smem_small, st, a);
+      MDM_NOTE_ATTN("attn_bwd_small_kernel<%d>", D);
       MDM_LAUNCH_STATUS();
     }
   }
   hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, DQ_QT>), dim3((a.L + 64 * DQ_QT - 1) / (64 * DQ_QT), a.B * a.H), dim3(256), smem_q, st, a);
   const int nself = (a.L + 64 * KV_KT - 1) / (64 * KV_KT), ncross = a.kc ? (a.S + 64 * KV_KT - 1) / (64 * KV_KT) : 0;
   hipLaunchKernelGGL(kkv, dim3(nself + ncross, a.B * a.H), dim3(256), smem_kv, st, a);
+  MDM_NOTE_ATTN("attn_bwd_dq_kernel<%s,%d,%d>+attn_bwd_dkv_kernel<%s,%d,%d>", attn_type_name<T>(), D, DQ_QT, attn_type_name<T>(), D, KV_KT);
   MDM_LAUNCH_STATUS();
 }
 

@@ -11,6 +11,7 @@
     active); and the forward holds at least the analytic bytes of every recomputed activation less.
 Exactness rests on N = 2: dgamma / dbeta are summed over samples with atomics, and a two-term sum has one order.  The one
 larger case runs where those sums are per-sample rows reduced in a fixed order, and first shows that the stored path repeats."""
+import gc
 import types
 
 import pytest
@@ -382,6 +383,9 @@ def test_forward_holds_the_recomputed_activations_less(name, dtype):
     held = {}
     for on in (False, True, False, True):   # the first pair is the warm-up (packed weights, workspaces)
         with recompute(on), count_gn_conv() as cnt, torch.autocast("cuda", dtype=torch.bfloat16, enabled=dtype == torch.bfloat16):
+            # unreachable cycles that earlier tests left (whole models: gigabytes) are freed HERE, not by a collection that
+            # happens to run during the forward and would be booked as memory the forward gave back
+            gc.collect()
             torch.cuda.synchronize()
             base = torch.cuda.memory_allocated()
             loss = PC.loss_of(model(*args), inp["gys"])
