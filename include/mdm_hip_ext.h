@@ -26,6 +26,24 @@ int mdm_attn_cross_bias(const void* qkv, const void* kvc, const float* mask, con
                         const void* base, int base_ld, void* out, int B, int L, int S, int H, int d, int dtype,
                         void* stream);
 
+/* mdm_attn_cross_maps -- the probabilities of that text cross-attention term, averaged over the heads and accumulated:
+ *   acc[b, l, s] += w / H * sum_h softmax_s( q_h . k_c,h / sqrt(d) (+ bias[b, l, s]) ; live keys )       w = w_host * (*w_dev)
+ * what mdm_attn_fwd / mdm_attn_cross_addv / mdm_attn_cross_bias multiply into v_c and never write: per-token heat maps.
+ * qkv [B, L, 3C] (only q is read), kvc [B, S, 2C] (only k_c is read), mask [B, S] of 0/1 floats or NULL, bias as for
+ * mdm_attn_cross_bias or NULL (fp32 [B, L, bias_ld], bias_ld >= S and % 4 == 0, 16-byte aligned; columns [S, bias_ld)
+ * are never used and may hold anything).  A key is live where mask != 0 and bias > -1e30; a query with no live key adds 0.
+ * acc: fp32 [B, L, acc_ld], query-major like the bias, acc_ld >= S and % 4 == 0, 16-byte aligned; columns [S, acc_ld)
+ * are neither read nor written.  w_dev: a device float or NULL (= 1); w == 0 launches blocks that return before they
+ * load anything, acc untouched bit for bit -- one captured graph serves a trajectory in which only some steps record.
+ * The exponent is that of the sister kernels ((s c2) rounded, + bias log2(e), - max), so a single live key has
+ * probability exactly 1; the probabilities are fp32 in every mode and scaled by nothing but w / H.  dtype: MDM_F32,
+ * MDM_BF16, or MDM_F32_SPLIT, which runs the exact-fp32 products; d in {32, 64, 96, 128}, H <= 64, any L, any S >= 1.
+ * One launch: the heads are looped inside the block and every acc element is read once and written once by the lane that
+ * owns it.  No workspace, no atomics, deterministic, a batch row's result independent of B, forward only. */
+int mdm_attn_cross_maps(const void* qkv, const void* kvc, const float* mask, const float* bias, int bias_ld, float* acc,
+                        int acc_ld, float w_host, const float* w_dev, int B, int L, int S, int H, int d, int dtype,
+                        void* stream);
+
 /* FreeU (Si et al., CVPR 2024) fused into the up path's skip concat: backbone h [N, H, W, C1], skip r [N, H, W, C2], NHWC,
  * of dtype MDM_F32 or MDM_BF16 (the fp32-split mode has fp32 tensors: MDM_F32), arithmetic in fp32 ->
  *   out[.., 0:C1/2]   = h[.., :C1/2] * m       m = b, or with `structure` (FreeU v2)  1 + (b - 1) hm[n, y, x],

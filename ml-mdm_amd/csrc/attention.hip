@@ -1717,3 +1717,295 @@ extern "C" int mdm_attn_cross_bias(const void* qkv, const void* kvc, const float
 #undef MDM_ATTN_CROSS_BIAS
   return -1;
 }
+
+// ---------------------------------------------------------------------------------------
+// cross-attention maps:  acc[b, l, s] += w / H * sum_h softmax_s(q_h k_c,h^T / sqrt(d) (+ bias[b, l, s]); live keys)
+// ---------------------------------------------------------------------------------------
+// The text term is a softmax of its own over the S text keys, so its probabilities are an L x S quantity that never
+// touches the L x L pass: the QK^T half of attn_cross_addv_kernel (same operand plan, same masking, same bias handling,
+// same exponent: (s c2) rounded, + bias log2(e), - m) with the probabilities KEPT -- fp32 in every mode -- instead of
+// multiplied into v_c.  One block owns 16 queries of one batch row and every head of them: wave w takes the heads w,
+// w + 4, ... (each wave stages the 64-key tile of ITS head in its own quarter of the LDS), sums their probabilities in
+// registers, and the four partial sums meet in LDS in a fixed order -- so the mean over heads never goes through memory,
+// every acc element is read once and written once by the lane that holds it, there are no atomics and no workspace, the
+// result is bit-reproducible and a batch row's does not depend on B.  (Heads outer and queries inner across the waves,
+// not the other way round: the grid of L / 16 x B blocks is four times the one of 64 queries per block, and the chain
+// of dependent tiles per block four times shorter -- the recording launches of a sampling batch are few and small.)
+//   S <= 64 (one key tile): a head's softmax is complete after its tile -- one pass.
+//   S  > 64: pass 0 keeps the running (max, sum) of every (head, query) in LDS, key tile outer and head inner; pass 1 walks
+//            the tiles again, p = 2^(t - m) / l summed over the heads, then the tile's acc read-modify-write.
+// After the heads of a tile, wave w owns score tile kt = w of it: four consecutive keys per lane, one 16-byte access (the
+// group that straddles S goes element by element, so the columns [S, acc_ld) are neither read nor written).  Its acc
+// elements are requested at the top of the tile, ahead of every head's MFMAs, and stored after the reduction: in the one
+// in-order counter of gfx950 the loads trail nothing but the bias loads (with several key tiles: the stores of the tile
+// before, a whole head loop earlier).
+// w = w_host * (*w_dev): 0 returns before anything is loaded (block-uniform) -- one captured graph serves a trajectory
+// in which only some steps record.
+namespace mdm {
+
+struct AttnMapsArgs {
+  const void* q; size_t q_bs; int q_rs;     // row (b, i), head h, channel c: q[b * q_bs + i * q_rs + h * d + c]
+  const void* kc; size_t c_bs; int c_rs;
+  const float* mask;                         // [B, S] or null
+  const float* bias; int bias_ld;            // [B, L, bias_ld] or null (BIAS = false)
+  float* acc; int acc_ld;                    // [B, L, acc_ld]
+  float w_host; const float* w_dev;          // w_dev: device float or null
+  int B, H, L, S;
+  float scale;                               // 1/sqrt(d)
+};
+
+// load_nat_tile by ONE wave into its own tile
+template <typename T, int D>
+__device__ __forceinline__ void load_nat_tile_wave(char* dst, const T* src, int rs, int row0, int nrows, int lane) {
+  using G = AttnGeom<T, D>;
+  for (int c = lane; c < 64 * G::CPR; c += 64) {
+    const int row = c / G::CPR, cc = c - row * G::CPR;
+    const bool ok = row0 + row < nrows;
+    uint4 val = *reinterpret_cast<const uint4*>(src + (ok ? (size_t)(row0 + row) * rs + cc * G::EPV : (size_t)0));
+    val.x = ok ? val.x : 0u; val.y = ok ? val.y : 0u; val.z = ok ? val.z : 0u; val.w = ok ? val.w : 0u;
+    *reinterpret_cast<uint4*>(dst + (cc >> 3) * (64 * 128) + lds_chunk_off(row, cc & 7)) = val;
+  }
+}
+
+template <typename T, int D, bool BIAS>
+__global__ __launch_bounds__(256) void attn_cross_maps_kernel(AttnMapsArgs p) {
+  using G = AttnGeom<T, D>;
+  using F = Frag<T>;
+  constexpr int KSTEPS = G::KSTEPS, DS = G::DS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  float w = p.w_host;
+  if (p.w_dev) w *= *p.w_dev;
+  if (w == 0.f) return;   // block-uniform, before any load of q or k_c: acc untouched
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int quad = lane >> 4, l16 = lane & 15;
+  char* Ks = smem + wave * G::NAT_BYTES;                                 // this wave's key tile ...
+  f32x4* red = reinterpret_cast<f32x4*>(smem);                           // ... whose head is the wave's partial sums later:
+  constexpr int RED_STRIDE = G::NAT_BYTES / (int)sizeof(f32x4);          //     red[wave * RED_STRIDE + kt * 64 + lane]
+  static_assert(G::NAT_BYTES >= 4 * 64 * (int)sizeof(f32x4), "a wave's partial sums fit in its key tile");
+  float2* stats = reinterpret_cast<float2*>(smem + 4 * G::NAT_BYTES);   // [H][16 queries]: running max, running sum
+  const int b = blockIdx.y;
+  const int qi = blockIdx.x * 16 + l16;
+  const bool q_ok = qi < p.L;
+  const int nk = p.S, rs = p.c_rs;
+  const float wh = w / (float)p.H;
+  const float c2 = p.scale * 1.4426950408889634f;   // scores -> base-2 exponent
+
+  const T* Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.q_bs + (size_t)(q_ok ? qi : 0) * p.q_rs + quad * 8;
+  const T* Kp = reinterpret_cast<const T*>(p.kc) + (size_t)b * p.c_bs;
+  const float* mrow = p.mask ? p.mask + (size_t)b * p.S : nullptr;
+  [[maybe_unused]] const float* brow = nullptr;
+  if constexpr (BIAS) brow = p.bias + ((size_t)b * p.L + (q_ok ? qi : 0)) * p.bias_ld;
+  float* arow = p.acc + ((size_t)b * p.L + (q_ok ? qi : 0)) * p.acc_ld;
+
+  const bool single = nk <= 64;   // block-uniform
+  const int passes = single ? 1 : 2;
+  for (int pass = 0; pass < passes; ++pass) {
+    const bool emit = single || pass == 1;   // this pass forms probabilities and updates acc
+    for (int k0 = 0; k0 < nk; k0 += 64) {
+      // the lane's bias of this tile, shared by all heads: keys key0 + [0, 4) per score tile; key0 % 4 == 0 and
+      // bias_ld % 4 == 0 >= S keep a load that starts below S inside the row
+      [[maybe_unused]] f32x4 bv[4];
+      if constexpr (BIAS) {
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+          const int key0 = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4;
+          const bool in = q_ok && key0 < nk;
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          bv[kt] = in ? *reinterpret_cast<const f32x4*>(brow + (in ? key0 : 0)) : z;
+        }
+      }
+      // ... and the acc elements this wave will own (score tile kt = wave), requested before any head's MFMAs
+      const int akey0 = k0 + (wave >> 1) * 32 + quad * 8 + (wave & 1) * 4;
+      f32x4 av = {0.f, 0.f, 0.f, 0.f};
+      if (emit && q_ok) {
+        if (akey0 + 4 <= nk) {
+          av = *reinterpret_cast<const f32x4*>(arow + akey0);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (akey0 + i < nk) av[i] = arow[akey0 + i];
+        }
+      }
+      f32x4 pa[4];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) pa[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+      for (int h0 = 0; h0 < p.H; h0 += 4) {
+        const int h = h0 + wave;
+        const bool active = h < p.H;   // wave-uniform
+        F qf[DS];
+        if (active) {
+#pragma unroll
+          for (int ks = 0; ks < DS; ++ks) frag_from_global_x(qf[ks], Q + (size_t)h * D + ks * 32, q_ok);
+        }
+        __syncthreads();   // every wave is done with what the tiles held before (the partial sums of the tile before)
+        if (active) load_nat_tile_wave<T, D>(Ks, Kp + (size_t)h * D, rs, k0, nk, lane);
+        __syncthreads();
+        if (!active) continue;
+
+        f32x4 s[4];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+          const int row = perm_row(kt, l16);
+          s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < DS; ++ks) {
+            F kf;
+            load_frag_x(kf, Ks + (ks / KSTEPS) * (64 * 128), row, ks % KSTEPS, quad);
+            mma16(s[kt], kf, qf[ks]);
+          }
+        }
+        // The first reads of s sit behind block-uniform branches (`full`, `pass`), and on a taken edge the compiler (ROCm
+        // 7.2) leaves the last MFMA's XDL write -> VALU read hazard 5 wait states in the unbiased instantiations
+        // (tools/mfma_hazard_scan.py; the case of conv3x3_direct_kernel, gemm_conv.hip): fence the MFMAs from the softmax
+        // and pay the wait states here.
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_nop 7" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        // the lane holds key positions (kt>>1)*32 + quad*8 + (kt&1)*4 + i of its query column (lane & 15)
+        {
+#pragma clang fp contract(off)
+          const bool full = (k0 + 64 <= nk) && !mrow;   // block-uniform
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              float t = s[kt][i] * c2;
+              if constexpr (BIAS) {
+                const int key = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4 + i;
+                bool ok = key < nk && bv[kt][i] > -1e30f;   // false for NaN too
+                if (ok && mrow) ok = mrow[key] != 0.f;
+                const float bl = (ok ? bv[kt][i] : 0.f) * 1.4426950408889634f;
+                t = ok ? t + bl : -3.0e38f;
+              } else if (!full) {
+                const int key = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4 + i;
+                bool ok = key < nk;
+                if (ok && mrow) ok = mrow[key] != 0.f;
+                t = ok ? t : -3.0e38f;
+              }
+              s[kt][i] = t;
+            }
+          if (pass == 0) {
+            float m_run = -1e30f, l_run = 0.f;
+            if (k0 > 0) {
+              const float2 st = stats[h * 16 + l16];
+              m_run = st.x; l_run = st.y;
+            }
+            float mx = -3.0e38f;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][i]);
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float m_new = fmaxf(m_run, fmaxf(mx, -1e30f));   // a fully masked tile leaves m_run alone
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            float ls = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const float e = __builtin_amdgcn_exp2f(s[kt][i] - m_new);   // masked: -3e38 - m = -3e38 -> 0
+                s[kt][i] = e; ls += e;
+              }
+            ls += __shfl_xor(ls, 16, 64);
+            ls += __shfl_xor(ls, 32, 64);
+            const float l_new = l_run * alpha + ls;
+            if (single) {
+              const float inv = l_new > 0.f ? 1.f / l_new : 0.f;   // no live key: the query contributes 0
+#pragma unroll
+              for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pa[kt][i] += s[kt][i] * inv;
+            } else if (quad == 0) {
+              stats[h * 16 + l16] = float2{m_new, l_new};   // read back by this wave only, tiles later
+            }
+          } else {
+            const float2 st = stats[h * 16 + l16];
+            const float inv = st.y > 0.f ? 1.f / st.y : 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) pa[kt][i] += __builtin_amdgcn_exp2f(s[kt][i] - st.x) * inv;
+          }
+        }
+      }
+
+      if (emit) {   // block-uniform
+        // the waves' partial sums over their heads, each into the head of its own tile (its reads of it are done), then
+        // wave w adds up score tile w in the fixed order 0, 1, 2, 3
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) red[wave * RED_STRIDE + kt * 64 + lane] = pa[kt];
+        __syncthreads();
+        f32x4 sum = red[0 * RED_STRIDE + wave * 64 + lane];
+#pragma unroll
+        for (int ww = 1; ww < 4; ++ww) {
+          const f32x4 v = red[ww * RED_STRIDE + wave * 64 + lane];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) sum[i] += v[i];
+        }
+        if (q_ok) {
+#pragma clang fp contract(off)
+          if (akey0 + 4 <= nk) {
+            f32x4 r;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r[i] = av[i] + sum[i] * wh;
+            *reinterpret_cast<f32x4*>(arow + akey0) = r;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              if (akey0 + i < nk) arow[akey0 + i] = av[i] + sum[i] * wh;
+          }
+        }
+      }
+    }
+  }
+}
+
+}  // namespace mdm
+
+template <typename T, int D, bool BIAS>
+static int attn_cross_maps_launch(const AttnMapsArgs& a, hipStream_t st) {
+  using G = AttnGeom<T, D>;
+  const int smem = 4 * G::NAT_BYTES + a.H * 16 * (int)sizeof(float2);
+  ensure_dynamic_lds(attn_cross_maps_kernel<T, D, BIAS>, 4 * G::NAT_BYTES + 64 * 16 * (int)sizeof(float2));   // H <= 64: one size
+  dim3 grid((a.L + 15) / 16, a.B);   // 16 queries per block, a wave per head
+  hipLaunchKernelGGL((attn_cross_maps_kernel<T, D, BIAS>), grid, dim3(256), smem, st, a);
+  MDM_LAUNCH_STATUS();
+}
+
+// qkv [B, L, 3C] (only q is read), kvc [B, S, 2C] (only k_c), mask [B, S] or null, bias [B, L, bias_ld] or null,
+// acc [B, L, acc_ld] fp32 (include/mdm_hip_ext.h); no workspace.
+extern "C" int mdm_attn_cross_maps(const void* qkv, const void* kvc, const float* mask, const float* bias, int bias_ld,
+                                   float* acc, int acc_ld, float w_host, const float* w_dev, int B, int L, int S, int H,
+                                   int d, int dtype, void* stream) {
+  MDM_CHECK_ARG(qkv && kvc && acc);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_F32_SPLIT);
+  if (dtype == DT_F32_SPLIT) dtype = DT_F32;   // exact fp32 products, as mdm_attn_cross_addv
+  MDM_CHECK_ARG(B > 0 && L > 0 && S > 0);
+  MDM_CHECK_ARG(H > 0 && H <= 64);   // the (max, sum) of every (head, query) of a block: H * 128 bytes of LDS
+  MDM_CHECK_ARG(d == 32 || d == 64 || d == 96 || d == 128);
+  MDM_CHECK_ARG(!bias || (bias_ld >= S && bias_ld % 4 == 0 && (uintptr_t)bias % 16 == 0));
+  MDM_CHECK_ARG(acc_ld >= S && acc_ld % 4 == 0 && (uintptr_t)acc % 16 == 0);   // the lanes' 16-byte accesses
+  const int C = H * d;
+  AttnMapsArgs a = {};
+  a.q = qkv; a.q_bs = (size_t)L * 3 * C; a.q_rs = 3 * C;
+  a.kc = kvc; a.c_bs = (size_t)S * 2 * C; a.c_rs = 2 * C;
+  a.mask = mask; a.bias = bias; a.bias_ld = bias_ld;
+  a.acc = acc; a.acc_ld = acc_ld; a.w_host = w_host; a.w_dev = w_dev;
+  a.B = B; a.H = H; a.L = L; a.S = S; a.scale = 1.0f / sqrtf((float)d);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!w_dev && w_host == 0.f) return 0;   // nothing to add, nothing to launch
+#define MDM_ATTN_CROSS_MAPS(DD)                                                                                    \
+  case DD:                                                                                                         \
+    if (bias) return dtype == DT_F32 ? attn_cross_maps_launch<float, DD, true>(a, st) : attn_cross_maps_launch<bf16, DD, true>(a, st); \
+    return dtype == DT_F32 ? attn_cross_maps_launch<float, DD, false>(a, st) : attn_cross_maps_launch<bf16, DD, false>(a, st);
+  switch (d) {
+    MDM_ATTN_CROSS_MAPS(32) MDM_ATTN_CROSS_MAPS(64) MDM_ATTN_CROSS_MAPS(96) MDM_ATTN_CROSS_MAPS(128)
+    default: MDM_CHECK_ARG(!"unsupported head dim");
+  }
+#undef MDM_ATTN_CROSS_MAPS
+  return -1;
+}

@@ -20,6 +20,8 @@ Layout of the package
   pag.py          perturbed-attention guidance: select / perturbed (the samplers' pag_scale / pag_layers)
   regions.py      regional prompts and token weights, a bias on the text cross-attention logits: RegionPrompts / concat /
                   applied (the samplers' regions / region_layers)
+  attn_maps.py    cross-attention maps, the text term's probabilities recorded per token: AttnMaps / record / applied (the
+                  samplers' attn_maps)
   freeu.py        FreeU on the up path's skip concat: FreeU / select / applied (the samplers' freeu)
   guidance.py     projected and rescaled classifier-free guidance (APG, CFG rescale, guidance interval): CFG / cfg_combine
                   (the samplers' cfg)
@@ -53,6 +55,8 @@ from .samplers import LossGuide, SASolver  # noqa: F401,E402
 from . import pag  # noqa: F401,E402
 from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
+from . import attn_maps  # noqa: F401,E402
+from .attn_maps import AttnMaps  # noqa: F401,E402
 from . import freeu  # noqa: F401,E402
 from .freeu import FreeU  # noqa: F401,E402
 from . import guidance  # noqa: F401,E402
@@ -72,6 +76,8 @@ __all__ = [
     "pag",
     "regions",
     "RegionPrompts",
+    "attn_maps",
+    "AttnMaps",
     "UNet",
     "UNetConfig",
     "ResNetConfig",

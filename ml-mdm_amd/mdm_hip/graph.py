@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops, regions as _regions
+from . import attn_maps as _attn_maps, ops, regions as _regions
 from . import tiling as _tiling
 from .samplers import SampleOptions, _checked_rule, gather_windows, merge_windows, model_rows, repeat_rows, split_rows
 from .unet import switch_state, switchable
@@ -61,7 +61,7 @@ class GraphedDenoiser(nn.Module):
         if torch.is_grad_enabled() or self.model.training or micros:
             return self.model(x_t, times, conditioning, cond_mask, micros)
         switches = switch_state(self._switchable)
-        if any(h is not None for h in switches["_cross_bias"]):
+        if any(h is not None for h in switches["_cross_bias"] + switches["_attn_rec"]):   # (a recorder: the caller's too)
             return self.model(x_t, times, conditioning, cond_mask, micros)
         if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
             self._graphs.clear()
@@ -199,6 +199,12 @@ class GraphedSampler:
         # regional prompts: static bias buffers, one per attention resolution -- the warm-up passes discover the resolutions
         # (each buffer starts as a copy of the caller's bias); every sample() call fills them anew
         bias_s = _regions.StaticBias(bias_source) if bias_source is not None else None
+        # cross-attention maps: static accumulators, one per attention resolution, found by the warm-up passes too, and the
+        # table of gates, one row per replay; sample() zeroes the former and fills the latter.  Until then: every row records
+        rec_s = rec_gate = None
+        if opts.attn_maps is not None:
+            rec_s = _attn_maps.StaticRows(opts.attn_maps.rows_for(*opts.blocks(guidance), dev))
+            rec_gate = torch.ones(len(t_host), dtype=torch.float32, device=dev)
 
         def body():
             t = tab_t.index_select(0, idx)
@@ -216,7 +222,9 @@ class GraphedSampler:
                 xin, tin = repeat_rows(x_static, times, reps)
             else:   # one gather per scale in place of the repeat; the merge below hands the step whole canvases
                 xin, tin = gather_windows(x_static, tiles, ratios, reps), _tiling.time_rows(times, T, reps)
-            with opts.switches(vm, guidance, B * T, names=names, bias=bias_s):
+            if rec_s is not None:
+                rec_s.gate = rec_gate.index_select(0, idx)
+            with opts.switches(vm, guidance, B * T, names=names, bias=bias_s, rec=rec_s):
                 preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
             preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
             if out_scale != 0:
@@ -260,6 +268,8 @@ class GraphedSampler:
         torch.cuda.current_stream().wait_stream(side)
         if bias_s is not None:
             bias_s.freeze()   # a resolution first met during the capture would be an allocation inside the graph: an error
+        if rec_s is not None:
+            rec_s.freeze()    # the same; and the capture counts the launches of one step per resolution
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             body()
@@ -268,7 +278,8 @@ class GraphedSampler:
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
                    t_host=t_host, s_host=s_host, rows=tab_rule, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
-                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, keep=(tab_t, tab_s, tab_jump, tab_prev, state, cfg_state))
+                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, rec=rec_s, rec_gate=rec_gate,
+                   keep=(tab_t, tab_s, tab_jump, tab_prev, state, cfg_state))
         self._graphs[key] = ent
         return ent
 
@@ -288,6 +299,10 @@ class GraphedSampler:
         ``copy_`` from ``regions`` on every call (the pattern of the known images), and its body hands the switch a handle
         over those buffers.  The graph key holds ("regions", S, ld, the resolved layer names): other masks or weights
         replay the same graph, another S or layer set captures anew.
+        ``attn_maps``: each graph entry owns static accumulators, one per attention resolution, zeroed at the start of every
+        call outside the graph, and a table of gates, one per row, that the call fills from ``attn_maps.interval``: a row
+        outside it launches the same kernel, which returns before it loads anything.  After the last replay the accumulators
+        are copied into ``attn_maps``.  The graph key holds ("attn_maps", S, ld, the resolved layer names).
         ``pag_scale`` / ``pag_layers``: the static conditioning and micros buffers carry the perturbed block's rows and one
         combine kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
         ``tiles``: ``image_side`` may be (H, W).  The static conditioning and micros buffers carry every row once per
@@ -338,6 +353,10 @@ class GraphedSampler:
         if regions is not None and (regions.rows != xs[0].shape[0] or regions.S != cond.shape[1]):
             raise ValueError("regions over %d rows of %d tokens for a batch of %d images with %d tokens"
                              % (regions.rows, regions.S, xs[0].shape[0], cond.shape[1]))
+        maps = opts.attn_maps
+        if maps is not None and (maps.rows != xs[0].shape[0] or maps.S != cond.shape[1]):
+            raise ValueError("attn_maps over %d rows of %d tokens for a batch of %d images with %d tokens"
+                             % (maps.rows, maps.S, xs[0].shape[0], cond.shape[1]))
         names = opts.layer_names(model.vision_model)
         # the perturbed block repeats the conditional rows of everything per-row; tiles repeat every row once per window
         T = 1
@@ -388,11 +407,17 @@ class GraphedSampler:
             run_on[first:] = seen > 0
             ent["cfg_w_gate"].copy_(torch.from_numpy(w_on))
             ent["cfg_run_gate"].copy_(torch.from_numpy(run_on))
+        if maps is not None:
+            rec_on = np.asarray([maps.on(t, smp.n_steps) for t in ent["t_host"]], dtype="float32")
+            ent["rec_gate"].copy_(torch.from_numpy(rec_on))
+            ent["rec"].zero()
         # the rule's rows of this call, counted from its first row: a late start is a trajectory of its own
         ent["rows"][first:].copy_(torch.from_numpy(rule.rows(smp, ent["t_host"][first:], ent["s_host"][first:])))
         if seed is not None:
             ent["rng"].state.copy_(torch.tensor([seed & (2**63 - 1), 0], dtype=torch.int64))
         for _ in range(ent["n"] - first):
             ent["graph"].replay()
+        if maps is not None:
+            ent["rec"].flush(maps, int(rec_on[first:].sum()))
         out = [x.clone() for x in ent["x"]]
         return smp._postprocess(smp._from_scales(out), clip=True)

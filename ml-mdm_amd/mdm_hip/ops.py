@@ -2228,6 +2228,52 @@ def attention_biased(qkv, kvc, mask, bias, heads, pag_rows=0):
     return out
 
 
+@torch.no_grad()
+def attn_cross_maps(qkv, kvc, mask, heads, acc, bias=None, weight=1.0, gate=None, row0=0, rows=None):
+    """acc[r - row0] += weight * gate / heads * sum_h softmax(q_h k_c,h^T / sqrt(d) [+ bias] [masked; bias <= -1e30
+    excludes]) for the batch rows r in [row0, row0 + rows) of ``qkv`` [N, L, 3C] / ``kvc`` [N, S, 2C] / ``mask`` [N, S] /
+    ``bias`` (fp32 [N, L, ld], as ``attn_cross_bias`` takes it) -- the probabilities of the text cross-attention, mean over
+    heads (include/mdm_hip_ext.h mdm_attn_cross_maps).  ``acc``: fp32 [rows, L, ld], ld >= S, ld % 4 == 0, contiguous,
+    updated in place and returned; its columns [S, ld) are left alone.  ``gate``: a device float[1] or None (= 1) -- 0
+    leaves ``acc`` untouched, which lets one captured graph skip steps.  Reads detached values under no_grad: legal inside
+    a forward that records autograd.  CPU tensors: ``attn_maps.cross_maps``."""
+    _require_gpu(qkv)
+    if kvc is None:
+        raise _lib.MdmHipError("attn_cross_maps: no text keys (kvc is None) -- there is no cross-attention to record")
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
+    N, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    row0 = int(row0)
+    rows = N - row0 if rows is None else int(rows)
+    if not (0 <= row0 and 0 < rows and row0 + rows <= N):
+        raise _lib.MdmHipError("attn_cross_maps: rows [%d, %d) of a batch of %d" % (row0, row0 + rows, N))
+    if (acc.dim() != 3 or tuple(acc.shape[:2]) != (rows, L) or acc.shape[2] < S or acc.shape[2] % 4
+            or not acc.is_contiguous()):
+        raise _lib.MdmHipError("attn_cross_maps: acc %s for rows = %d, L = %d, S = %d (wanted a contiguous [rows, L, ld], "
+                               "ld >= S, ld %% 4 == 0)" % (tuple(acc.shape), rows, L, S))
+    if acc.dtype != torch.float32 or acc.device != qkv.device:
+        raise _lib.MdmHipError("attn_cross_maps: acc is fp32 on the tensors' device (got %s on %s)" % (acc.dtype, acc.device))
+    if bias is not None:
+        if bias.dim() != 3 or bias.shape[0] != N or bias.shape[1] != L or bias.shape[2] < S or bias.shape[2] % 4:
+            raise _lib.MdmHipError("attn_cross_maps: bias %s for N = %d, L = %d, S = %d (wanted [N, L, ld], ld >= S, "
+                                   "ld %% 4 == 0)" % (tuple(bias.shape), N, L, S))
+        if bias.dtype != torch.float32 or bias.device != qkv.device:
+            raise _lib.MdmHipError("attn_cross_maps: the bias is fp32 on the tensors' device (got %s on %s)"
+                                   % (bias.dtype, bias.device))
+        bias = _c(bias.detach())
+    if gate is not None and (gate.dtype != torch.float32 or gate.numel() != 1 or gate.device != qkv.device):
+        raise _lib.MdmHipError("attn_cross_maps: gate is one fp32 value on the tensors' device (got %s %s on %s)"
+                               % (gate.dtype, tuple(gate.shape), gate.device))
+    m32 = _c(mask.detach().float()) if mask is not None else None
+    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
+    _prof_wrap("attn_cross_maps_kernel<d=%d> L=%d" % (d, L), 2.0 * rows * heads * L * S * d, lambda: _lib.check(
+        _lib.lib().mdm_attn_cross_maps(off(qkv), off(kvc), off(m32), off(bias), 0 if bias is None else bias.shape[-1],
+                                       _p(acc), acc.shape[-1], float(weight), _p(gate), rows, L, S, heads, d, _dt_mm(qkv),
+                                       _stream()),
+        "mdm_attn_cross_maps",
+    ), kind="attn")
+    return acc
+
+
 # --------------------------------------------------------------------------------------
 # streaming helpers
 # --------------------------------------------------------------------------------------

@@ -42,6 +42,7 @@ from . import freeu as _freeu
 from . import guidance as _guidance
 from . import ops, pag
 from . import regions as _regions
+from . import attn_maps as _attn_maps
 from . import tiling as _tiling
 from .unet import switched
 
@@ -727,11 +728,19 @@ class SampleOptions:
     act per window.  A nested model takes window, stride and canvas as multiples of its largest ratio.  One window equal
     to the canvas changes no bit.  All T windows go through ONE denoiser call: memory grows with the canvas.
 
-    The three model switches (perturbed rows, region bias, FreeU) are held around each step's denoiser call only
+    ``attn_maps = maps`` (a ``mdm_hip.AttnMaps`` over the conditional rows and the S tokens of ``lm_outputs``): the
+    ``SelfAttention`` layers with text keys that ``maps.layers`` selects add the probabilities of their text cross-attention
+    -- the biased ones under ``regions`` --, mean over heads, into ``maps`` (``ops.attn_cross_maps``, one launch per layer
+    and recorded step; CPU tensors: ``attn_maps.cross_maps``) for the conditional block of the model batch, in the steps
+    of ``maps.interval``.  The layers' outputs are computed as before: the images do not change by a bit.  Reads detached
+    values, so it composes with ``guide`` too.
+
+    The model switches (perturbed rows, region bias, FreeU, the map recorder) are held around each step's denoiser call only
     (``switches``), never across a ``yield``, and a switch that is off is not even resolved.  What excludes what
     (``check``: NotImplementedError): ``guide`` with each of the other four, because their kernels have no backward or, for
-    ``cfg``, no Jacobian; ``pag_scale`` with ``cfg``; ``guide`` with ``tiles`` (no backward); and ``regions`` with ``tiles``
-    (the bias is laid out over the whole canvas).  Everything else composes."""
+    ``cfg``, no Jacobian; ``pag_scale`` with ``cfg``; ``guide`` with ``tiles`` (no backward); ``regions`` with ``tiles``
+    (the bias is laid out over the whole canvas); and ``attn_maps`` with ``tiles`` (a window's queries are not the
+    canvas's).  Everything else composes."""
 
     guide: object = None
     pag_scale: float = 0.0
@@ -741,6 +750,7 @@ class SampleOptions:
     freeu: object = None
     cfg: object = None
     tiles: object = None
+    attn_maps: object = None
 
     REFUSED = {
         ("guide", "pag"): "guide= together with pag_scale != 0: the perturbed rows' attention kernel (mdm_attn_cross_addv) "
@@ -758,6 +768,8 @@ class SampleOptions:
                             "backward, so the guide's input gradient cannot pass them",
         ("regions", "tiles"): "regions= together with tiles=: the bias is laid out per query position of the whole canvas, "
                               "and cropping it per window is not implemented",
+        ("attn_maps", "tiles"): "attn_maps= together with tiles=: a window's queries are not the canvas's, and merging the "
+                                "maps of the windows is not implemented",
     }
 
     @classmethod
@@ -769,7 +781,8 @@ class SampleOptions:
         """every type and range check, and the pairs of ``REFUSED``; several things wrong: guide, pag, regions, freeu, cfg,
         tiles"""
         on = dict(guide=self.guide is not None, pag=self.pag_scale != 0, regions=self.regions is not None,
-                  freeu=self.freeu is not None, cfg=self.cfg is not None, tiles=self.tiles is not None)
+                  freeu=self.freeu is not None, cfg=self.cfg is not None, tiles=self.tiles is not None,
+                  attn_maps=self.attn_maps is not None)
 
         def refuse(a, b):
             if on[a] and on[b]:
@@ -796,6 +809,9 @@ class SampleOptions:
             raise ValueError("tiles = %r (wanted a mdm_hip.Tiles)" % (self.tiles,))
         refuse("guide", "tiles")
         refuse("regions", "tiles")
+        if on["attn_maps"] and not isinstance(self.attn_maps, _attn_maps.AttnMaps):
+            raise ValueError("attn_maps = %r (wanted a mdm_hip.AttnMaps)" % (self.attn_maps,))
+        refuse("attn_maps", "tiles")
         return self
 
     def blocks(self, guidance_scale):
@@ -807,15 +823,17 @@ class SampleOptions:
         """the ``CFG`` that acts at this guidance scale: None at 1, where there is nothing to combine"""
         return self.cfg if guidance_scale != 1 else None
 
-    def switches(self, model, guidance_scale, B, device=None, names=None, bias=None):
+    def switches(self, model, guidance_scale, B, device=None, names=None, bias=None, rec=None, step=None):
         """-> the context manager of one denoiser call over ``B`` images: the model switches that are on -- perturbed rows,
-        region bias, FreeU -- as ONE ``unet.switched``.  They touch disjoint attributes, so there is no order among them to
-        get right.  A captured graph body passes the names it resolved (``layer_names``) and its ``StaticBias``; the eager
-        samplers pass neither."""
-        if self.pag_scale == 0 and self.regions is None and self.freeu is None:
+        region bias, FreeU, the map recorder -- as ONE ``unet.switched``.  They touch disjoint attributes, so there is no
+        order among them to get right.  A captured graph body passes the names it resolved (``layer_names``), its
+        ``StaticBias`` and its ``attn_maps.StaticRows`` (``rec``); the eager samplers pass none of them, and ``step`` =
+        (the time the step starts from, ``num_diffusion_steps``), by which ``attn_maps.interval`` decides whether this call
+        records (None: it does)."""
+        if self.pag_scale == 0 and self.regions is None and self.freeu is None and self.attn_maps is None:
             return _UNCHANGED
         vision_model = getattr(model, "vision_model", model)
-        pag_layers, region_layers = (self.pag_layers, self.region_layers) if names is None else names
+        pag_layers, region_layers = (self.pag_layers, self.region_layers) if names is None else names[:2]
         on = []
         if self.pag_scale != 0:
             on.append(pag.perturbed(vision_model, pag_layers, rows=B))
@@ -827,12 +845,25 @@ class SampleOptions:
             on.append(_regions.applied(vision_model, bias, region_layers))
         if self.freeu is not None:
             on.append(_freeu.applied(vision_model, self.freeu))
+        if self.attn_maps is not None:
+            if rec is None and (step is None or self.attn_maps.on(*step)):
+                if self.attn_maps.rows != B:
+                    raise ValueError("attn_maps over %d rows for a batch of %d images" % (self.attn_maps.rows, B))
+                rec = self.attn_maps.rows_for(*self.blocks(guidance_scale), device)
+            if rec is not None:
+                on.append(_attn_maps.applied(vision_model, rec, self.attn_maps.layers if names is None else names[2]))
+        if not on:   # a recorder outside its interval: this call launches what it always did
+            return _UNCHANGED
         return switched(s for one in on for s in one.settings)
 
     def layer_names(self, vision_model):
-        """-> (perturbed layers, biased layers) as tuples of module names: hashable; () where the option is off"""
-        return (pag.layer_names(vision_model, self.pag_layers) if self.pag_scale != 0 else (),
-                _regions.layer_names(vision_model, self.region_layers) if self.regions is not None else ())
+        """-> (perturbed layers, biased layers) as tuples of module names: hashable; () where the option is off; with
+        ``attn_maps``, and only then, a third: the recording layers"""
+        names = (pag.layer_names(vision_model, self.pag_layers) if self.pag_scale != 0 else (),
+                 _regions.layer_names(vision_model, self.region_layers) if self.regions is not None else ())
+        if self.attn_maps is not None:
+            names += (_attn_maps.layer_names(vision_model, self.attn_maps.layers),)
+        return names
 
     def graph_key(self, vision_model, guidance_scale, names):
         """the options' part of a ``GraphedSampler`` key, ``names`` being ``layer_names`` of the model: one component per
@@ -848,6 +879,8 @@ class SampleOptions:
             key += (self.cfg.key(),)
         if self.tiles is not None:
             key += (self.tiles.graph_key(),)
+        if self.attn_maps is not None:   # (the interval is a table of gates that every call rewrites: no part of the key)
+            key += (("attn_maps", self.attn_maps.S, self.attn_maps.ld, names[2]),)
         return key
 
 
@@ -1232,7 +1265,7 @@ class Sampler(nn.Module):
         return (pc if pu is None else pu + guidance_scale * (pc - pu)), extras
 
     def _forward_model_raw(self, model, x_t, t, lm_outputs, lm_mask, micros, guidance_scale, opts=SampleOptions(),
-                           rows=None):
+                           rows=None, step=None):
         """The one denoiser call of a step.  ``x_t``: the list of scales -> (conditional predictions, unconditional
         predictions or Nones, extras, perturbed predictions or None), one entry per scale: the guidance combine itself is
         folded into the step kernel.  The model runs once, on [uncond | cond | perturbed] -- the blocks ``opts.blocks``
@@ -1241,7 +1274,7 @@ class Sampler(nn.Module):
         the times are repeated per window, and the predictions are merged back to whole canvases (``merge_windows``) before
         they are split; the extras are those of each image's window 0.  ``rows``: (T, (lm_outputs, lm_mask, micros)) -- the
         window count of the checked geometry and what ``model_rows`` made for this call; ``_sample`` makes both once, not
-        once per step."""
+        once per step.  ``step``: (the time the step starts from, ``num_diffusion_steps``) for ``opts.attn_maps``'s interval."""
         uncond, pert = opts.blocks(guidance_scale)
         B = x_t[0].shape[0]
         tiles, T = opts.tiles, 1
@@ -1256,7 +1289,7 @@ class Sampler(nn.Module):
             xin, tin = repeat_rows(x_t, t, reps)
         else:
             xin, tin = gather_windows(x_t, tiles, ratios, reps), _tiling.time_rows(t, T, reps)
-        with opts.switches(model, guidance_scale, B * T, x_t[0].device):
+        with opts.switches(model, guidance_scale, B * T, x_t[0].device, step=step):
             preds, extras = self._call_model(model, xin, tin, lm_outputs, lm_mask, micros)
         if tiles is not None:
             preds = merge_windows(preds, tiles, ratios, canvases)
@@ -1342,7 +1375,7 @@ class Sampler(nn.Module):
             thr = []   # one entry per scale, hi -> lo
         with grad:
             pcs, pus, _, pps = self._forward_model_raw(model, x_in, t - 1, lm_outputs, lm_mask, micros, guidance_scale,
-                                                       opts, rows)   # model sees t-1 (:415)
+                                                       opts, rows, (time_step, self.n_steps))   # model sees t-1 (:415)
         outs = (x_in, pcs, pus)
         if guide is not None:   # the update itself: unchanged, on detached tensors
             outs = ([None if v is None else v.detach() for v in vs] for vs in outs)

@@ -263,6 +263,9 @@ class SelfAttention(nn.Module):
     # regional prompts / token weights (mdm_hip.regions.applied): a handle whose bias(N, H, W) -> fp32 [N, H * W, ld] is added
     # to the text logits (ops.attention_biased).  None: as above.
     _cross_bias = None
+    # cross-attention maps (mdm_hip.attn_maps.applied / record): a handle whose record(qkv, kvc, cond_mask, heads, bias, N,
+    # H, W) accumulates the text term's probabilities after the attention call (ops.attn_cross_maps).  None: as above.
+    _attn_rec = None
 
     def forward(self, x, cond=None, cond_mask=None):
         N, H, W, C = x.shape
@@ -303,6 +306,9 @@ class SelfAttention(nn.Module):
                                   self._pag_rows)
         else:
             a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
+        if self._attn_rec is not None and kvc is not None:   # reads q, k_c, the mask and the bias; writes its own buffer
+            self._attn_rec.record(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask, self.num_heads,
+                                  self._cross_bias.bias(N, H, W) if self._cross_bias is not None else None, N, H, W)
         a = a.reshape(N, H, W, C)
         if fp8 is not None and fp8.on("proj_out"):
             x = fp8.conv(a, self.proj_out, residual=x)
@@ -395,9 +401,10 @@ class ResNetBlock(nn.Module):
 
 # --------------------------------------------------------------------------------------
 # The sampling switches: the class attributes above that an instance attribute overrides for the duration of a ``with``
-# block (``pag.perturbed``: _pag_rows; ``regions.applied``: _cross_bias; ``freeu.applied``: _freeu, _freeu_name).
+# block (``pag.perturbed``: _pag_rows; ``regions.applied``: _cross_bias; ``freeu.applied``: _freeu, _freeu_name;
+# ``attn_maps.applied``: _attn_rec).
 # --------------------------------------------------------------------------------------
-SWITCHES = ("_pag_rows", "_cross_bias", "_freeu")   # what changes the launches of a forward (_freeu_name only names a block)
+SWITCHES = ("_pag_rows", "_cross_bias", "_freeu", "_attn_rec")   # what changes the launches of a forward (_freeu_name only names a block)
 
 
 class switched:
