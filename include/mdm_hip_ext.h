@@ -44,6 +44,29 @@ int mdm_attn_cross_maps(const void* qkv, const void* kvc, const float* mask, con
                         int acc_ld, float w_host, const float* w_dev, int B, int L, int S, int H, int d, int dtype,
                         void* stream);
 
+/* mdm_attn_cross_maps_bwd -- the gradient of those maps with respect to q (attention-map guidance: a loss on the maps,
+ * Attend-and-Excite for one, moves x_t).  With dacc = d loss / d acc of one mdm_attn_cross_maps launch of weight w:
+ *   P_h        = the probabilities exactly as mdm_attn_cross_maps forms them, without a bias (the same exponent,
+ *                (s c2) rounded and then - max; a key is live where key < S and mask != 0)
+ *   delta_h[l] = sum_s P_h[l, s] dacc[b, l, s]
+ *   dS_h       = P_h o (dacc - delta_h)
+ *   dq[b, l, h d + c] = w / (H sqrt(d)) sum_s dS_h[l, s] k_c[b, s, h d + c]
+ * (w / H is applied once, to the finished sum, so dacc enters the products unscaled.)
+ * qkv [B, L, 3C] (only q is read), kvc [B, S, 2C] (only k_c is read), mask [B, S] of 0/1 floats or NULL.  dacc: fp32
+ * [B, L, dacc_ld], query-major like acc, dacc_ld >= S and % 4 == 0, 16-byte aligned; its columns [S, dacc_ld) and the
+ * entries of keys that are not live are selected away, never computed on: they may hold NaN.  dq: the compute dtype, row
+ * (b, l) at dq + b * dq_bs + l * dq_rs elements, C of them written (dq_rs >= C, dq_rs and dq_bs % 4 == 0, dq aligned to
+ * four elements): dq_rs = 3C, dq_bs = L * 3C writes straight into the q columns of a qkv-shaped gradient, and nothing
+ * outside those columns is touched.  A query with no live key gets exact zeros; a single live key gives exact zeros too.
+ * No bias: a biased map has no backward here.  Gradients to k_c are not formed.
+ * dtype: MDM_F32, MDM_BF16 (dS rounded to bf16 for the second product, as the attention backward does), or MDM_F32_SPLIT,
+ * which runs the exact-fp32 products; accumulation in fp32; d in {32, 64, 96, 128}, any L, any S >= 1, any H with
+ * B * H <= 65535.  One block per 64 queries of one (batch, head): S <= 64 is one key tile with everything in registers,
+ * beyond that two sweeps over the key tiles.  Every dq element is written once by the lane that owns it: no workspace, no
+ * atomics, deterministic, a batch row's result independent of B.  Invalid arguments: a negative status, nothing launched. */
+int mdm_attn_cross_maps_bwd(const void* qkv, const void* kvc, const float* mask, const float* dacc, int dacc_ld, float w,
+                            void* dq, size_t dq_bs, int dq_rs, int B, int L, int S, int H, int d, int dtype, void* stream);
+
 /* FreeU (Si et al., CVPR 2024) fused into the up path's skip concat: backbone h [N, H, W, C1], skip r [N, H, W, C2], NHWC,
  * of dtype MDM_F32 or MDM_BF16 (the fp32-split mode has fp32 tensors: MDM_F32), arithmetic in fp32 ->
  *   out[.., 0:C1/2]   = h[.., :C1/2] * m       m = b, or with `structure` (FreeU v2)  1 + (b - 1) hm[n, y, x],

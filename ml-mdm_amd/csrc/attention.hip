@@ -2009,3 +2009,258 @@ extern "C" int mdm_attn_cross_maps(const void* qkv, const void* kvc, const float
 #undef MDM_ATTN_CROSS_MAPS
   return -1;
 }
+
+// ---------------------------------------------------------------------------------------
+// backward of the cross-attention maps with respect to q (attention-map guidance: attend-and-excite and its kin)
+// ---------------------------------------------------------------------------------------
+// acc[b, l, s] = w / H * sum_h P_h[l, s] with P_h the masked softmax of mdm_attn_cross_maps; given dacc = d loss / d acc,
+//   delta_h[l] = sum_s P_h[l, s] dacc[l, s]      dS_h = P_h o (dacc - delta_h)      dq_h = w / (H sqrt(d)) dS_h k_c,h
+// This is attn_cross_addv_kernel with two substitutions: dacc takes the place of the bias (the same [B, L, ld] rows, the
+// same 16-byte load of a lane's four consecutive keys per score tile, issued ahead of the QK^T MFMAs, but applied AFTER the
+// softmax), and k_c takes the place of v_c in the second product (the same [S, d] rows: bf16 reads the K^T fragments out
+// of the natural key tile that the first product already staged, by the LDS transpose read, so ONE tile is staged; fp32
+// stages the transposed image beside it).  The probabilities are those of attn_cross_maps_kernel operation for operation:
+// (s c2) rounded, - m, exp2, the row sum reduced per tile, times 1 / l.  w / H is applied once, to the finished sum
+// together with 1 / sqrt(d), so dacc enters the products as it is -- small integers stay exact.  dS is rounded to bf16 for
+// the second MFMA in the bf16 mode, as the attention backward rounds its dS; fp32 keeps exact products.
+//   S <= 64 (one key tile): P, delta and dS complete in registers, delta reduced by the two shuffles of the row sum.
+//   S  > 64: sweep 0 keeps the running max, sum and sum of e dacc (rescaled by the same alpha); sweep 1 walks the tiles
+//            again, forms dS and accumulates dq.
+// dacc is SELECTED, never computed on, where the key is not live or past S: those entries may hold NaN.  A query with no
+// live key has P = 0 and gets exact zeros.  One block per 64 queries of one (batch, head), each dq element written once
+// by the lane that owns it and by nobody else: no workspace, bit-reproducible, a batch row's result independent of B.
+namespace mdm {
+
+struct AttnMapsBwdArgs {
+  const void* q; size_t q_bs; int q_rs;     // row (b, i), head h, channel c: q[b * q_bs + i * q_rs + h * d + c]
+  const void* kc; size_t c_bs; int c_rs;
+  const float* mask;                         // [B, S] or null
+  const float* dacc; int dacc_ld;            // [B, L, dacc_ld]
+  void* dq; size_t dq_bs; int dq_rs;         // addressed as q
+  float w;
+  int B, H, L, S;
+  float scale;                               // 1/sqrt(d)
+};
+
+template <typename T, int D>
+__global__ __launch_bounds__(256) void attn_cross_maps_bwd_kernel(AttnMapsBwdArgs p) {
+  using G = AttnGeom<T, D>;
+  using F = Frag<T>;
+  constexpr int KSTEPS = G::KSTEPS, DS = G::DS, DT = G::DT;
+  constexpr bool BF = sizeof(T) == 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Ks = smem;
+  [[maybe_unused]] char* Kt = smem + G::NAT_BYTES;   // fp32 only: the transposed image
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int quad = lane >> 4, l16 = lane & 15;
+  const TrOff<D> troff(quad, l16);
+  const int bx_ = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
+  const int by = bx_ / (int)gridDim.x, bx = bx_ - by * (int)gridDim.x;
+  const int b = by / p.H, h = by - b * p.H;
+  const int qi = bx * 64 + wave * 16 + l16;
+  const bool q_ok = qi < p.L;
+
+  f32x4 o[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const T* Q = reinterpret_cast<const T*>(p.q) + (size_t)b * p.q_bs + (size_t)h * D;
+  F qf[DS];
+#pragma unroll
+  for (int ks = 0; ks < DS; ++ks)
+    frag_from_global_x(qf[ks], Q + (size_t)(q_ok ? qi : 0) * p.q_rs + ks * 32 + quad * 8, q_ok);
+  const T* Kp = reinterpret_cast<const T*>(p.kc) + (size_t)b * p.c_bs + (size_t)h * D;
+  const int rs = p.c_rs, nk = p.S;
+  const float* mrow = p.mask ? p.mask + (size_t)b * p.S : nullptr;
+  const float c2 = p.scale * 1.4426950408889634f;   // scores -> base-2 exponent
+  const float* grow = p.dacc + ((size_t)b * p.L + (q_ok ? qi : 0)) * p.dacc_ld;
+
+  const bool single = nk <= 64;   // block-uniform
+  const int passes = single ? 1 : 2;
+  float m_run = -1e30f, l_run = 0.f, r_run = 0.f;   // running max, sum (both whole-row) and the lane's part of sum e dacc
+  float inv = 0.f, delta = 0.f;
+  for (int pass = 0; pass < passes; ++pass) {
+    const bool emit = single || pass == 1;   // this sweep forms dS and accumulates dq
+    for (int k0 = 0; k0 < nk; k0 += 64) {
+      __syncthreads();   // every wave is done with the tile before
+      load_nat_tile<T, D>(Ks, Kp, rs, k0, nk, tid);
+      if constexpr (!BF) {
+        if (emit) load_tr_tile<T, D>(Kt, Kp, rs, k0, nk, tid);
+      }
+      __syncthreads();
+
+      // the lane's dacc of this tile: keys key0 + [0, 4) per score tile; key0 % 4 == 0 and dacc_ld % 4 == 0 >= S keep a
+      // load that starts below S inside the row
+      f32x4 gv[4];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int key0 = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4;
+        const bool in = q_ok && key0 < nk;
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        gv[kt] = in ? *reinterpret_cast<const f32x4*>(grow + (in ? key0 : 0)) : z;
+      }
+
+      f32x4 s[4];
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int row = perm_row(kt, l16);
+        s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < DS; ++ks) {
+          F kf;
+          load_frag_x(kf, Ks + (ks / KSTEPS) * (64 * 128), row, ks % KSTEPS, quad);
+          mma16(s[kt], kf, qf[ks]);
+        }
+      }
+      // the first reads of s sit behind block-uniform branches (`full`, `pass`): fence the MFMAs from the softmax and pay
+      // the XDL write -> VALU read wait states here, as attn_cross_maps_kernel does (tools/mfma_hazard_scan.py)
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_nop 7" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      // the lane holds key positions (kt>>1)*32 + quad*8 + (kt&1)*4 + i of its query column (lane & 15)
+      {
+#pragma clang fp contract(off)
+        const bool full = (k0 + 64 <= nk) && !mrow;   // block-uniform
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            float t = s[kt][i] * c2;
+            if (!full) {
+              const int key = k0 + (kt >> 1) * 32 + quad * 8 + (kt & 1) * 4 + i;
+              bool ok = key < nk;
+              if (ok && mrow) ok = mrow[key] != 0.f;
+              t = ok ? t : -3.0e38f;
+              gv[kt][i] = ok ? gv[kt][i] : 0.f;   // selected away, NaN included
+            }
+            s[kt][i] = t;
+          }
+        if (pass == 0) {
+          float mx = -3.0e38f;
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mx = fmaxf(mx, s[kt][i]);
+          mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+          mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+          const float m_new = fmaxf(m_run, fmaxf(mx, -1e30f));   // a fully masked tile leaves m_run alone
+          const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+          m_run = m_new;
+          float ls = 0.f, rsum = 0.f;
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float e = __builtin_amdgcn_exp2f(s[kt][i] - m_new);   // masked: -3e38 - m = -3e38 -> 0
+              s[kt][i] = e; ls += e;
+              rsum += e * gv[kt][i];
+            }
+          ls += __shfl_xor(ls, 16, 64);
+          ls += __shfl_xor(ls, 32, 64);
+          l_run = l_run * alpha + ls;
+          r_run = r_run * alpha + rsum;
+          if (single) {
+            float r = r_run;
+            r += __shfl_xor(r, 16, 64);
+            r += __shfl_xor(r, 32, 64);
+            inv = l_run > 0.f ? 1.f / l_run : 0.f;   // no live key: P = 0, dq = 0
+            delta = r * inv;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) s[kt][i] = (s[kt][i] * inv) * (gv[kt][i] - delta);
+          }
+        } else {
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+              s[kt][i] = (__builtin_amdgcn_exp2f(s[kt][i] - m_run) * inv) * (gv[kt][i] - delta);
+        }
+      }
+      if (emit) {   // block-uniform
+        F pf[2];
+        frag_from_acc_x(pf[0], s[0], s[1]);
+        frag_from_acc_x(pf[1], s[2], s[3]);
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+          for (int hh = 0; hh < 2; ++hh) {
+            F kf;
+            if constexpr (BF) troff.read(kf, Ks, dt, hh);
+            else load_frag_x(kf, Kt + (hh / KSTEPS) * (D * 128), dt * 16 + l16, hh % KSTEPS, quad);
+            mma16(o[dt], kf, pf[hh]);
+          }
+      }
+    }
+    if (!single && pass == 0) {
+      float r = r_run;
+      r += __shfl_xor(r, 16, 64);
+      r += __shfl_xor(r, 32, 64);
+      inv = l_run > 0.f ? 1.f / l_run : 0.f;
+      delta = r * inv;
+    }
+  }
+  // o is read behind the block-uniform sweep loop: the same fence and wait states as above
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_nop 7" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  if (!q_ok) return;
+  // the lane's own channels dt*16 + quad*4 + [0, 4)
+  using V4 = typename std::conditional<BF, bf16x4, f32x4>::type;
+  T* O = reinterpret_cast<T*>(p.dq) + (size_t)b * p.dq_bs + (size_t)qi * p.dq_rs + (size_t)h * D + quad * 4;
+  const float fs = p.scale * (p.w / (float)p.H);
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    V4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = from_f32<T>(o[dt][i] * fs);
+    *reinterpret_cast<V4*>(O + dt * 16) = r;
+  }
+}
+
+}  // namespace mdm
+
+template <typename T, int D>
+static int attn_cross_maps_bwd_launch(const AttnMapsBwdArgs& a, hipStream_t st) {
+  using G = AttnGeom<T, D>;
+  constexpr int smem = sizeof(T) == 2 ? G::NAT_BYTES : G::NAT_BYTES + (G::NAT_BYTES > G::TR_BYTES ? G::NAT_BYTES : G::TR_BYTES);
+  ensure_dynamic_lds(attn_cross_maps_bwd_kernel<T, D>, smem);
+  dim3 grid((a.L + 63) / 64, a.B * a.H);   // 16 queries per wave
+  hipLaunchKernelGGL((attn_cross_maps_bwd_kernel<T, D>), grid, dim3(256), smem, st, a);
+  MDM_LAUNCH_STATUS();
+}
+
+// qkv [B, L, 3C] (only q is read), kvc [B, S, 2C] (only k_c), mask [B, S] or null, dacc [B, L, dacc_ld] fp32, dq: row
+// (b, l) at dq + b * dq_bs + l * dq_rs elements of the compute dtype, C of them written (include/mdm_hip_ext.h).
+extern "C" int mdm_attn_cross_maps_bwd(const void* qkv, const void* kvc, const float* mask, const float* dacc, int dacc_ld,
+                                       float w, void* dq, size_t dq_bs, int dq_rs, int B, int L, int S, int H, int d,
+                                       int dtype, void* stream) {
+  MDM_CHECK_ARG(qkv && kvc && dacc && dq);
+  MDM_CHECK_ARG(dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_F32_SPLIT);
+  if (dtype == DT_F32_SPLIT) dtype = DT_F32;   // exact fp32 products, as mdm_attn_cross_maps
+  MDM_CHECK_ARG(B > 0 && L > 0 && S > 0 && H > 0);
+  MDM_CHECK_ARG(d == 32 || d == 64 || d == 96 || d == 128);
+  MDM_CHECK_ARG(dacc_ld >= S && dacc_ld % 4 == 0 && (uintptr_t)dacc % 16 == 0);   // the lanes' 16-byte loads
+  const int C = H * d;
+  const size_t es = dtype == DT_F32 ? 4 : 2;
+  MDM_CHECK_ARG(dq_rs >= C && dq_rs % 4 == 0 && dq_bs % 4 == 0 && (uintptr_t)dq % (4 * es) == 0);   // four channels per store
+  MDM_CHECK_ARG(B == 1 || dq_bs >= (size_t)(L - 1) * (size_t)dq_rs + (size_t)C);                  // batch rows do not overlap
+  MDM_CHECK_ARG((size_t)B * H <= 65535);                                                           // grid y
+  AttnMapsBwdArgs a = {};
+  a.q = qkv; a.q_bs = (size_t)L * 3 * C; a.q_rs = 3 * C;
+  a.kc = kvc; a.c_bs = (size_t)S * 2 * C; a.c_rs = 2 * C;
+  a.mask = mask; a.dacc = dacc; a.dacc_ld = dacc_ld;
+  a.dq = dq; a.dq_bs = dq_bs; a.dq_rs = dq_rs; a.w = w;
+  a.B = B; a.H = H; a.L = L; a.S = S; a.scale = 1.0f / sqrtf((float)d);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define MDM_ATTN_CROSS_MAPS_BWD(DD) \
+  case DD: return dtype == DT_F32 ? attn_cross_maps_bwd_launch<float, DD>(a, st) : attn_cross_maps_bwd_launch<bf16, DD>(a, st);
+  switch (d) {
+    MDM_ATTN_CROSS_MAPS_BWD(32) MDM_ATTN_CROSS_MAPS_BWD(64) MDM_ATTN_CROSS_MAPS_BWD(96) MDM_ATTN_CROSS_MAPS_BWD(128)
+    default: MDM_CHECK_ARG(!"unsupported head dim");
+  }
+#undef MDM_ATTN_CROSS_MAPS_BWD
+  return -1;
+}

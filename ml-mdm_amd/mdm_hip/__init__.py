@@ -21,7 +21,8 @@ Layout of the package
   regions.py      regional prompts and token weights, a bias on the text cross-attention logits: RegionPrompts / concat /
                   applied (the samplers' regions / region_layers)
   attn_maps.py    cross-attention maps, the text term's probabilities recorded per token: AttnMaps / record / applied (the
-                  samplers' attn_maps)
+                  samplers' attn_maps); GradRows / cross_probs: the maps on the autograd tape, for the samplers' map_guide
+                  (samplers.MapGuide, samplers.AttendExcite: attention-map guidance, Attend-and-Excite)
   freeu.py        FreeU on the up path's skip concat: FreeU / select / applied (the samplers' freeu)
   guidance.py     projected and rescaled classifier-free guidance (APG, CFG rescale, guidance interval): CFG / cfg_combine
                   (the samplers' cfg)
@@ -51,7 +52,7 @@ from .unet import ResNetConfig, UNet, UNetConfig  # noqa: F401,E402
 from . import lora  # noqa: F401,E402
 from . import fp8  # noqa: F401,E402
 from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
-from .samplers import LossGuide, SASolver  # noqa: F401,E402
+from .samplers import AttendExcite, LossGuide, MapGuide, SASolver  # noqa: F401,E402
 from . import pag  # noqa: F401,E402
 from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
@@ -94,5 +95,7 @@ __all__ = [
     "enable_activation_recompute",
     "activation_recompute_enabled",
     "LossGuide",
+    "MapGuide",
+    "AttendExcite",
     "SASolver",
 ]

@@ -14,6 +14,8 @@ computed exactly as before, so the images do not change by a bit; with ``regions
 ``record``     the switch for one forward outside the samplers (``with record(vision_model, maps): model(...)``).
 ``applied``    the switch a sampler holds around its denoiser call, in the style of ``regions.applied``.
 ``cross_maps`` the kernel restated in torch ops, for CPU tensors.
+``cross_probs`` the same probabilities as a DIFFERENTIABLE function of qkv (``ops.attn_cross_probs`` in torch ops).
+``GradRows``   the recorder of attention-map guidance (``samplers.MapGuide``): it keeps the maps on the autograd tape.
 The samplers do the rest: ``Sampler.sample(..., attn_maps=maps)``, ``GraphedSampler.sample`` alike -- the conditional
 block of [uncond | cond | perturbed] is what is recorded.
 """
@@ -59,6 +61,30 @@ def cross_maps(qkv, kvc, mask, heads, acc, bias=None, weight=1.0, gate=None, row
         p = torch.where(l > 0, e / l.clamp(min=1e-38), torch.zeros_like(e))
         acc[:, :, :S] += (w / heads) * p.sum(dim=1)
     return acc
+
+
+def cross_probs(qkv, kvc, mask, heads, row0=0, rows=None):
+    """``ops.attn_cross_probs`` in torch ops (CPU tensors, any float dtype; arithmetic in fp32) -> fp32 [rows, L, ld], ld = S
+    rounded up to 4 with zero pad columns: ``cross_maps`` without ``no_grad`` and without an accumulator, differentiable in
+    ``qkv`` by torch autograd; ``kvc`` and ``mask`` are constants."""
+    N, S = qkv.shape[0], kvc.shape[1]
+    C = qkv.shape[-1] // 3
+    L = qkv.numel() // max(N * 3 * C, 1)
+    d = C // heads
+    rows = N - row0 if rows is None else int(rows)
+    sl = slice(row0, row0 + rows)
+    q = qkv.reshape(N, L, 3 * C)[sl, :, :C].float().reshape(rows, L, heads, d)
+    k = kvc.detach()[sl, :, :C].float().reshape(rows, S, heads, d)
+    logits = torch.einsum("blhd,bshd->bhls", q, k) / math.sqrt(d)
+    live = torch.ones(rows, 1, L, S, dtype=torch.bool, device=q.device)
+    if mask is not None:
+        live = live & (mask.detach()[sl].float() != 0)[:, None, None, :]
+    logits = logits.masked_fill(~live, float("-inf"))
+    m = logits.detach().amax(dim=-1, keepdim=True).clamp(min=-1e30)
+    e = torch.exp(logits - m)
+    l = e.sum(dim=-1, keepdim=True)
+    p = torch.where(l > 0, e / l.clamp(min=1e-38), torch.zeros_like(e))
+    return F.pad(p.mean(dim=1), (0, _ld(S) - S))
 
 
 def layer_names(vision_model, layers="all"):
@@ -234,10 +260,53 @@ class StaticRows:
             maps.counted(h, w, steps * self.per_step.get((h, w), 0))
 
 
+class GradRows:
+    """``GradRows(S, row0, rows, total)``: the recorder of attention-map guidance -- rows [row0, row0 + rows) of a model
+    batch of ``total``, over ``S`` tokens.  ``record`` calls the DIFFERENTIABLE op (``ops.attn_cross_probs``; CPU tensors:
+    ``cross_probs``) and keeps, per attention resolution, the running sum of what it returned and the layer count, so
+    ``maps()`` is attached to the autograd graph of the forward that recorded: a loss on it reaches the model's input.
+    One handle serves one forward.  A bias (``regions=``) is refused: the biased map has no backward."""
+
+    def __init__(self, S, row0, rows, total):
+        self.S, self.row0, self.rows, self.total = int(S), int(row0), int(rows), int(total)
+        if self.S < 1 or self.rows < 1 or self.row0 < 0 or self.row0 + self.rows > self.total:
+            raise ValueError("GradRows: S = %d tokens, rows [%d, %d) of a batch of %d"
+                             % (self.S, self.row0, self.row0 + self.rows, self.total))
+        self.ld = _ld(self.S)
+        self._sum = {}     # (h, w) -> fp32 [rows, h * w, ld], on the tape
+        self._count = {}   # (h, w) -> layers recorded
+
+    def record(self, qkv, kvc, mask, heads, bias, N, h, w):
+        if bias is not None:
+            raise NotImplementedError("GradRows: a bias on the text logits (regions=): the biased cross-attention map has no "
+                                      "backward (mdm_attn_cross_maps_bwd takes none)")
+        if N != self.total:
+            raise _mixed("GradRows", N, self.rows, self.total)
+        _check_tokens("GradRows", self.S, kvc)
+        fn = ops.attn_cross_probs if qkv.is_cuda else cross_probs
+        # the text keys are constants of the guidance: trainable adapters of kv_cond (LoRA) get no gradient from the maps
+        p = fn(qkv, kvc.detach(), mask, heads, row0=self.row0, rows=self.rows)
+        key = (int(h), int(w))
+        self._sum[key] = p if key not in self._sum else self._sum[key] + p
+        self._count[key] = self._count.get(key, 0) + 1
+
+    def counts(self):
+        """{(h, w): layers recorded}"""
+        return dict(self._count)
+
+    def maps(self):
+        """-> {(h, w): fp32 [rows, S, h, w]}: the mean over the recording layers and the heads, on the autograd tape"""
+        out = {}
+        for (h, w), t in self._sum.items():
+            m = t[:, :, :self.S] / self._count[(h, w)]
+            out[(h, w)] = m.transpose(1, 2).reshape(self.rows, self.S, h, w)
+        return out
+
+
 class applied(switched):
     """``with applied(vision_model, handle, layers="all"):`` -- inside, the selected ``SelfAttention`` layers that have text
-    keys call ``handle.record(...)`` after their attention (``handle``: a ``BatchRows`` / ``StaticRows``, or anything with
-    that method); on exit (also by an exception) every layer has what it had before."""
+    keys call ``handle.record(...)`` after their attention (``handle``: a ``BatchRows`` / ``StaticRows`` / ``GradRows``, or
+    anything with that method); on exit (also by an exception) every layer has what it had before."""
 
     def __init__(self, vision_model, handle, layers="all"):
         if not callable(getattr(handle, "record", None)):
@@ -253,4 +322,4 @@ def record(vision_model, maps, layers=None):
     return applied(vision_model, BatchRows(maps, 0, maps.rows), maps.layers if layers is None else layers)
 
 
-__all__ = ["AttnMaps", "BatchRows", "StaticRows", "applied", "record", "cross_maps", "layer_names"]
+__all__ = ["AttnMaps", "BatchRows", "StaticRows", "GradRows", "applied", "record", "cross_maps", "cross_probs", "layer_names"]

@@ -289,7 +289,7 @@ class GraphedSampler:
                start_step=None, **options):
         """``options``: the keywords of ``SampleOptions`` (what each does is said there), with these graph-specific facts;
         the key parts are ``SampleOptions.graph_key``, and the body runs the model under ``SampleOptions.switches``.
-        ``guide``: refused -- neither the user's function nor the autograd pass of every step can be captured.
+        ``guide``, ``map_guide``: refused -- neither the user's function nor the autograd pass of a guided step can be captured.
         ``cfg``: the graph key holds ("cfg", eta, norm_threshold, momentum, rescale, interval): other values capture anew.
         Each entry owns the momentum buffers and the two gate tables; every call rewrites the tables for the rows it
         replays, so a late start and a second call begin without history, as the eager sampler does.
@@ -321,6 +321,10 @@ class GraphedSampler:
             raise NotImplementedError("GraphedSampler does not take guide=: loss-guided sampling calls an arbitrary user "
                                       "function and an autograd pass through the denoiser every step, and neither can be "
                                       "captured in a hipGraph; use the eager Sampler.sample(..., guide=...)")
+        if opts.map_guide is not None:
+            raise NotImplementedError("GraphedSampler does not take map_guide=: attention-map guidance calls an arbitrary "
+                                      "user function and an autograd pass through the denoiser in every guided step, and "
+                                      "neither can be captured in a hipGraph; use the eager Sampler.sample(..., map_guide=...)")
         rule = _checked_rule(solver, ddim_eta, opts.check(), known_images, resample)
         cfg = opts.cfg_at(guidance_scale)
         if known_mask is not None and known_images is None:

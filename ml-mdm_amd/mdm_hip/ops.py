@@ -2274,6 +2274,92 @@ def attn_cross_maps(qkv, kvc, mask, heads, acc, bias=None, weight=1.0, gate=None
     return acc
 
 
+def _cross_probs_check(what, qkv, kvc, mask, heads, row0, rows):
+    """the operands of mdm_attn_cross_maps / mdm_attn_cross_maps_bwd as ``attn_cross_probs`` takes them -> (row0, rows)"""
+    _require_gpu(qkv)
+    if kvc is None:
+        raise _lib.MdmHipError("%s: no text keys (kvc is None) -- there is no cross-attention to differentiate" % what)
+    if torch.is_grad_enabled() and kvc.requires_grad:
+        raise _lib.MdmHipError("%s: kvc requires grad, and mdm_attn_cross_maps_bwd forms the gradient of q only -- gradients "
+                               "to the text keys are not implemented: detach kvc, or freeze what makes it" % what)
+    if qkv.dim() < 3 or qkv.shape[-1] % 3 or kvc.dim() != 3 or kvc.shape[0] != qkv.shape[0] or \
+            2 * (qkv.shape[-1] // 3) != kvc.shape[-1] or kvc.dtype != qkv.dtype or kvc.device != qkv.device:
+        raise _lib.MdmHipError("%s: qkv %s %s and kvc %s %s (wanted [N, L, 3C] and [N, S, 2C] of one dtype on one device)"
+                               % (what, tuple(qkv.shape), qkv.dtype, tuple(kvc.shape), kvc.dtype))
+    N, C = qkv.shape[0], qkv.shape[-1] // 3
+    if heads < 1 or C % heads:
+        raise _lib.MdmHipError("%s: %d heads for C = %d" % (what, heads, C))
+    if mask is not None and (mask.numel() != N * kvc.shape[1] or mask.shape[0] != N or mask.device != qkv.device):
+        raise _lib.MdmHipError("%s: mask %s on %s for N = %d, S = %d" % (what, tuple(mask.shape), mask.device, N, kvc.shape[1]))
+    row0 = int(row0)
+    rows = N - row0 if rows is None else int(rows)
+    if not (0 <= row0 and 0 < rows and row0 + rows <= N):
+        raise _lib.MdmHipError("%s: rows [%d, %d) of a batch of %d" % (what, row0, row0 + rows, N))
+    return row0, rows
+
+
+def attn_cross_maps_bwd(qkv, kvc, mask, heads, dacc, dqkv, weight=1.0, row0=0, rows=None):
+    """The q columns of the batch rows [row0, row0 + rows) of ``dqkv`` (shaped and typed like ``qkv`` [N, L, 3C],
+    contiguous) <- the gradient of ``weight`` x the head-mean text probabilities of those rows with respect to q, given
+    ``dacc`` fp32 [rows, L, ld] (ld >= S, ld % 4 == 0; the columns [S, ld) and the entries of masked keys may hold
+    anything): include/mdm_hip_ext.h mdm_attn_cross_maps_bwd.  Nothing else of ``dqkv`` is touched.  -> dqkv"""
+    row0, rows = _cross_probs_check("attn_cross_maps_bwd", qkv, kvc, mask, heads, row0, rows)
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
+    N, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    if (dacc.dim() != 3 or tuple(dacc.shape[:2]) != (rows, L) or dacc.shape[2] < S or dacc.shape[2] % 4
+            or not dacc.is_contiguous() or dacc.dtype != torch.float32 or dacc.device != qkv.device):
+        raise _lib.MdmHipError("attn_cross_maps_bwd: dacc %s %s for rows = %d, L = %d, S = %d (wanted a contiguous fp32 "
+                               "[rows, L, ld], ld >= S, ld %% 4 == 0)" % (tuple(dacc.shape), dacc.dtype, rows, L, S))
+    if (dqkv.numel() != qkv.numel() or dqkv.shape[0] != N or dqkv.shape[-1] != 3 * C or dqkv.dtype != qkv.dtype
+            or not dqkv.is_contiguous() or dqkv.device != qkv.device):
+        raise _lib.MdmHipError("attn_cross_maps_bwd: dqkv %s %s (wanted a contiguous %s %s)"
+                               % (tuple(dqkv.shape), dqkv.dtype, tuple(qkv.shape), qkv.dtype))
+    m32 = _c(mask.detach().float()) if mask is not None else None
+    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
+    flops = (4.0 if S <= 64 else 6.0) * rows * heads * L * S * d   # QK^T per sweep (one, or two beyond a key tile) + dS K
+    _prof_wrap("attn_cross_maps_bwd_kernel<d=%d> L=%d" % (d, L), flops, lambda: _lib.check(
+        _lib.lib().mdm_attn_cross_maps_bwd(off(qkv), off(kvc), off(m32), _p(dacc.detach()), dacc.shape[-1], float(weight),
+                                           off(dqkv), L * 3 * C, 3 * C, rows, L, S, heads, d, _dt_mm(qkv), _stream()),
+        "mdm_attn_cross_maps_bwd",
+    ), kind="attn")
+    return dqkv
+
+
+class AttnCrossProbsFn(torch.autograd.Function):
+    """the head-mean text probabilities of a row range, differentiable in qkv: mdm_attn_cross_maps onto zeros forward,
+    mdm_attn_cross_maps_bwd into the q columns of a zero qkv-shaped gradient backward; kvc and the mask are constants"""
+
+    @staticmethod
+    def forward(ctx, qkv, kvc, mask, heads, row0, rows):
+        qd, kd = _c(qkv.detach()), _c(kvc.detach())
+        _, _, L, S, _ = _attn_dims(qd, kd, heads)
+        acc = torch.zeros(rows, L, (S + 3) // 4 * 4, dtype=torch.float32, device=qd.device)
+        attn_cross_maps(qd, kd, mask, heads, acc, row0=row0, rows=rows)
+        ctx.save_for_backward(qd, kd, mask)
+        ctx.geom = (heads, row0, rows)
+        return acc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dacc):
+        qd, kd, mask = ctx.saved_tensors
+        heads, row0, rows = ctx.geom
+        dqkv = torch.zeros_like(qd)
+        attn_cross_maps_bwd(qd, kd, mask, heads, _c(dacc.float()), dqkv, row0=row0, rows=rows)
+        return dqkv, None, None, None, None, None
+
+
+def attn_cross_probs(qkv, kvc, mask, heads, row0=0, rows=None):
+    """-> fp32 [rows, L, ld], ld = S rounded up to 4 with zero pad columns: the probabilities of the text cross-attention,
+    mean over heads, of the batch rows [row0, row0 + rows) of ``qkv`` [N, L, 3C] / ``kvc`` [N, S, 2C] / ``mask`` [N, S] --
+    bit for bit what ``attn_cross_maps`` adds onto zeros -- and DIFFERENTIABLE in ``qkv``: the backward fills the q columns
+    of those rows of a zero qkv-shaped gradient (include/mdm_hip_ext.h mdm_attn_cross_maps_bwd).  ``kvc`` and ``mask`` are
+    constants: a ``kvc`` that requires grad is refused under grad mode.  No bias: a biased map has no backward.  CPU
+    tensors: ``attn_maps.cross_probs``."""
+    row0, rows = _cross_probs_check("attn_cross_probs", qkv, kvc, mask, heads, row0, rows)
+    return AttnCrossProbsFn.apply(qkv, kvc.detach(), mask, heads, row0, rows)
+
+
 # --------------------------------------------------------------------------------------
 # streaming helpers
 # --------------------------------------------------------------------------------------

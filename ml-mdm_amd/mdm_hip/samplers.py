@@ -324,6 +324,10 @@ class SASolver(StepRule):
 
     def check(self, ddim_eta, opts, known_images, resample):
         StepRule.check(self, ddim_eta, opts, known_images, resample)
+        if opts.map_guide is not None:
+            raise NotImplementedError("map_guide= together with an SA solver: a correction of x_t between the predictor's "
+                                      "launch and the corrector's, which redoes that step from the history, is not "
+                                      "implemented -- as for guide=")
         if opts.guide is not None:
             raise NotImplementedError("guide= together with an SA solver: the guide's correction of x_s between the "
                                       "predictor and the corrector that redoes the step is not implemented")
@@ -683,6 +687,138 @@ class LossGuide:
         return torch.where(loss > 0, z, torch.zeros_like(z))
 
 
+class MapGuide:
+    """Attention-map guidance: ``sample(..., map_guide=MapGuide(fn, scale, layers, interval, iterations))`` moves x_t down the
+    gradient of a loss on the text cross-attention maps before the reverse step (Attend-and-Excite, Chefer et al. 2023;
+    layout guidance and self-guidance are the same mechanism with another ``fn``).
+
+    ``fn(maps) -> loss [B]``: any differentiable torch function, one NON-NEGATIVE scalar per image, of what
+    ``attn_maps.GradRows.maps()`` returns for the B images: {(h, w): fp32 [B, S, h, w]}, the text term's probabilities, mean
+    over the heads and over the recording layers of that resolution (``AttendExcite`` is a ready-made one).
+    ``scale``: the step size, a float or a callable (time_step, num_diffusion_steps) -> float.
+    ``layers``: the vocabulary of ``pag.select``; the layers with text keys among them record.
+    ``interval = (lo, hi)`` in fractions of ``num_diffusion_steps``, the convention of ``AttnMaps.interval``: a step is
+    guided where lo <= t / T <= hi for the time t it starts from; None: every step.
+    ``iterations``: gradient sub-steps per guided step -- a fixed count, nothing is read back from the device.
+
+    Per guided step, ``iterations`` times, before the step's own denoiser call: every scale's x_t becomes a leaf; the model
+    runs once with grad enabled and frozen parameters on the B CONDITIONAL rows only (the conditional half of
+    ``lm_outputs`` / ``lm_mask``), at the time the step uses, with only the recorder switch on (``ops.attn_cross_probs``,
+    whose backward is mdm_attn_cross_maps_bwd: no PAG, regions or FreeU switch, their kernels have no backward);
+    loss = fn(maps); one ``autograd.grad`` of loss.sum() to the leaves; x_t <- x_t - scale grad for every scale that got a
+    gradient (GPU tensors: ``ops.guide_apply``).  A sample whose loss is exactly 0 keeps its bits.  Then the step runs
+    unchanged, with all its options, on the moved x_t; what the model returned in the guidance pass is discarded, and the
+    pass does not record into ``attn_maps=``.  The MXFP8 layers are inference-only and raise; ``GraphedSampler`` refuses."""
+
+    def __init__(self, fn, scale, layers="all", interval=(0.5, 1.0), iterations=1):
+        if not callable(fn):
+            raise TypeError("MapGuide: fn must be callable, {(h, w): maps [B, S, h, w]} -> loss [B] (got %r)" % (type(fn).__name__,))
+        if not callable(scale):
+            try:
+                scale = float(scale)
+            except (TypeError, ValueError):
+                raise TypeError("MapGuide: scale = %r (wanted a float, or a callable (time_step, num_diffusion_steps) -> float)"
+                                % (scale,))
+            if not math.isfinite(scale):
+                raise ValueError("MapGuide: scale = %r (wanted a finite step size)" % (scale,))
+        if interval is not None:
+            try:
+                lo, hi = interval
+                interval = (float(lo), float(hi))
+            except (TypeError, ValueError):
+                raise ValueError("MapGuide: interval = %r (wanted (lo, hi) in fractions of the schedule, or None)" % (interval,))
+            if not (math.isfinite(interval[0]) and math.isfinite(interval[1]) and interval[0] <= interval[1]):
+                raise ValueError("MapGuide: interval = %r (wanted finite lo <= hi)" % (interval,))
+        if not (callable(layers) or isinstance(layers, (str, list, tuple, set, frozenset))):
+            raise ValueError("MapGuide: layers = %r (wanted a named set, a list of module names, or a predicate)" % (layers,))
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+            raise ValueError("MapGuide: iterations = %r (wanted an int >= 1: a fixed count of gradient sub-steps)" % (iterations,))
+        self.fn, self.scale, self.layers, self.interval, self.iterations = fn, scale, layers, interval, iterations
+
+    def on(self, time_step, num_diffusion_steps):
+        """is the step that starts from ``time_step`` guided?"""
+        if self.interval is None:
+            return True
+        return self.interval[0] <= float(time_step) / float(num_diffusion_steps) <= self.interval[1]
+
+    def scale_at(self, time_step, num_diffusion_steps):
+        """the step size of the step that starts from ``time_step``, a host float"""
+        return float(self.scale(int(time_step), int(num_diffusion_steps))) if callable(self.scale) else self.scale
+
+    def loss(self, maps, B):
+        """fn(maps), checked -> loss [B], attached to the tape"""
+        loss = self.fn(maps)
+        if not torch.is_tensor(loss) or tuple(loss.shape) != (B,):
+            raise ValueError("MapGuide: fn must return one loss per image, shape (%d,) (got %s)"
+                             % (B, tuple(loss.shape) if torch.is_tensor(loss) else type(loss).__name__))
+        if not loss.requires_grad:
+            raise ValueError("MapGuide: the loss does not depend on the maps (nothing to differentiate)")
+        return loss
+
+
+class AttendExcite:
+    """The loss of Attend-and-Excite (Chefer et al., SIGGRAPH 2023) as a ``MapGuide`` function, in plain torch: every
+    subject token must attend strongly somewhere,
+
+        loss_b = max over s in tokens_b of (1 - max over (y, x) of M~[b, s, y, x]).
+
+    ``tokens``: one list of token indices for every image, or one list per image.  ``resolution = (h, w)``: which maps,
+    M = maps[resolution]; None takes the single recorded resolution (several: ValueError).  ``exclude``: token indices
+    (start / end / padding markers) removed from M, the rest renormalised per pixel to sum 1.  ``smooth``: M~ = M under a
+    3 x 3 Gaussian of sigma 0.5 with reflect padding, as in the paper; else M~ = M."""
+
+    def __init__(self, tokens, resolution=None, smooth=True, exclude=()):
+        tokens = list(tokens)
+        if not tokens:
+            raise ValueError("AttendExcite: no tokens")
+        per_row = all(isinstance(t, (list, tuple)) for t in tokens)
+        rows = [list(t) for t in tokens] if per_row else [tokens]
+        for r in rows:
+            if not r or any(isinstance(t, bool) or not isinstance(t, int) or t < 0 for t in r):
+                raise ValueError("AttendExcite: tokens = %r (wanted a non-empty list of token indices >= 0, or one per image)"
+                                 % (tokens,))
+        self.tokens, self.per_row = rows, per_row
+        self.resolution = None if resolution is None else (int(resolution[0]), int(resolution[1]))
+        self.smooth = bool(smooth)
+        self.exclude = tuple(int(t) for t in exclude)
+        if any(t in self.exclude for r in rows for t in r):
+            raise ValueError("AttendExcite: a subject token is among the excluded ones (%r)" % (self.exclude,))
+
+    @staticmethod
+    def kernel(dtype, device):
+        """the 3 x 3 Gaussian of sigma 0.5, normalised"""
+        g = torch.exp(-torch.arange(-1, 2, dtype=torch.float64) ** 2 / (2 * 0.5 ** 2))
+        k = torch.outer(g, g)
+        return (k / k.sum()).to(dtype=dtype, device=device)
+
+    def __call__(self, maps):
+        if self.resolution is None:
+            if len(maps) != 1:
+                raise ValueError("AttendExcite: maps of the resolutions %s: say which with resolution=" % (sorted(maps),))
+            M = next(iter(maps.values()))
+        else:
+            if self.resolution not in maps:
+                raise ValueError("AttendExcite: no maps of resolution %s (recorded: %s)" % (self.resolution, sorted(maps)))
+            M = maps[self.resolution]
+        B, S, h, w = M.shape
+        if self.per_row and len(self.tokens) != B:
+            raise ValueError("AttendExcite: token lists for %d images, maps of %d" % (len(self.tokens), B))
+        if max(max(r) for r in self.tokens) >= S:
+            raise ValueError("AttendExcite: token %d of %d" % (max(max(r) for r in self.tokens), S))
+        if self.exclude:
+            keep = torch.ones(S, dtype=torch.bool, device=M.device)
+            keep[list(self.exclude)] = False
+            M = M * keep.to(M.dtype)[None, :, None, None]
+            M = M / M.sum(dim=1, keepdim=True).clamp(min=1e-20)
+        if self.smooth:
+            k = self.kernel(M.dtype, M.device)
+            M = F.conv2d(F.pad(M.reshape(B * S, 1, h, w), (1, 1, 1, 1), mode="reflect" if min(h, w) > 1 else "replicate"),
+                         k[None, None]).reshape(B, S, h, w)
+        peak = M.amax(dim=(2, 3))                                   # [B, S]
+        rows = self.tokens if self.per_row else self.tokens * B
+        return torch.stack([(1 - peak[b, r]).max() for b, r in enumerate(rows)])
+
+
 @dataclass(frozen=True)
 class SampleOptions:
     """The sampling options beyond the reference, as the keywords of ``Sampler.sample``, ``get_xt_minus_1``,
@@ -734,13 +870,18 @@ class SampleOptions:
     and recorded step; CPU tensors: ``attn_maps.cross_maps``) for the conditional block of the model batch, in the steps
     of ``maps.interval``.  The layers' outputs are computed as before: the images do not change by a bit.  Reads detached
     values, so it composes with ``guide`` too.
+    ``map_guide = MapGuide(fn, scale, layers, interval, iterations)``: attention-map guidance (``MapGuide``; ``AttendExcite``
+    is the ready-made ``fn``) -- in the steps of its interval, x_t is first moved down the gradient of a loss on the text
+    cross-attention maps of the conditional rows (one more forward + backward over B rows per iteration, with only the
+    recorder switch on), then the step runs unchanged with every other option on the moved x_t.  Eager samplers only.
 
     The model switches (perturbed rows, region bias, FreeU, the map recorder) are held around each step's denoiser call only
     (``switches``), never across a ``yield``, and a switch that is off is not even resolved.  What excludes what
     (``check``: NotImplementedError): ``guide`` with each of the other four, because their kernels have no backward or, for
     ``cfg``, no Jacobian; ``pag_scale`` with ``cfg``; ``guide`` with ``tiles`` (no backward); ``regions`` with ``tiles``
     (the bias is laid out over the whole canvas); and ``attn_maps`` with ``tiles`` (a window's queries are not the
-    canvas's).  Everything else composes."""
+    canvas's); ``map_guide`` with ``guide`` (two corrections of one step), with ``tiles`` and with an SA solver.  Everything
+    else composes."""
 
     guide: object = None
     pag_scale: float = 0.0
@@ -751,6 +892,7 @@ class SampleOptions:
     cfg: object = None
     tiles: object = None
     attn_maps: object = None
+    map_guide: object = None
 
     REFUSED = {
         ("guide", "pag"): "guide= together with pag_scale != 0: the perturbed rows' attention kernel (mdm_attn_cross_addv) "
@@ -770,6 +912,10 @@ class SampleOptions:
                               "and cropping it per window is not implemented",
         ("attn_maps", "tiles"): "attn_maps= together with tiles=: a window's queries are not the canvas's, and merging the "
                                 "maps of the windows is not implemented",
+        ("map_guide", "guide"): "map_guide= together with guide=: two corrections of one step -- the map loss moves x_t before "
+                                "the step, the guide's loss moves x_s after it -- have not been tested together",
+        ("map_guide", "tiles"): "map_guide= together with tiles=: a window's queries are not the canvas's, and merging the "
+                                "maps of the windows is not implemented",
     }
 
     @classmethod
@@ -782,7 +928,7 @@ class SampleOptions:
         tiles"""
         on = dict(guide=self.guide is not None, pag=self.pag_scale != 0, regions=self.regions is not None,
                   freeu=self.freeu is not None, cfg=self.cfg is not None, tiles=self.tiles is not None,
-                  attn_maps=self.attn_maps is not None)
+                  attn_maps=self.attn_maps is not None, map_guide=self.map_guide is not None)
 
         def refuse(a, b):
             if on[a] and on[b]:
@@ -812,6 +958,10 @@ class SampleOptions:
         if on["attn_maps"] and not isinstance(self.attn_maps, _attn_maps.AttnMaps):
             raise ValueError("attn_maps = %r (wanted a mdm_hip.AttnMaps)" % (self.attn_maps,))
         refuse("attn_maps", "tiles")
+        if on["map_guide"] and not isinstance(self.map_guide, MapGuide):
+            raise TypeError("map_guide must be an mdm_hip.MapGuide (got %r)" % (type(self.map_guide).__name__,))
+        refuse("map_guide", "guide")
+        refuse("map_guide", "tiles")
         return self
 
     def blocks(self, guidance_scale):
@@ -1259,6 +1409,43 @@ class Sampler(nn.Module):
                 out[i] = x - _b(zeta).to(x.dtype) * grad
         return out
 
+    # ---- attention-map guidance (MapGuide; not in the reference) ----------------------------------------
+    def _map_guide_pass(self, mg, model, time_step, x_t, t, lm_outputs, lm_mask, micros, guidance_scale):
+        """The correction of x_t in front of one guided step (``MapGuide``): ``mg.iterations`` times, the model on leaf x_t
+        (the list of scales, hi -> lo) with grad enabled and frozen parameters -- the B conditional rows with their text, at
+        the time the step uses, under the recorder switch alone --, the loss of the recorded maps, one ``autograd.grad`` to
+        the leaves, x_t <- x_t - scale grad per scale that got one.  -> the moved list (new tensors: the caller's stay)"""
+        B = x_t[0].shape[0]
+        if guidance_scale != 1:   # [uncond | cond] -> cond
+            rows = lm_outputs.shape[0]
+            assert rows == 2 * B
+            half = lambda v: v[-B:] if (torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == rows) else v
+            lm_outputs, lm_mask, micros = half(lm_outputs), half(lm_mask), {k: half(v) for k, v in micros.items()}
+        vision_model = getattr(model, "vision_model", model)
+        names = _attn_maps.layer_names(vision_model, mg.layers)
+        scale = mg.scale_at(time_step, self.n_steps)
+        xs = list(x_t)
+        for _ in range(mg.iterations):
+            x_in = [x.detach().clone().requires_grad_(True) for x in xs]
+            handle = _attn_maps.GradRows(lm_outputs.shape[1], 0, B, B)
+            with torch.enable_grad(), _frozen_parameters(model), _attn_maps.applied(vision_model, handle, names):
+                self._call_model(model, x_in, t - 1, lm_outputs, lm_mask, micros)   # model sees t-1 (:415); outputs discarded
+                if not handle.counts():
+                    raise ValueError("MapGuide: no layer recorded (the model was run without text keys)")
+                loss = mg.loss(handle.maps(), B)
+                grads = torch.autograd.grad(loss.sum(), x_in, allow_unused=True)
+            zeta = torch.where(loss.detach() > 0, torch.full_like(loss.detach(), scale), torch.zeros_like(loss.detach())).float()
+            for i, g in enumerate(grads):
+                if g is None:
+                    continue
+                x = x_in[i].detach()
+                if x.is_cuda:
+                    xs[i] = ops.guide_apply(x, zeta, direct=g.float())
+                else:
+                    z = _b(zeta).to(x.dtype)
+                    xs[i] = torch.where(z != 0, x - z * g, x)
+        return xs
+
     def forward_model(self, model, x_t, t, lm_outputs, lm_mask, micros={}, guidance_scale=1):
         """classifier-free guidance doubles the batch: [uncond | cond] (:435-459)."""
         (pc,), (pu,), extras, _ = self._forward_model_raw(model, [x_t], t, lm_outputs, lm_mask, micros, guidance_scale)
@@ -1366,6 +1553,8 @@ class Sampler(nn.Module):
         image_scales = self._scale_info(model)[1]
         st = {} if solver_state is None else solver_state
         g_hist, state = rule.load(self, st, x_t, g_t)
+        if opts.map_guide is not None and opts.map_guide.on(time_step, self.n_steps):   # moves x_t; the step below is unchanged
+            x_t = self._map_guide_pass(opts.map_guide, model, time_step, x_t, t, lm_outputs, lm_mask, micros, guidance_scale)
         cfg_kw = {} if opts.cfg_at(guidance_scale) is None else dict(cfg_state=st, cfg_on=opts.cfg.on(time_step, self.n_steps))
         guide = opts.guide
         x_in, grad, no_grad, thr = x_t, _UNCHANGED, _UNCHANGED, None
