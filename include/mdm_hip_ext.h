@@ -250,6 +250,35 @@ int mdm_sampler_step_sa(const float* x_t, const float* pred, const float* pred_u
                         float* h1, float* psum, float* x0_out, float* x_last_out, int B, size_t chw, int pred_type, int clip,
                         float image_scale, int max_predictor, int max_corrector, void* stream);
 
+/* Image inversion: taking a GIVEN image back to the noise that reproduces it, on fp32 NCHW [B, chw] images, per scale and per
+ * sample.  alpha = sqrt(gamma), sigma = sqrt(1 - gamma); p = pred_uncond ? pred_uncond + guidance (pred - pred_uncond) : pred.
+ *
+ * mdm_sampler_invert_step -- the preimage of one DDIM(0) step with the prediction held fixed: from x_s at the CLEANER node
+ * (gamma_s > gamma_t) the x_t for which mdm_sampler_step(mode 1, eta 0, clip 0) with the same p returns x_s,
+ *   pred_type 0, 1 (eps):  x_t = (alpha_t / alpha_s) (x_s - sigma_s p) + sigma_t p
+ *   pred_type 2 (v):       x_t = (x_s - (sigma_s alpha_t - alpha_s sigma_t) p) / (alpha_s alpha_t + sigma_s sigma_t)
+ * DDIM inversion with fixed-point refinement (Song et al. 2021; Pan et al. 2023; Garibi et al. 2024) evaluates p at the
+ * iterate and applies this to the same x_s again.  The small coefficients are formed without cancellation:
+ * sigma_s alpha_t - alpha_s sigma_t = (gamma_t - gamma_s) / (sigma_s alpha_t + alpha_s sigma_t), and for eps the coefficient
+ * of p is (gamma_s - gamma_t) / ((sigma_t alpha_s + alpha_t sigma_s) alpha_s).  gamma_s == 1 (the image itself) is allowed;
+ * gamma_t < 1.  No threshold: a clamp has no inverse.  x_t_out aliases nothing.
+ *
+ * mdm_sampler_noise_map -- the noise of one ancestral step solved for (edit-friendly DDPM inversion, Huberman-Spiegelglas et
+ * al. 2024): z = (x_s - mu) / sigma, where mu is what mdm_sampler_step computes from (x_t, p) before it adds noise -- the same
+ * guidance combine, x0, clip 0 / 1 / 2 (2: thr[b], from mdm_sampler_step(clip 3) and mdm_abs_quantile) and mode 0 / 1, by the
+ * same device functions -- and sigma its noise factor, so that mdm_sampler_step(noise = z) maps x_t to x_s.  A sample whose
+ * sigma is 0 (gamma_last == 1) gets z = 0.  mode 1 needs ddim_eta > 0.  z_out aliases nothing.
+ *
+ * Both: chw % 4 == 0, 16-byte accesses, one vec4 per thread with a grid stride, no allocation, no workspace, no host sync,
+ * no atomics: capturable, two runs are bit-identical, and a row's bits do not depend on the rows beside it.  Invalid host
+ * arguments: a negative status, nothing launched. */
+int mdm_sampler_invert_step(const float* x_s, const float* pred, const float* pred_uncond, float guidance,
+                            const float* gamma_s, const float* gamma_t, float* x_t_out, int B, size_t chw, int pred_type,
+                            void* stream);
+int mdm_sampler_noise_map(const float* x_t, const float* x_s, const float* pred, const float* pred_uncond, float guidance,
+                          const float* gamma, const float* gamma_last, const float* thr, float* z_out, int B, size_t chw,
+                          int pred_type, int mode, float ddim_eta, int clip, float image_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@
 //   models/unet.py:871-872 x_t / x_t.std((1, 2, 3))   (unbiased), nested level with skip_normalization = false
 //   clis/train_parallel.py:194-195  images = (uint8 - 127) / 128, NHWC -> NCHW
 #include "common.hpp"
+#include "step_math.hpp"
 
 namespace mdm {
 
@@ -42,17 +43,7 @@ __device__ __forceinline__ void normal4(const RngState& st, unsigned long long b
 
 __global__ void rng_advance_kernel(RngState* st, unsigned long long blocks) { st->offset += blocks; }
 
-template <typename F>
-__device__ __forceinline__ void for_each_vec4(size_t total4, F f) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (size_t)gridDim.x * blockDim.x) f(i);
-}
-
-enum { PT_EPS = 0, PT_V = 2 };   // PredictionType: DDPM (0) and DDIM (1) both predict eps; V_PREDICTION = 2
-
-// x0 from the model output (samplers.py:347-367)
-__device__ __forceinline__ float x0_of(float xt, float pred, float sg, float s1g, int ptype) {
-  return ptype == PT_V ? xt * sg - pred * s1g : (xt - pred * s1g) / sg;
-}
+// (for_each_vec4, x0_of and the step's own arithmetic -- step_row / step_mean: step_math.hpp, shared with invert.hip)
 
 // ---------------------------------------------------------------------------------------------------------
 // N1: one reverse step on a [B, chw] image.  mode 0 = ancestral DDPM posterior mean (ddim_eta is None),
@@ -75,40 +66,23 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(StepArgs a) {
   const float gate = a.noise_gate ? a.noise_gate[0] : 1.f;
   for_each_vec4(total4, [&](size_t i) {
     const int b = (int)(i / a.chw4);
-    const float g = a.gamma[b], gl = a.gamma_last[b];
-    const float sg = sqrtf(g), s1g = sqrtf(1.f - g), sgl = sqrtf(gl);
+    const StepRow r = step_row(a.gamma[b], a.gamma_last[b], a.mode, a.eta);
     const f32x4 xt = reinterpret_cast<const f32x4*>(a.x_t)[i];
     f32x4 p = reinterpret_cast<const f32x4*>(a.pred)[i];
-    if (a.pred_uncond) {
-      const f32x4 pu = reinterpret_cast<const f32x4*>(a.pred_uncond)[i];
-      p = pu + a.guidance * (p - pu);
-    }
-    const float alpha = g / gl, beta = 1.f - alpha;
-    float beta_t = beta * (1.f - gl) / (1.f - g);
+    if (a.pred_uncond) p = guided(p, reinterpret_cast<const f32x4*>(a.pred_uncond)[i], a.guidance);
     f32x4 x0, xl;
     float nz[4] = {0.f, 0.f, 0.f, 0.f};
     if (a.need_noise) {
       if (a.noise) { const f32x4 t = reinterpret_cast<const f32x4*>(a.noise)[i]; nz[0] = t[0]; nz[1] = t[1]; nz[2] = t[2]; nz[3] = t[3]; }
       else if (gen) normal4(st, i, a.rng_stream, nz);
     }
-    if (a.mode == 1 && a.eta > 0.f) beta_t *= a.eta * a.eta;
     const float thr = a.clip == 2 ? a.thr[b] : 1.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float v = x0_of(xt[e], p[e], sg, s1g, a.ptype);
-      if (a.clip == 1) v = fminf(fmaxf(v * a.scale, -1.f), 1.f) / a.scale;
-      else if (a.clip == 2) v = fminf(fmaxf(v * a.scale, -thr), thr) / thr / a.scale;
-      else if (a.clip == 3) v = v * a.scale;
-      x0[e] = v;
-      float x;
-      if (a.mode == 0) {
-        x = v * beta * sgl / (1.f - g) + xt[e] * sqrtf(alpha) * (1.f - gl) / (1.f - g);
-      } else {
-        const float eps = (xt[e] - v * sg) / s1g;
-        x = v * sgl + eps * sqrtf(a.eta > 0.f ? 1.f - gl - beta_t : 1.f - gl);
-      }
-      if (a.need_noise && !(a.mode == 1 && a.eta <= 0.f)) x += sqrtf(beta_t) * gate * nz[e];
-      xl[e] = x;
+      float v;
+      float x = step_mean(r, xt[e], p[e], thr, a.ptype, a.mode, a.eta, a.clip, a.scale, v);
+      if (a.need_noise && !(a.mode == 1 && a.eta <= 0.f)) x += sqrtf(r.beta_t) * gate * nz[e];
+      x0[e] = v; xl[e] = x;
     }
     reinterpret_cast<f32x4*>(a.x0_out)[i] = x0;
     if (a.clip != 3) reinterpret_cast<f32x4*>(a.x_last_out)[i] = xl;
@@ -544,11 +518,6 @@ __global__ __launch_bounds__(256) void pag_combine_kernel(const float* pred, con
 }  // namespace mdm
 
 using namespace mdm;
-
-static inline int stream_blocks(size_t n) {
-  size_t b = (n + 255) / 256;
-  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
 
 extern "C" int mdm_rng_advance(unsigned long long* state, unsigned long long blocks, void* stream) {
   MDM_CHECK_ARG(state);

@@ -5,7 +5,8 @@ Layout of the package
   ops.py          torch.autograd tape entries around the C ABI
   unet.py         UNet, config dataclasses (mirror of ml_mdm.models.unet)
   nested_unet.py  NestedUNet (mirror of ml_mdm.models.nested_unet)
-  diffusion.py    Diffusion / NestedDiffusion train-step + sampling call surface
+  diffusion.py    Diffusion / NestedDiffusion train-step + sampling call surface; invert / sample_from / Inverted: image
+                  inversion (DDIM fixed point, DDPM noise maps: samplers.Sampler.invert / noise_maps / step_noise=)
   samplers.py     noise schedules + DDPM/DDIM updates, DPM-Solver++(2M), SASolver (SA-Solver: predictor-corrector); LossGuide: loss-guided (DPS) sampling through the model's input gradient;
                   SampleOptions: the sampling options beyond the reference, their checks and what they compose with
   configs.py      the three shipped architectures (cc12m 64 / 256 / 1024)
@@ -53,6 +54,7 @@ from . import lora  # noqa: F401,E402
 from . import fp8  # noqa: F401,E402
 from .ops import activation_recompute_enabled, enable_activation_recompute  # noqa: F401,E402
 from .samplers import AttendExcite, LossGuide, MapGuide, SASolver  # noqa: F401,E402
+from .diffusion import Inverted  # noqa: F401,E402
 from . import pag  # noqa: F401,E402
 from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
@@ -98,4 +100,5 @@ __all__ = [
     "MapGuide",
     "AttendExcite",
     "SASolver",
+    "Inverted",
 ]

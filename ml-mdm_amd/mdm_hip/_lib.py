@@ -20,7 +20,7 @@ EXT_HEADER = os.path.join(_ROOT, "include", "mdm_hip_ext.h")    # capabilities t
 LIB_PATH = os.environ.get("MDM_HIP_LIB") or os.path.join(_HERE, "libmdm_hip.so")
 SOURCES = ["gemm_conv.hip", "norm.hip", "attention.hip", "elementwise.hip", "optim.hip", "diffusion_ops.hip",
            "text_encoder.hip", "text_encoder_bwd.hip", "lora.hip", "fp8.hip", "stem.hip", "freeu.hip", "guidance.hip", "tiles.hip", "quantile.hip",
-           "sa_solver.hip"]
+           "sa_solver.hip", "invert.hip"]
 
 ABI_VERSION = int(re.search(r"#define\s+MDM_HIP_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1))
 
@@ -35,7 +35,7 @@ class MdmHipError(RuntimeError):
 def build(force: bool = False, verbose: bool = True) -> str:
     """Compile every HIP source for gfx950 into ml-mdm_amd/mdm_hip/libmdm_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    hdrs = [os.path.join(CSRC, h) for h in ("common.hpp", "conv_args.hpp", "attn32.hpp")]
+    hdrs = [os.path.join(CSRC, h) for h in ("common.hpp", "conv_args.hpp", "attn32.hpp", "step_math.hpp")]
     deps = srcs + [HEADER, EXT_HEADER] + hdrs
     if not force and os.path.exists(LIB_PATH):
         if all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):

@@ -201,6 +201,69 @@ class Diffusion(nn.Module):
                           t=t0, **kwargs)
 
 
+    def invert(self, images, lm_outputs, lm_mask, device, method="ddim", graphed=None, micros={}, **kwargs):
+        """A GIVEN image back to the noise and the trajectory that reproduce it -> an ``Inverted`` for ``sample_from``.
+        ``method="ddim"``: DDIM inversion with fixed-point refinement (``Sampler.invert``; ``iterations=`` K); ``graphed``: a
+        ``GraphedSampler`` of this pipeline replays the K n denoiser calls.  ``method="ddpm"``: edit-friendly DDPM inversion
+        (``Sampler.noise_maps``; ``ddim_eta=``, ``seed=`` / ``noise_fn=``) -- its n - 1 calls are independent and run once,
+        eagerly, whatever ``graphed`` says.  Schedule keywords (``num_inference_steps`` / ``resample_steps`` / ``t``) as
+        ``sample`` and ``partial_diffusion``; they are kept in the record.  Other keywords go to the sampler's method
+        (``guidance_scale`` and the options it takes)."""
+        if method not in ("ddim", "ddpm"):
+            raise ValueError("invert: method = %r (wanted \"ddim\" or \"ddpm\")" % (method,))
+        self.eval()
+        smp, model = self.sampler, self.get_model()
+        images = images.to(device)
+        resample_steps = bool(kwargs.pop("resample_steps", False))
+        n = int(kwargs.pop("num_inference_steps", 2000)) if resample_steps else smp.n_steps
+        schedule = dict(num_inference_steps=n, resample_steps=True)   # (all of the schedule's steps: the same nodes)
+        if method == "ddpm":
+            eta = kwargs.pop("ddim_eta", None)
+            x_t, maps = smp.noise_maps(model, images, lm_outputs, lm_mask, micros, ddim_eta=eta, **schedule, **kwargs)
+            t0 = int(smp._inversion_nodes("invert", n, True, kwargs.get("t"))[0])
+            return Inverted("ddpm", x_t, t0, maps, ddim_eta=eta, **schedule)
+        if graphed is not None:
+            sample = dict(micros, lm_outputs=lm_outputs, lm_mask=lm_mask)
+            x_t, t0 = graphed.invert(images, sample, device, num_inference_steps=n, **kwargs)
+        else:
+            x_t, t0 = smp.invert(model, images, lm_outputs, lm_mask, micros, **schedule, **kwargs)
+        return Inverted("ddim", x_t, t0, None, **schedule)
+
+    def sample_from(self, inv, sample, device, graphed=None, **kwargs):
+        """Resume from an ``Inverted``: the trajectory from ``inv.x_t`` at time ``inv.t`` on the schedule it was made with --
+        DDIM(0) for a DDIM record, the replay of ``inv.step_noise`` (``step_noise=``) under ``inv.ddim_eta`` for a DDPM one.
+        With the conditioning and guidance of the inversion: the image again; with another prompt in ``sample``
+        (``lm_outputs`` / ``lm_mask`` and the micro-conditioning): its edit.  The late start is ``partial_diffusion``'s:
+        ``t=`` of the eager sampler, ``start_step`` / ``start_noise`` of ``graphed``.  Other keywords go to ``sample``."""
+        self.eval()
+        smp, model = self.sampler, self.get_model()
+        kw = dict(kwargs, ddim_eta=0 if inv.method == "ddim" else inv.ddim_eta)
+        if inv.step_noise is not None:
+            kw["step_noise"] = inv.step_noise
+        xs = inv.x_t if isinstance(inv.x_t, (list, tuple)) else [inv.x_t]
+        if graphed is not None:
+            return graphed.sample(xs[0].shape[0], sample, xs[0].shape[-1], device, num_inference_steps=inv.num_inference_steps,
+                                  start_noise=[x.to(device) for x in xs], start_step=inv.t, **kw)
+        x_t = [x.to(device) for x in xs] if isinstance(inv.x_t, (list, tuple)) else inv.x_t.to(device)
+        return smp.sample(model, x_t, sample["lm_outputs"], sample["lm_mask"], self.get_micro_conditioning(sample), t=inv.t,
+                          num_inference_steps=inv.num_inference_steps, resample_steps=inv.resample_steps, **kw)
+
+
+@dataclass
+class Inverted:
+    """What ``Diffusion.invert`` found for an image, and what ``Diffusion.sample_from`` needs to resume from it.
+    ``method``: "ddim" or "ddpm".  ``x_t``: the start of the trajectory, at schedule time ``t`` (a hi -> lo list for a nested
+    model).  ``step_noise``: the noise maps of the DDPM method (``Sampler.noise_maps``), None for DDIM.  The schedule
+    arguments it was made with -- the replay must walk the same nodes -- and, for the maps, the ``ddim_eta`` they solve."""
+    method: str
+    x_t: object
+    t: int
+    step_noise: object = None
+    num_inference_steps: int = None
+    resample_steps: bool = True
+    ddim_eta: float = None
+
+
 class NestedModel(Model):
     def forward(self, x_t: List[torch.Tensor], times, lm_outputs, lm_mask, micros={}, mixed_ratio=None):
         if not self.diffusion_config.no_use_residual:

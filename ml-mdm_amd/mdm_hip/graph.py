@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from . import attn_maps as _attn_maps, ops, regions as _regions
 from . import tiling as _tiling
-from .samplers import SampleOptions, _checked_rule, gather_windows, merge_windows, model_rows, repeat_rows, split_rows
+from .samplers import (SampleOptions, _check_step_noise, _checked_rule, gather_windows, merge_windows, model_rows, repeat_rows,
+                       split_rows)
 from .unet import switch_state, switchable
 
 
@@ -103,6 +104,31 @@ class GraphedDenoiser(nn.Module):
         return static_out.clone()
 
 
+def _predict(smp, vm, opts, guidance, names, xs, times, cond_s, micros_s, out_scale, bias_s=None, rec_s=None, tiled=None):
+    """The denoiser call of a graph body: the vision model ``vm`` on the static images ``xs`` (hi -> lo) at ``times`` [B], with
+    the static conditioning ``cond_s`` = (cond_emb, cond_states, cond_mask) and micros -> (conditional predictions,
+    unconditional ones or Nones, perturbed ones or None), one entry per scale.  The model's batch: [uncond | cond] under
+    classifier-free guidance, + [perturbed] under perturbed-attention guidance (the static conditioning and micros buffers
+    hold that many rows), under ``opts.switches`` with the body's static bias / recorder handles.  ``tiled`` = (tiles,
+    ratios, canvases, T): one gather per scale in place of the row repeat, one merge behind the model -- whole canvases out."""
+    uncond, pert = opts.blocks(guidance)
+    reps = 1 + uncond + pert
+    T = 1
+    if tiled is None:
+        xin, tin = repeat_rows(xs, times, reps)
+    else:
+        tiles, ratios, canvases, T = tiled
+        xin, tin = gather_windows(xs, tiles, ratios, reps), _tiling.time_rows(times, T, reps)
+    with opts.switches(vm, guidance, xs[0].shape[0] * T, names=names, bias=bias_s, rec=rec_s):
+        preds = vm.forward_denoising(smp._from_scales(xin), tin, *cond_s, micros_s)
+    preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
+    if out_scale != 0:
+        preds = [torch.tanh(p / out_scale) * out_scale for p in preds]
+    if tiled is not None:
+        preds = merge_windows(preds, tiles, ratios, canvases)
+    return split_rows(preds, uncond, pert)
+
+
 class GraphedSampler:
     """``Diffusion.sample`` / ``NestedDiffusion.sample`` with one hipGraph replay per denoise step.
 
@@ -155,9 +181,11 @@ class GraphedSampler:
         return (mk(t, torch.long), mk(s, torch.long), mk(jump, torch.float32), prev,
                 mk(rule.rows(self.sampler, t, s), torch.float32)), (t, s)
 
-    def _build(self, key, xs, cond, mask, n_steps, guidance, micros, rule, known, resample, opts, names, bias_source):
+    def _build(self, key, xs, cond, mask, n_steps, guidance, micros, rule, known, resample, opts, names, bias_source,
+               step_noise=False):
         """``rule``: the call's ``StepRule``; ``opts``: its ``SampleOptions``, with what ``sample`` resolved of them for this
-        model: ``names``, its ``layer_names``, and the caller's bias handle (None without ``regions``)"""
+        model: ``names``, its ``layer_names``, and the caller's bias handle (None without ``regions``); ``step_noise``: the
+        body hands the step the call's noise maps"""
         smp = self.sampler
         cfg = opts.cfg_at(guidance)
         model = self.pipe.get_model()
@@ -179,6 +207,9 @@ class GraphedSampler:
             kn_mask = [None if m is None else m.clone() for m in known.masks]
             kn_inv, kn_rng = known.inv_scales, ops.DeviceRng(0, dev)
         x_static = [x.clone() for x in xs]
+        # step_noise: the maps of every row, [rows, B, C, H, W] per scale; the body hands the step row ``idx`` of each as its
+        # noise.  sample() fills the rows it replays (zeros where a step has no map: its gate is 0 anyway)
+        noise_tab = [torch.zeros(len(t_host), *x.shape, dtype=torch.float32, device=dev) for x in xs] if step_noise else None
         # the rule's history, updated in place by the step kernel and read only where its row says there is some: what a
         # warm-up pass or an earlier call left is never seen.  ``tab_rule`` holds the full schedule's rows until a call
         # writes those it replays; the warm-up passes run row 0
@@ -214,30 +245,17 @@ class GraphedSampler:
             g_t, g_s = gammas(t), gammas(s)
             g_hist = [gammas(p.index_select(0, idx)) for p in tab_prev]
             times = (t - 1).expand(B)
-            # the model's batch: [uncond | cond] under classifier-free guidance, + [perturbed] under perturbed-attention
-            # guidance (the static conditioning and micros buffers hold that many rows)
-            uncond, pert = opts.blocks(guidance)
-            reps = 1 + uncond + pert
-            if tiles is None:
-                xin, tin = repeat_rows(x_static, times, reps)
-            else:   # one gather per scale in place of the repeat; the merge below hands the step whole canvases
-                xin, tin = gather_windows(x_static, tiles, ratios, reps), _tiling.time_rows(times, T, reps)
             if rec_s is not None:
                 rec_s.gate = rec_gate.index_select(0, idx)
-            with opts.switches(vm, guidance, B * T, names=names, bias=bias_s, rec=rec_s):
-                preds = vm.forward_denoising(smp._from_scales(xin), tin, ce_s, cs_s, cm_s, micros_s)
-            preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
-            if out_scale != 0:
-                preds = [torch.tanh(p / out_scale) * out_scale for p in preds]
-            if tiles is not None:
-                preds = merge_windows(preds, tiles, ratios, canvases)
-            preds, pus, pps = split_rows(preds, uncond, pert)
+            preds, pus, pps = _predict(smp, vm, opts, guidance, names, x_static, times, (ce_s, cs_s, cm_s), micros_s, out_scale,
+                                       bias_s, rec_s, None if tiles is None else (tiles, ratios, canvases, T))
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> ops.abs_quantile, the
             # library's radix select, -> update kernel, all captured), drawing in its order (use_device_rng())
             cfg_kw = {} if cfg is None else dict(cfg_state=cfg_state, cfg_gates=(cfg_run_gate.index_select(0, idx),
                                                                                   cfg_w_gate.index_select(0, idx)))
+            given = None if noise_tab is None else [tab.index_select(0, idx)[0] for tab in noise_tab]
             _, x_last = smp._step_scales(x_static, preds, pus, g_t, g_s, image_scales, opts, rule, row, state, g_hist,
-                                         guidance_scale=guidance, rng=rng, pps=pps, **cfg_kw)
+                                         guidance_scale=guidance, rng=rng, pps=pps, step_noise=given, **cfg_kw)
             for x, xl in zip(x_static, x_last):
                 x.copy_(xl)
             if known is not None:   # blends hi -> lo, then jumps hi -> lo: the draw order of KnownRegion
@@ -278,15 +296,144 @@ class GraphedSampler:
         # indices -> out-of-bounds gather)
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
                    t_host=t_host, s_host=s_host, rows=tab_rule, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
-                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, rec=rec_s, rec_gate=rec_gate,
+                   cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, rec=rec_s, rec_gate=rec_gate, noise=noise_tab,
                    keep=(tab_t, tab_s, tab_jump, tab_prev, state, cfg_state))
         self._graphs[key] = ent
         return ent
 
+    def _build_invert(self, key, xs, cond, mask, n_steps, iterations, guidance, micros, opts, names, bias_source):
+        """The graph of ``invert``: ONE denoiser call at a static iterate plus the invert kernel of every scale, replayed
+        K n times.  Device tables, one row per replay: the time of the cleaner node s the step starts from, the time of
+        the node t it goes to (the time the model is handed, plus one), and a gate that is 1 on a step's last iteration,
+        where the iterate becomes the next step's x_s."""
+        smp = self.sampler
+        model = self.pipe.get_model()
+        vm = model.vision_model
+        dev = xs[0].device
+        B = xs[0].shape[0]
+        nodes = smp.set_timesteps(n_steps)[::-1]                     # ascending from 0
+        mk = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        s_host, t_host = np.repeat(nodes[:-1], iterations), np.repeat(nodes[1:], iterations)
+        last_host = np.zeros(len(t_host), dtype="float32")
+        last_host[iterations - 1::iterations] = 1
+        tab_s, tab_t, tab_last = mk(s_host, torch.long), mk(t_host, torch.long), mk(last_host, torch.float32)
+        idx = torch.zeros(1, dtype=torch.long, device=dev)
+        x_static = [x.clone() for x in xs]   # x_s, the node the step starts from
+        y_static = [x.clone() for x in xs]   # the iterate y^j: what the model sees, and what the invert kernel writes
+        micros_s = {k: v.clone() for k, v in micros.items()}
+        ce, cs, cm = vm.forward_conditioning(cond, mask)
+        cond_s = (ce.clone(), cs.clone(), cm.clone() if cm is not None else None)
+        out_scale = model._output_scale
+        bias_s = _regions.StaticBias(bias_source) if bias_source is not None else None
+        rec_s = rec_gate = None
+        if opts.attn_maps is not None:   # records on a step's last iteration, inside the recorder's interval: invert() fills the gates
+            rec_s = _attn_maps.StaticRows(opts.attn_maps.rows_for(*opts.blocks(guidance), dev))
+            rec_gate = torch.ones(len(t_host), dtype=torch.float32, device=dev)
+
+        def body():
+            s, t, last = tab_s.index_select(0, idx), tab_t.index_select(0, idx), tab_last.index_select(0, idx)
+            gammas = lambda time: smp._gammas_of_scales(model, smp.gammas.index_select(0, time).expand(B))
+            g_s, g_t = gammas(s), gammas(t)
+            if rec_s is not None:
+                rec_s.gate = rec_gate.index_select(0, idx)
+            preds, pus, _ = _predict(smp, vm, opts, guidance, names, y_static, (t - 1).expand(B), cond_s, micros_s, out_scale,
+                                     bias_s, rec_s)
+            for k, (x, y) in enumerate(zip(x_static, y_static)):
+                # the kernel reads x_s and the predictions and writes the iterate, which the model is done with
+                smp.get_inverted_xt(x, preds[k], g_s[k], g_t[k], pred_uncond=pus[k], guidance_scale=guidance, out=y)
+                x.copy_(torch.where(last != 0, y, x))   # the gate SELECTS: off, x_s keeps its bits
+            idx.add_(1)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):   # warm-up: packs weights, sets kernel attributes, sizes the allocator
+            for _ in range(self._warmup):
+                idx.zero_()
+                body()
+            idx.zero_()
+        torch.cuda.current_stream().wait_stream(side)
+        if bias_s is not None:
+            bias_s.freeze()
+        if rec_s is not None:
+            rec_s.freeze()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            body()
+        ent = dict(graph=graph, x=x_static, y=y_static, ce=cond_s[0], cs=cond_s[1], cm=cond_s[2], idx=idx, micros=micros_s,
+                   t_host=t_host, last_host=last_host, nodes=nodes, bias=bias_s, rec=rec_s, rec_gate=rec_gate,
+                   keep=(tab_s, tab_t, tab_last))
+        self._graphs[key] = ent
+        return ent
+
+    @torch.no_grad()
+    def invert(self, images, sample, device, iterations=1, num_inference_steps=50, t=None, guidance_scale=1, **options):
+        """``Sampler.invert(..., resample_steps=True)`` -- DDIM inversion with fixed-point refinement -- with one hipGraph
+        replay per denoiser call: K n of them (``_build_invert``), to the eager result bit for bit.  -> (x_t at the noisiest
+        node reached, a hi -> lo list for a nested model; that node's time).  ``t``: stop at the first node <= t -- the
+        same graph, fewer replays.  ``options``: those ``Sampler.invert`` takes (``regions`` / ``region_layers``, ``freeu``,
+        ``attn_maps``), with the static buffers and the graph-key parts they have in ``sample``; the key also holds
+        "invert" and K."""
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+            raise ValueError("invert: iterations = %r (wanted an int >= 1)" % (iterations,))
+        smp = self.sampler
+        opts = smp._inversion_options("GraphedSampler.invert", dict(options),
+                                      ("guide", "map_guide", "tiles", "known_images", "cfg", "pag"))
+        if ops.adapter_epoch() != self._adapter_epoch:   # as sample(): LoRA adapters moved since the graphs were captured
+            self._graphs.clear()
+            self._adapter_epoch = ops.adapter_epoch()
+        self.pipe.eval()
+        model = self.pipe.get_model()
+        n = int(num_inference_steps)
+        nodes = smp._inversion_nodes("invert", n, True, t)[::-1]
+        pyr, image_scales = smp._image_scales(model, images.to(device))
+        xs = [x if sc == 1 else x / sc for x, sc in zip(pyr, image_scales)]
+        cond, mask = sample["lm_outputs"], sample["lm_mask"]
+        if guidance_scale != 1:
+            assert xs[0].shape[0] * 2 == cond.shape[0], "classifier-free guidance: lm_outputs = [uncond | cond]"
+        micros = {k: torch.as_tensor(v, device=xs[0].device).reshape(-1).float()
+                  for k, v in self.pipe.get_micro_conditioning(sample).items()}
+        regions, maps = opts.regions, opts.attn_maps
+        for what, o in (("regions", regions), ("attn_maps", maps)):
+            if o is not None and (o.rows != xs[0].shape[0] or o.S != cond.shape[1]):
+                raise ValueError("%s over %d rows of %d tokens for a batch of %d images with %d tokens"
+                                 % (what, o.rows, o.S, xs[0].shape[0], cond.shape[1]))
+        names = opts.layer_names(model.vision_model)
+        key = (("invert", int(iterations)), tuple(tuple(x.shape) for x in xs), tuple(cond.shape), n, float(guidance_scale),
+               torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype() if torch.is_autocast_enabled() else None,
+               ops.fp32_split_enabled(), tuple(sorted((k, tuple(v.shape)) for k, v in micros.items())))
+        key = key + opts.graph_key(model.vision_model, guidance_scale, names)
+        bias_source = None if regions is None else regions.rows_for(*opts.blocks(guidance_scale), xs[0].device)
+        ent = self._graphs.get(key) or self._build_invert(key, xs, cond, mask, n, int(iterations), float(guidance_scale), micros,
+                                                          opts, names, bias_source)
+        if bias_source is not None:
+            ent["bias"].fill(bias_source)
+        for sx, sy, x in zip(ent["x"], ent["y"], xs):
+            sx.copy_(x)
+            sy.copy_(x)
+        for k, v in micros.items():
+            ent["micros"][k].copy_(v)
+        ce, cs, cm = model.vision_model.forward_conditioning(cond, mask)
+        ent["ce"].copy_(ce)
+        ent["cs"].copy_(cs)
+        if ent["cm"] is not None:
+            ent["cm"].copy_(cm)
+        replays = (len(nodes) - 1) * int(iterations)
+        if maps is not None:
+            rec_on = ent["last_host"] * np.asarray([maps.on(tt, smp.n_steps) for tt in ent["t_host"]], dtype="float32")
+            ent["rec_gate"].copy_(torch.from_numpy(rec_on))
+            ent["rec"].zero()
+        ent["idx"].zero_()
+        for _ in range(replays):
+            ent["graph"].replay()
+        if maps is not None:
+            ent["rec"].flush(maps, int(rec_on[:replays].sum()))
+        out = [x.clone() for x in ent["x"]]
+        return smp._from_scales(out), int(nodes[-1])
+
     @torch.no_grad()
     def sample(self, num_examples, sample, image_side, device, num_inference_steps=50, ddim_eta=None, guidance_scale=1,
                start_noise=None, seed=None, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-               start_step=None, **options):
+               start_step=None, step_noise=None, **options):
         """``options``: the keywords of ``SampleOptions`` (what each does is said there), with these graph-specific facts;
         the key parts are ``SampleOptions.graph_key``, and the body runs the model under ``SampleOptions.switches``.
         ``guide``, ``map_guide``: refused -- neither the user's function nor the autograd pass of a guided step can be captured.
@@ -315,7 +462,12 @@ class GraphedSampler:
         known image, and ``resample``, are part of the graph key.  ``start_step=t``: replay only the rows whose time is
         <= t, from ``start_noise`` = the image noised to the first of them (``Diffusion.partial_diffusion(...,
         graphed=self)`` does the noising).  ``solver=``: ``rule.key`` is part of the graph key (an ``SASolver``: its fields); every
-        call writes the rule's rows from its first replayed row on, counted from it: a late start restarts the orders."""
+        call writes the rule's rows from its first replayed row on, counted from it: a late start restarts the orders.
+        ``step_noise=maps`` (``Sampler.noise_maps``; as ``Sampler._sample``, which says what is refused): the maps live in a
+        static [rows, B, C, H, W] table per scale, filled by ``copy_`` on every call, and the body hands the step row ``idx``
+        of each table as its noise, so the generator is neither read nor advanced.  The graph key gains a "step_noise" flag:
+        other map values replay the same graph.  The tables hold rows x the size of x_t in fp32 -- about 0.67 GB for 50
+        steps of one nested-1024 image (3 x (1024^2 + 256^2 + 64^2) floats per row), per image of the batch."""
         opts = SampleOptions(**options)
         if opts.guide is not None:
             raise NotImplementedError("GraphedSampler does not take guide=: loss-guided sampling calls an arbitrary user "
@@ -326,6 +478,7 @@ class GraphedSampler:
                                       "user function and an autograd pass through the denoiser in every guided step, and "
                                       "neither can be captured in a hipGraph; use the eager Sampler.sample(..., map_guide=...)")
         rule = _checked_rule(solver, ddim_eta, opts.check(), known_images, resample)
+        _check_step_noise(step_noise, solver, ddim_eta, resample)
         cfg = opts.cfg_at(guidance_scale)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
@@ -377,9 +530,14 @@ class GraphedSampler:
             known = smp._known_region(model, xs, known_images, known_mask, known_seed, None)
             key = key + (tuple(k is not None for k in known.images), int(resample))
         key = key + opts.graph_key(model.vision_model, guidance_scale, names)
+        if step_noise is not None:   # checked against the rows this call replays, before anything is captured
+            steps = smp.set_timesteps(int(num_inference_steps))
+            kept = steps[:-1] <= (steps[0] if start_step is None else start_step)
+            step_noise = smp._checked_step_noise(model, xs, step_noise, rule.rows(smp, steps[:-1][kept], steps[1:][kept]))
+            key = key + (("step_noise",),)
         bias_source = None if regions is None else regions.rows_for(*opts.blocks(guidance_scale), xs[0].device)
         ent = self._graphs.get(key) or self._build(key, xs, cond, mask, int(num_inference_steps), float(guidance_scale), micros,
-                                                   rule, known, int(resample), opts, names, bias_source)
+                                                   rule, known, int(resample), opts, names, bias_source, step_noise is not None)
         if bias_source is not None:
             ent["bias"].fill(bias_source)
         for sx, x in zip(ent["x"], xs):
@@ -417,6 +575,10 @@ class GraphedSampler:
             ent["rec"].zero()
         # the rule's rows of this call, counted from its first row: a late start is a trajectory of its own
         ent["rows"][first:].copy_(torch.from_numpy(rule.rows(smp, ent["t_host"][first:], ent["s_host"][first:])))
+        if step_noise is not None:
+            for i, z in enumerate(step_noise):
+                for k, tab in enumerate(ent["noise"]):
+                    tab[first + i].zero_() if z is None else tab[first + i].copy_(z[k])
         if seed is not None:
             ent["rng"].state.copy_(torch.tensor([seed & (2**63 - 1), 0], dtype=torch.int64))
         for _ in range(ent["n"] - first):

@@ -2877,6 +2877,65 @@ def sampler_jump(x_s, g_t, g_s, noise=None, rng=None, rng_stream=1, gate=None, o
     return out
 
 
+def sampler_invert_step(x_s, pred, g_s, g_t, prediction_type, pred_uncond=None, guidance_scale=1.0, out=None):
+    """The preimage of one DDIM(0) step with the prediction held fixed (include/mdm_hip_ext.h mdm_sampler_invert_step) as ONE
+    kernel: from ``x_s`` at the cleaner level ``g_s`` to the x_t at ``g_t`` ([B] each, g_s > g_t; g_s == 1 allowed) that
+    ``sampler_step(ddim_eta=0, clip="NONE")`` with the same prediction maps back to ``x_s``.  No threshold.  ``out``: the
+    buffer x_t is written to (it aliases nothing).  -> x_t"""
+    x_s, pred = _img(x_s), _img(pred)
+    B = x_s.shape[0]
+    chw = x_s.numel() // B
+    if chw % 4:
+        raise _lib.MdmHipError("sampler_invert_step: C * H * W must be a multiple of 4 (got %s)" % (tuple(x_s.shape),))
+    if pred.shape != x_s.shape:
+        raise _lib.MdmHipError("sampler_invert_step: pred %s vs x_s %s" % (tuple(pred.shape), tuple(x_s.shape)))
+    g_s, g_t = _vec(g_s, B), _vec(g_t, B)
+    pu = _img(pred_uncond) if pred_uncond is not None else None
+    if pu is not None and pu.shape != x_s.shape:
+        raise _lib.MdmHipError("sampler_invert_step: pred_uncond %s vs x_s %s" % (tuple(pu.shape), tuple(x_s.shape)))
+    out = torch.empty_like(x_s) if out is None else _inplace_img(out, x_s, "sampler_invert_step: out")
+    _lib.check(
+        _lib.lib().mdm_sampler_invert_step(_p(x_s), _p(pred), _p(pu), float(guidance_scale), _p(g_s), _p(g_t), _p(out), B, chw,
+                                           _ptype(prediction_type), _stream()),
+        "mdm_sampler_invert_step",
+    )
+    return out
+
+
+def sampler_noise_map(x_t, x_s, pred, g, g_last, prediction_type, ddim_eta=None, clip="CLIP", image_scale=1.0,
+                      pred_uncond=None, guidance_scale=1.0, thr=None):
+    """The noise of one ancestral step solved for (include/mdm_hip_ext.h mdm_sampler_noise_map) as ONE kernel:
+    z = (x_s - mu) / sigma with mu and sigma those of ``sampler_step`` on (x_t, pred) with the same arguments, so that
+    ``sampler_step(..., need_noise=True, noise=z)`` maps ``x_t`` to ``x_s``; z = 0 for a sample with ``g_last == 1``.
+    ``ddim_eta``: None (the DDPM posterior) or > 0.  ``clip``: "NONE" | "CLIP" | "DYNAMIC" (needs ``thr`` [B], from
+    ``sampler_step(clip="X0_ONLY")`` + ``abs_quantile``).  -> z"""
+    x_t, x_s, pred = _img(x_t), _img(x_s), _img(pred)
+    B = x_t.shape[0]
+    chw = x_t.numel() // B
+    if chw % 4:
+        raise _lib.MdmHipError("sampler_noise_map: C * H * W must be a multiple of 4 (got %s)" % (tuple(x_t.shape),))
+    if x_s.shape != x_t.shape or pred.shape != x_t.shape:
+        raise _lib.MdmHipError("sampler_noise_map: x_s %s and pred %s vs x_t %s"
+                               % (tuple(x_s.shape), tuple(pred.shape), tuple(x_t.shape)))
+    g, gl = _vec(g, B), _vec(g_last, B)
+    pu = _img(pred_uncond) if pred_uncond is not None else None
+    if pu is not None and pu.shape != x_t.shape:
+        raise _lib.MdmHipError("sampler_noise_map: pred_uncond %s vs x_t %s" % (tuple(pu.shape), tuple(x_t.shape)))
+    th = _vec(thr, B) if thr is not None else None
+    cm = {"NONE": 0, "CLIP": 1, "DYNAMIC": 2}[clip]
+    mode, eta = (0, 0.0) if ddim_eta is None else (1, float(ddim_eta))
+    if mode == 1 and eta <= 0:
+        raise _lib.MdmHipError("sampler_noise_map: ddim_eta = %r adds no noise, there is no map to solve for" % (ddim_eta,))
+    z = torch.empty_like(x_t)
+    _lib.check(
+        _lib.lib().mdm_sampler_noise_map(_p(x_t), _p(x_s), _p(pred), _p(pu), float(guidance_scale), _p(g), _p(gl), _p(th),
+                                         _p(z), B, chw, _ptype(prediction_type), mode, eta, cm,
+                                         float(image_scale) if image_scale else 1.0, _stream()),
+        "mdm_sampler_noise_map",
+    )
+    return z
+
+
 def guide_seed(v, x0, a, b, clip="CLIP", thr=None, image_scale=1.0):
     """Chain rule of loss-guided sampling through the step's x0 = a x_t + b pred, its image scale and its threshold
     (include/mdm_hip.h mdm_guide_seed) as ONE kernel: ``v`` = d loss / d x0 in image units, ``x0`` what the step kernel

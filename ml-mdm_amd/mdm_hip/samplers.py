@@ -26,7 +26,10 @@ noised image (SDEdit, Meng et al. 2022).  Six options act on the denoiser call o
 and leave the update alone -- loss guidance (``guide``), perturbed-attention guidance (``pag_scale`` / ``pag_layers``), regional
 prompts and token weights (``regions`` / ``region_layers``), FreeU (``freeu``), projected / rescaled classifier-free
 guidance (``cfg``) and tiled sampling of a canvas larger than the model's window (``tiles``): ``SampleOptions`` says what each
-does, holds their checks and is what travels from ``sample`` to the step.
+does, holds their checks and is what travels from ``sample`` to the step.  Image inversion goes the other way, from a GIVEN
+image to the noise and the trajectory that reproduce it: ``Sampler.invert`` (DDIM inversion with fixed-point refinement;
+``ops.sampler_invert_step`` / ``invert_step``) and ``Sampler.noise_maps`` with ``sample(..., step_noise=maps)`` (edit-friendly
+DDPM inversion; ``ops.sampler_noise_map`` / ``noise_map``); the update rules and the reverse-step kernels are untouched by it.
 """
 import contextlib
 import math
@@ -538,6 +541,54 @@ def jump(x_s, g_t, g_s, noise):
     return a.sqrt() * x_s + (1 - a).clamp(min=0).sqrt() * noise
 
 
+def invert_step(x_s, pred, g_s, g_t, prediction_type, pred_uncond=None, guidance_scale=1):
+    """torch ops of ``ops.sampler_invert_step`` (for CPU tensors): the preimage of one DDIM(0) step with the prediction held
+    fixed.  With alpha = sqrt(g), sigma = sqrt(1 - g), ``g_s`` the cleaner level (g_s > g_t; g_s == 1 allowed) and p the
+    guided prediction:
+
+        eps:  x_t = (alpha_t / alpha_s) (x_s - sigma_s p) + sigma_t p
+        v:    x_t = (x_s - (sigma_s alpha_t - alpha_s sigma_t) p) / (alpha_s alpha_t + sigma_s sigma_t)
+
+    so that ``get_prediction_xt_last(x_t, p, g_t, g_s, ddim_eta=0)`` without a threshold returns ``x_s``.  The small
+    coefficients come as quotients, (sigma_t alpha_s)^2 - (alpha_t sigma_s)^2 = g_s - g_t, not as differences: between
+    neighbouring nodes of a 1000-step schedule the difference would cancel to a few digits."""
+    p = pred if pred_uncond is None else pred_uncond + guidance_scale * (pred - pred_uncond)
+    g_s, g_t = _b(g_s), _b(g_t)
+    a_s, s_s, a_t, s_t = g_s.sqrt(), (1 - g_s).sqrt(), g_t.sqrt(), (1 - g_t).sqrt()
+    cross = s_t * a_s + a_t * s_s
+    if _enum(PredictionType, prediction_type) == PredictionType.V_PREDICTION:
+        inv = 1 / (a_s * a_t + s_s * s_t)
+        return inv * x_s + (g_s - g_t) / cross * inv * p
+    return a_t / a_s * x_s + (g_s - g_t) / (cross * a_s) * p
+
+
+def noise_map(x_s, mu, g, g_last, ddim_eta=None):
+    """torch ops of the last line of ``ops.sampler_noise_map``: z = (x_s - mu) / sigma for the mean ``mu`` of the step from
+    level ``g`` to ``g_last`` and sigma the factor ``get_prediction_xt_last`` puts on its noise -- the square root of the DDPM
+    posterior variance, times ``ddim_eta`` under DDIM; z = 0 for a sample with sigma == 0 (g_last == 1)"""
+    g, g_last = _b(g), _b(g_last)
+    sigma = ((1 - g / g_last) * (1 - g_last) / (1 - g)).sqrt()
+    if ddim_eta is not None:
+        sigma = ddim_eta * sigma
+    on = sigma > 0
+    return torch.where(on, (x_s - mu) / torch.where(on, sigma, torch.ones_like(sigma)), torch.zeros_like(x_s))
+
+
+def _check_step_noise(step_noise, solver, ddim_eta, resample):
+    """what a call with ``step_noise=`` cannot have"""
+    if step_noise is None:
+        return
+    if solver is not None:
+        raise ValueError("step_noise= with solver=%r: the maps are the noise of the ancestral step (solver=None) they were "
+                         "extracted for" % (solver,))
+    if ddim_eta is not None and ddim_eta <= 0:
+        raise ValueError("step_noise= with ddim_eta=%r: a deterministic step adds no noise, the maps would be ignored" % (ddim_eta,))
+    if resample > 1:
+        raise ValueError("step_noise= with resample=%d: there is one map per step, and a repeated step would add it twice" % resample)
+    if not isinstance(step_noise, (list, tuple)):
+        raise ValueError("step_noise must be the list of maps Sampler.noise_maps returned (got %s)" % type(step_noise).__name__)
+
+
 def known_pyramid(known, mask, ratios):
     """One top-scale image and mask -> hi->lo lists for the scales ``ratios`` (top side / side of the scale; ratios[0] == 1).
     Images are average-pooled.  A lower-scale pixel is known only where EVERY pixel of its block is (mask == 1 there),
@@ -881,7 +932,12 @@ class SampleOptions:
     ``cfg``, no Jacobian; ``pag_scale`` with ``cfg``; ``guide`` with ``tiles`` (no backward); ``regions`` with ``tiles``
     (the bias is laid out over the whole canvas); and ``attn_maps`` with ``tiles`` (a window's queries are not the
     canvas's); ``map_guide`` with ``guide`` (two corrections of one step), with ``tiles`` and with an SA solver.  Everything
-    else composes."""
+    else composes.
+
+    Not a field here: ``step_noise=maps`` (``Sampler.noise_maps`` -> ``sample``) replaces the noise the ancestral update adds,
+    so it is a plain keyword of ``sample`` beside ``solver_noise_fn``; every option above composes with it, because the maps
+    are added behind whatever prediction the options make.  ``Sampler.invert`` and ``Sampler.noise_maps`` themselves take the
+    options that act on the denoiser call only (``Sampler.INVERSION_REFUSED``)."""
 
     guide: object = None
     pag_scale: float = 0.0
@@ -1235,6 +1291,37 @@ class Sampler(nn.Module):
         flat = x0s if x0s.dtype == torch.float64 else x0s.float()
         return _abs_quantile_clamped(flat.reshape(flat.shape[0], -1), ratio, vmax)
 
+    # ---- the two steps of image inversion (not in the reference) ----------------------------------------
+    def get_inverted_xt(self, x_s, pred, g_s, g_t, prediction_type=None, pred_uncond=None, guidance_scale=1, out=None):
+        """The preimage of one DDIM(0) step with the prediction held fixed (``invert_step`` has the formulas) -> x_t at the
+        noisier level ``g_t``.  GPU tensors take ``ops.sampler_invert_step`` (``out``: the buffer it writes), CPU tensors
+        the torch ops."""
+        pt = prediction_type or self._config.prediction_type
+        if self._on_hip(x_s, None):
+            return ops.sampler_invert_step(x_s.float(), pred.float(), g_s, g_t, pt, guidance_scale=guidance_scale, out=out,
+                                           pred_uncond=None if pred_uncond is None else pred_uncond.float())
+        if out is not None:
+            raise ValueError("out= belongs to the invert kernel: GPU tensors only")
+        return invert_step(x_s, pred, g_s, g_t, pt, pred_uncond, guidance_scale)
+
+    def get_noise_map(self, x_t, x_s, pred, g, g_last, prediction_type=None, clip_fn=None, ddim_eta=None, image_scale=None,
+                      pred_uncond=None, guidance_scale=1):
+        """The noise z for which the step of ``get_prediction_xt_last`` -- same arguments, ``need_noise=True,
+        input_noise=z`` -- takes ``x_t`` to ``x_s``: z = (x_s - mu) / sigma, mu and sigma that step's mean and noise factor;
+        0 for a sample with ``g_last == 1``.  ``ddim_eta``: None or > 0.  GPU tensors take ``ops.sampler_noise_map`` (the
+        dynamic thresholds: the x0 kernel and ``ops.abs_quantile`` in front of it, as the step does), CPU tensors the torch
+        ops: the step itself without noise, then ``noise_map``."""
+        if ddim_eta is not None and ddim_eta <= 0:
+            raise ValueError("get_noise_map: ddim_eta = %r adds no noise, there is no map to solve for" % (ddim_eta,))
+        if self._on_hip(x_t, clip_fn):
+            x_t, pred, kw = self._hip_step_args(x_t, pred, g, g_last, prediction_type, clip_fn, image_scale, pred_uncond,
+                                                guidance_scale, None, ddim_eta)
+            return ops.sampler_noise_map(x_t, x_s.float(), pred, g, g_last, ddim_eta=ddim_eta, **kw)
+        _, mu, _ = self.get_prediction_xt_last(x_t, pred, g, g_last, prediction_type, clip_fn, need_noise=False,
+                                               ddim_eta=ddim_eta, image_scale=image_scale, return_eps=False,
+                                               pred_uncond=pred_uncond, guidance_scale=guidance_scale)
+        return noise_map(x_s, mu, g, g_last, ddim_eta)
+
     # ---- one step of DPM-Solver++(2M) (not in the reference) ------------------------------------------
     def get_prediction_xt_last_2m(self, x_t, pred, g, g_last, g_prev=None, x0_prev=None, second_order=False,
                                   prediction_type=None, clip_fn=None, image_scale=None, pred_uncond=None,
@@ -1539,7 +1626,7 @@ class Sampler(nn.Module):
                           return_details, solver_state)
 
     def _step(self, model, time_step, x_t, lm_outputs, lm_mask, micros, opts, rule, row, last, guidance_scale=1,
-              return_details=False, solver_state=None, rows=None, noise_fn=None):
+              return_details=False, solver_state=None, rows=None, noise_fn=None, step_noise=None):
         """``get_xt_minus_1`` behind its checks: what the loop of ``_sample`` calls, with the options it checked and the
         ``StepRule`` it resolved once, that rule's ``row`` of this step and the time ``last`` the step goes to (and, under
         ``opts.tiles``, with the window count and the conditioning it repeated per window once: ``rows``).  Denoiser, update
@@ -1570,7 +1657,7 @@ class Sampler(nn.Module):
             outs = ([None if v is None else v.detach() for v in vs] for vs in outs)
         with no_grad:
             x0, x_s = self._step_scales(*outs, g_t, g_s, image_scales, opts, rule, row, state, g_hist, guidance_scale,
-                                        thr_out=thr, pps=pps, noise_fn=noise_fn, **cfg_kw)
+                                        thr_out=thr, pps=pps, noise_fn=noise_fn, step_noise=step_noise, **cfg_kw)
         if guide is not None:
             x_s = self._guide_update(guide, x_in, list(zip(pcs, pus)), x0[0], x_s, g_t[0], image_scales[0], guidance_scale,
                                      thr[0])
@@ -1580,13 +1667,30 @@ class Sampler(nn.Module):
         return self._from_scales(x0), self._from_scales(x_s), (g_t[-1], g_s[-1])
 
     def _step_scales(self, x_t, pcs, pus, g_t, g_s, image_scales, opts, rule, row, state, g_hist=(), guidance_scale=1,
-                     thr_out=None, pps=None, rng=None, cfg_state=None, cfg_on=True, cfg_gates=None, noise_fn=None):
+                     thr_out=None, pps=None, rng=None, cfg_state=None, cfg_on=True, cfg_gates=None, noise_fn=None,
+                     step_noise=None):
         """The update of every scale behind the denoiser call -> (x0 list, x_s list), all lists hi -> lo: ``rule.step`` per
         scale with the rule's ``row``, ``state`` and ``g_hist`` (``StepRule``).  The one reverse step of the eager samplers
         and of ``GraphedSampler``, whose graph passes a device row, the rule's buffers, its generator ``rng`` and the cfg
-        state and gates through to the kernels.  ``pps`` with ``opts.pag_scale != 0``: the perturbed predictions -- one
-        combine per scale (GPU tensors: ``ops.pag_combine``, CPU tensors: ``pag_combine``) hands the step the guided prediction,
-        with no unconditional one and guidance 1; ``opts.cfg`` with ``guidance_scale != 1``: the same with ``_cfg_scales``."""
+        state and gates through to the kernels.  What the step is handed is ``_guided_preds``'s.  ``step_noise``: this
+        step's noise maps, one per scale (``_sample``'s ``step_noise[i]``), the ``input_noise`` of the ancestral step."""
+        n = len(x_t)
+        pcs, pus, guidance_scale = self._guided_preds(x_t, pcs, pus, g_t, image_scales, opts, guidance_scale, pps, cfg_state,
+                                                      cfg_on, cfg_gates)
+        kw = dict(prediction_type=self._config.prediction_type, clip_fn=self.clip_sample, guidance_scale=guidance_scale,
+                  thr_out=thr_out, rng=rng, noise_fn=noise_fn)
+        given = (lambda k: {}) if step_noise is None else (lambda k: dict(input_noise=step_noise[k]))
+        x0, x_s = zip(*(rule.step(self, k, x_t[k], pcs[k], g_t[k], g_s[k], row, g_hist, state, image_scale=image_scales[k],
+                                  pred_uncond=pus[k], **given(k), **kw) for k in range(n)))
+        return list(x0), list(x_s)
+
+    def _guided_preds(self, x_t, pcs, pus, g_t, image_scales, opts, guidance_scale=1, pps=None, cfg_state=None, cfg_on=True,
+                      cfg_gates=None):
+        """What the update of a step is handed, from what the denoiser call returned -> (predictions, unconditional
+        predictions or Nones, guidance scale), lists hi -> lo.  ``pps`` with ``opts.pag_scale != 0``: the perturbed
+        predictions -- one combine per scale (GPU tensors: ``ops.pag_combine``, CPU tensors: ``pag_combine``) makes the guided
+        prediction, with no unconditional one and guidance 1; ``opts.cfg`` with ``guidance_scale != 1``: the same with
+        ``_cfg_scales``.  Neither: as given -- the plain combine is the step kernel's."""
         n = len(x_t)
         cfg, pag_scale = opts.cfg_at(guidance_scale), opts.pag_scale
         if cfg is not None:
@@ -1596,11 +1700,7 @@ class Sampler(nn.Module):
             pcs = [ops.pag_combine(pc.float(), None if pu is None else pu.float(), pp.float(), guidance_scale, pag_scale)
                    if pc.is_cuda else pag_combine(pc, pu, pp, guidance_scale, pag_scale) for pc, pu, pp in zip(pcs, pus, pps)]
             pus, guidance_scale = [None] * n, 1
-        kw = dict(prediction_type=self._config.prediction_type, clip_fn=self.clip_sample, guidance_scale=guidance_scale,
-                  thr_out=thr_out, rng=rng, noise_fn=noise_fn)
-        x0, x_s = zip(*(rule.step(self, k, x_t[k], pcs[k], g_t[k], g_s[k], row, g_hist, state, image_scale=image_scales[k],
-                                  pred_uncond=pus[k], **kw) for k in range(n)))
-        return list(x0), list(x_s)
+        return pcs, pus, guidance_scale
 
     def _cfg_scales(self, cfg, x_t, pcs, pus, g_t, image_scales, guidance_scale, state=None, on=True, gates=None):
         """The projected / rescaled guidance combine of every scale (``mdm_hip/guidance.py``) -> the guided predictions.
@@ -1642,9 +1742,13 @@ class Sampler(nn.Module):
         (``resample_steps=True, num_inference_steps=20..50``).  ``solver=SASolver(predictor, corrector, tau,
         tau_interval)`` (``"sa"``: the defaults): SA-Solver, a predictor-corrector of up to third order with a noise level
         between the probability-flow ODE and the reverse SDE, one denoiser call per step too; its noise comes from
-        ``use_device_rng`` if set, else from ``torch.randn_like``.  It takes no ``guide=`` and no ``resample > 1``."""
+        ``use_device_rng`` if set, else from ``torch.randn_like``.  It takes no ``guide=`` and no ``resample > 1``.
+        ``step_noise=maps`` (what ``noise_maps`` returned for an image, with the same schedule arguments and ``t=``): the
+        ancestral step adds ``maps[i][k]`` at step i, scale k, in place of drawn noise -- the trajectory of that image, or,
+        with another prompt, its edit (``_sample`` has the details)."""
         opts = SampleOptions.pop(dict(kwargs)).check()   # the checks of the call, here and not at the generator's first next()
         _checked_rule(kwargs.get("solver"), kwargs.get("ddim_eta"), opts, kwargs.get("known_images"), kwargs.get("resample", 1))
+        _check_step_noise(kwargs.get("step_noise"), kwargs.get("solver"), kwargs.get("ddim_eta"), kwargs.get("resample", 1))
         guide = opts.guide
         gen = self._sample(*args, **kwargs)
         if guide is None:
@@ -1677,10 +1781,192 @@ class Sampler(nn.Module):
         return KnownRegion.build(shapes, top.device, top.dtype if top.is_floating_point() else torch.float32, known_images,
                                  known_mask, ratios, image_scales, known_seed, known_noise_fn)
 
+    # ---- image inversion (not in the reference): from a GIVEN image to the noise and the trajectory that reproduce it -------
+    INVERSION_REFUSED = {
+        "guide": "guide=: the guide corrects x_s after a reverse step, and inversion takes no reverse step",
+        "map_guide": "map_guide=: it moves x_t in front of a reverse step, and inversion takes no reverse step",
+        "tiles": "tiles=: inversion of a canvas larger than the model's window is not implemented",
+        "known_images": "known_images=: the whole image is given -- there is no free region to hold beside a known one",
+        "cfg": "cfg=: the projected / rescaled combine carries a momentum along the sampling direction and reads x_t; the "
+               "implicit step that mdm_sampler_invert_step solves takes the plain combine p_u + w (p_c - p_u) only",
+        "pag": "pag_scale != 0: mdm_sampler_invert_step takes the plain combine p_u + w (p_c - p_u) only, a combine of three "
+               "predictions in front of it is not implemented",
+    }
+
+    def _inversion_options(self, what, options, refused):
+        """the ``SampleOptions`` of an inversion call out of its keywords, checked; ``refused``: the names of
+        ``INVERSION_REFUSED`` this call cannot have"""
+        on = {name: options.pop(name, None) is not None for name in ("known_images", "known_mask")}
+        opts = SampleOptions(**options).check()
+        on = dict(guide=opts.guide is not None, map_guide=opts.map_guide is not None, tiles=opts.tiles is not None,
+                  known_images=on["known_images"] or on["known_mask"], cfg=opts.cfg is not None, pag=opts.pag_scale != 0)
+        for name in refused:
+            if on[name]:
+                raise NotImplementedError("%s does not take %s" % (what, self.INVERSION_REFUSED[name]))
+        return opts
+
+    def _inversion_nodes(self, what, num_inference_steps, resample_steps, t):
+        """the schedule nodes of an inversion call, descending to 0: those of ``_sample`` with the same arguments; ``t``
+        keeps the nodes <= t, the first of which is where ``partial_diffusion`` would start"""
+        steps = self.set_timesteps(num_inference_steps if resample_steps else self.n_steps)
+        if t is not None:
+            if not (steps <= t).any():
+                raise ValueError("%s: t = %r is below every step of the schedule" % (what, t))
+            steps = steps[steps <= t]
+        return steps
+
+    def _image_scales(self, model, images):
+        """a top-scale image in output units -> (the average-pooled pyramid hi -> lo, the image scale of every level): the
+        clean image of level k in the units of x_t is pyramid[k] / scale[k], as ``partial_diffusion`` takes it"""
+        ratios, image_scales = self._scale_info(model)
+        hip = images.is_cuda
+        top = images.float() if hip else images
+        if top.shape[-2] % ratios[-1] or top.shape[-1] % ratios[-1]:
+            raise ValueError("image side %d x %d is not a multiple of the nesting ratio %d" % (*top.shape[-2:], ratios[-1]))
+        return [top] + [ops.avgpool(top, r) if hip else F.avg_pool2d(top, r) for r in ratios[1:]], image_scales
+
+    @torch.no_grad()
+    def invert(self, model, images, lm_outputs, lm_mask, micros={}, iterations=1, num_inference_steps=2000,
+               resample_steps=False, t=None, guidance_scale=1, **options):
+        """DDIM inversion with fixed-point refinement (Song et al. 2021; Pan et al. 2023, "AIDI"; Garibi et al. 2024,
+        "ReNoise"): the deterministic DDIM(0) map walked BACKWARDS from ``images`` (top scale, output units) -> (x_t at the
+        noisiest node reached -- a hi -> lo list in ``NestedSampler`` --, that node's time), so that ``sample(model, x_t, ...,
+        t=time, ddim_eta=0)`` with the same schedule arguments, conditioning and guidance returns the images.
+
+        The nodes are those of ``set_timesteps`` as ``_sample`` takes them (``num_inference_steps`` / ``resample_steps``),
+        walked in ascending order from node 0, where every scale holds its clean image / image scale (a nested model: the
+        average-pooled pyramid); ``t`` stops at the first node <= t.  A step from node s to the noisier node t is implicit
+        -- the prediction belongs to the x_t looked for -- and is solved by ``iterations`` = K denoiser calls:
+
+            y^0 = x_s ;   y^{j+1} = invert_step(x_s, p(y^j, t))   (``get_inverted_xt``; the model is handed t - 1) ;   x_t = y^K
+
+        K = 1 is plain DDIM inversion with the prediction evaluated at the target time; more converge to the exact
+        preimage of the DDIM(0) step (for the v-prediction of Gaussian data on the cosine schedule the round-trip error
+        falls 16x per iteration).  K n denoiser calls over n steps: ``GraphedSampler.invert`` replays them.  No threshold is
+        applied -- a clamp has no inverse --, so the round trip is exact where sampling does not clamp either.
+        ``options``: of ``SampleOptions`` those that only change the denoiser call -- ``regions`` / ``region_layers``,
+        ``freeu``, and ``attn_maps``, which records the maps of the GIVEN image, at the last iteration of every step in its
+        interval; LoRA and MXFP8 act inside the model.  ``INVERSION_REFUSED`` says why the others are not taken."""
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+            raise ValueError("invert: iterations = %r (wanted an int >= 1)" % (iterations,))
+        opts = self._inversion_options("invert", dict(options), ("guide", "map_guide", "tiles", "known_images", "cfg", "pag"))
+        quiet = opts if opts.attn_maps is None else SampleOptions(**dict(vars(opts), attn_maps=None))
+        nodes = self._inversion_nodes("invert", num_inference_steps, resample_steps, t)[::-1]
+        pyr, image_scales = self._image_scales(model, images)
+        xs = [x if sc == 1 else x / sc for x, sc in zip(pyr, image_scales)]
+        B = xs[0].shape[0]
+        ones = torch.ones(B, dtype=torch.long, device=self.gammas.device)
+        for s, tt in zip(nodes[:-1], nodes[1:]):
+            g_s, g_t = self._scale_gammas(model, int(s), B), self._scale_gammas(model, int(tt), B)
+            ys = xs
+            for j in range(iterations):
+                pcs, pus, _, _ = self._forward_model_raw(model, ys, ones * int(tt) - 1, lm_outputs, lm_mask, micros,
+                                                         guidance_scale, opts if j == iterations - 1 else quiet, None,
+                                                         (int(tt), self.n_steps))
+                ys = [self.get_inverted_xt(xs[k], pcs[k], g_s[k], g_t[k], pred_uncond=pus[k], guidance_scale=guidance_scale)
+                      for k in range(len(xs))]
+            xs = ys
+        return self._from_scales(xs), int(nodes[-1])
+
+    @torch.no_grad()
+    def noise_maps(self, model, images, lm_outputs, lm_mask, micros={}, num_inference_steps=2000, resample_steps=False,
+                   t=None, guidance_scale=1, ddim_eta=None, seed=0, noise_fn=None, return_nodes=False, **options):
+        """Edit-friendly DDPM inversion (Huberman-Spiegelglas et al. 2024) of ``images`` (top scale, output units) ->
+        (x_start, maps) for ``sample(model, x_start, ..., t=<the same>, step_noise=maps)`` with the same schedule arguments
+        and ``ddim_eta`` (None: the DDPM posterior; or > 0).
+
+        Every node above 0 of the trajectory (``_sample``'s steps; ``t`` keeps those <= t) gets a noisy copy of the image
+        of its own, with INDEPENDENT noise, x_i = alpha_i image / scale + sigma_i eps_i per scale (a nested model: the
+        average-pooled pyramid and every scale's own gamma); ``x_start`` is the first.  ``maps[i]``, one tensor per scale
+        hi -> lo, is the noise z for which step i lands on the next copy exactly: z = (x_{i+1} - mu_i) / sigma_i with mu_i,
+        sigma_i the mean and noise factor of the ancestral step at x_i under the model's prediction there, this call's
+        conditioning and guidance, and the sampler's own threshold function (``get_noise_map``).  None where the step adds
+        no noise (``_noisy_step``: the last).  The n - 1 denoiser calls are independent of each other.
+        Replaying the maps reproduces the copies, hence the image, under ANY guidance scale and threshold function, because
+        the maps absorb what the step does; another prompt at replay edits the image with its layout kept.
+        The draws: GPU tensors -- ``ops.noise_images`` from ONE ``ops.DeviceRng(seed)`` on stream 0, the nodes in sampling
+        order (noisiest first), within a node the scales hi -> lo, the generator advanced by ``numel`` after each; CPU
+        tensors -- ``noise_fn(image)`` (default ``torch.randn_like``) called in the same order.
+        ``options``: as ``invert``, plus ``cfg=`` and ``pag_scale`` / ``pag_layers`` -- the prediction handed on is then the
+        combined one (``_guided_preds``, what the step itself would be handed).  ``return_nodes``: also return the copies, a
+        list over the nodes of hi -> lo lists."""
+        if ddim_eta is not None and ddim_eta <= 0:
+            raise ValueError("noise_maps: ddim_eta = %r is deterministic, it adds no noise to extract" % (ddim_eta,))
+        opts = self._inversion_options("noise_maps", dict(options), ("guide", "map_guide", "tiles", "known_images"))
+        steps = self._inversion_nodes("noise_maps", num_inference_steps, resample_steps, t)
+        if len(steps) < 2:
+            raise ValueError("noise_maps: t = %r leaves no step to invert" % (t,))
+        times = steps[:-1]
+        noisy = Ancestral(ddim_eta).rows(self, times, steps[1:])[:, 0]
+        pyr, image_scales = self._image_scales(model, images)
+        hip = images.is_cuda
+        B = pyr[0].shape[0]
+        rng = ops.DeviceRng(seed, images.device) if hip else None
+        noise_fn = noise_fn or torch.randn_like
+
+        def copy_at(time):
+            if time == 0:   # gamma = 1: the image itself, nothing drawn
+                return [x if sc == 1 else x / sc for x, sc in zip(pyr, image_scales)]
+            out = []
+            for img, g, sc in zip(pyr, self._scale_gammas(model, time, B), image_scales):
+                if hip:
+                    out.append(ops.noise_images(img, g, rng=rng, inv_scale=1.0 / sc)[0])
+                    rng.advance(img.numel())
+                else:
+                    out.append(Sampler.get_xt(self, img if sc == 1 else img / sc, noise_fn(img), g))
+            return out
+
+        ones = torch.ones(B, dtype=torch.long, device=self.gammas.device)
+        history = {}   # cfg: the momentum buffers, along the sampling direction
+        x_start = cur = copy_at(int(times[0]))
+        nodes, maps = [cur], []
+        for i, ts in enumerate(times):
+            ts, last = int(ts), int(steps[i + 1])
+            if not noisy[i]:
+                maps.append(None)
+                continue
+            nxt = copy_at(last)
+            g_t, g_s = self._scale_gammas(model, ts, B), self._scale_gammas(model, last, B)
+            pcs, pus, _, pps = self._forward_model_raw(model, cur, ones * ts - 1, lm_outputs, lm_mask, micros, guidance_scale,
+                                                       opts, None, (ts, self.n_steps))
+            cfg_kw = {} if opts.cfg_at(guidance_scale) is None else dict(cfg_state=history, cfg_on=opts.cfg.on(ts, self.n_steps))
+            pcs, pus, w = self._guided_preds(cur, pcs, pus, g_t, image_scales, opts, guidance_scale, pps, **cfg_kw)
+            maps.append([self.get_noise_map(cur[k], nxt[k], pcs[k], g_t[k], g_s[k], clip_fn=self.clip_sample, ddim_eta=ddim_eta,
+                                            image_scale=image_scales[k], pred_uncond=pus[k], guidance_scale=w)
+                         for k in range(len(cur))])
+            cur = nxt
+            if last != 0:
+                nodes.append(cur)
+        x_start = self._from_scales(x_start)
+        return (x_start, maps, nodes) if return_nodes else (x_start, maps)
+
+    def _checked_step_noise(self, model, x_t, step_noise, rule_rows):
+        """``step_noise`` against the trajectory it is replayed on -> one entry per step: the hi -> lo list of maps, or None
+        where the step adds no noise"""
+        top = x_t[0] if isinstance(x_t, (list, tuple)) else x_t
+        B, C, H, W = top.shape
+        shapes = [(B, C, H // r, W // r) for r in self._scale_info(model)[0]]
+        if len(step_noise) != len(rule_rows):
+            raise ValueError("step_noise holds the maps of %d steps, this trajectory has %d (the schedule arguments and t= "
+                             "of the noise_maps call?)" % (len(step_noise), len(rule_rows)))
+        out = []
+        for i, (maps, row) in enumerate(zip(step_noise, rule_rows)):
+            if not row[0]:
+                out.append(None)
+                continue
+            maps = _listed(maps)
+            if maps is None:
+                raise ValueError("step_noise[%d] is None, but step %d of this trajectory adds noise" % (i, i))
+            if len(maps) != len(shapes) or any(not torch.is_tensor(m) or tuple(m.shape) != s for m, s in zip(maps, shapes)):
+                raise ValueError("step_noise[%d]: wanted %d maps of the shapes %s (got %s)"
+                                 % (i, len(shapes), shapes, [tuple(m.shape) if torch.is_tensor(m) else type(m).__name__ for m in maps]))
+            out.append(list(maps))
+        return out
+
     def _sample(self, model, x_t, lm_outputs, lm_mask, micros, return_sequence=False, use_beta_tilde=False, t=-1,
                 num_inference_steps=2000, ddim_eta=None, guidance_scale=1, resample_steps=False, disable_bar=True,
                 yield_output=False, solver=None, known_images=None, known_mask=None, resample=1, known_seed=0,
-                known_noise_fn=None, solver_noise_fn=None, **post_args):
+                known_noise_fn=None, solver_noise_fn=None, step_noise=None, **post_args):
         """``guide``, ``pag_scale`` / ``pag_layers``, ``regions`` / ``region_layers``, ``freeu``, ``cfg``, ``tiles``: see
         ``SampleOptions``; they are taken out of the keywords here (``sample`` has checked them), the rest goes to ``_postprocess``.
         ``known_images`` / ``known_mask``: hold a region of the trajectory on a given image.  After every reverse step,
@@ -1691,10 +1977,17 @@ class Sampler(nn.Module):
         (n - 1) r + 1 denoiser calls.  The noise of both comes from ``known_seed`` (see ``KnownRegion``).  One top-scale
         tensor each, or hi -> lo lists for a nested model (``[None, low]``: super-resolution of a given image).
         ``solver_noise_fn(x)``: with an ``SASolver`` of tau > 0, the noise of every launch that adds some (called per scale,
-        hi -> lo) instead of the device generator / ``torch.randn_like``."""
+        hi -> lo) instead of the device generator / ``torch.randn_like``.
+        ``step_noise``: the noise maps of ``noise_maps`` -- one entry per step of THIS trajectory (same schedule arguments
+        and ``t=``), each a hi -> lo list of tensors shaped like that scale's x_t, or None where the step adds no noise (the
+        last).  The ancestral step (``solver=None``; DDPM, or DDIM with ``ddim_eta > 0``) gets ``step_noise[i][k]`` as its
+        ``input_noise``: no generator is read or advanced.  With ``x_t`` = the ``x_start`` of ``noise_maps`` and its
+        conditioning the trajectory passes through that call's noisy copies of the image, whatever the guidance scale and
+        the threshold function; another conditioning edits the image.  None: no bit changes."""
         assert not (yield_output and return_sequence)
         opts = SampleOptions.pop(post_args)
         rule = _checked_rule(solver, ddim_eta, opts, known_images, resample)
+        _check_step_noise(step_noise, solver, ddim_eta, resample)
         if known_mask is not None and known_images is None:
             raise ValueError("known_mask without known_images")
         if not resample_steps:
@@ -1705,6 +1998,8 @@ class Sampler(nn.Module):
         steps = torch.from_numpy(steps_host).to(self.gammas.device)
         # the rule's row of every step, counted from the first step of THIS trajectory, wherever it starts
         rule_rows = rule.rows(self, steps_host[:-1], steps_host[1:] if resample_steps else steps_host[:-1] - 1)
+        if step_noise is not None:
+            step_noise = self._checked_step_noise(model, x_t, step_noise, rule_rows)
         known = None
         if known_images is not None:
             known = self._known_region(model, x_t, known_images, known_mask, known_seed, known_noise_fn)
@@ -1721,7 +2016,8 @@ class Sampler(nn.Module):
             for rep in range(reps):
                 x0, x_t, extra = self._step(
                     model, ts, x_t, lm_outputs, lm_mask, micros, opts, rule, rule_rows[i], steps[i + 1] if resample_steps else ts - 1,
-                    guidance_scale, return_details=True, solver_state=history, rows=rows, noise_fn=solver_noise_fn)
+                    guidance_scale, return_details=True, solver_state=history, rows=rows, noise_fn=solver_noise_fn,
+                    step_noise=None if step_noise is None else step_noise[i])
                 if known is not None:
                     xs = self._to_scales(model, x_t)
                     B = xs[0].shape[0]
