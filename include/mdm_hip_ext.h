@@ -279,6 +279,39 @@ int mdm_sampler_noise_map(const float* x_t, const float* x_s, const float* pred,
                           const float* gamma, const float* gamma_last, const float* thr, float* z_out, int B, size_t chw,
                           int pred_type, int mode, float ddim_eta, int clip, float image_scale, void* stream);
 
+/* Prompt-to-prompt attention control (Hertz et al. 2022): an EDITED batch row r computes with the attention maps of its
+ * SOURCE row s.  The text term of mdm_attn_fwd is a softmax of its own over the S text keys, so mixing its probabilities
+ * over the token axis is linear in v_c -- (P_s M) v_c = P_s (M v_c) -- and the controlled layer is
+ *   out_h[r] = A_h(g_s ? s : r) v_h[r] + P_h(s) V'_h[r] + P_h(r) V''_h[r]
+ *   V'[r][i, :]  = g_c sum_{j live in r} M[r][i, j] v_c[r][j, :]     (i: a source token, j: an edit token; live: mask != 0)
+ *   V''[r][j, :] = (g_c D[r][j] + 1 - g_c) v_c[r][j, :]
+ * with the entry points above: mdm_attn_fwd without text keys on what mdm_ctrl_gather_qkv wrote, then mdm_attn_cross_bias
+ * twice in place with a zero bias -- (the source's q, kv_a, the source's mask) and (the row's own q, kv_b, its own mask).
+ * own_rows, src_rows: DEVICE int32 [R], the absolute batch rows r and s of the R edited rows; an entry outside [0, N)
+ * makes the kernel skip that row (nothing is read or written for it).  gate: a DEVICE float, 0 = off, anything else = on;
+ * it selects, so one captured graph serves a trajectory.
+ *
+ * mdm_ctrl_mix_kv -- kvc [N, S, 2C] (k_c | v_c) -> kv_a, kv_b [R, S, 2C] of the same dtype:
+ *   kv_a[r] = (k_c[s] | V'[r]),  kv_b[r] = (k_c[r] | V''[r]);  both key halves are copies, bit for bit.
+ * M: fp32 [R, S, m_ld], m_ld >= S and % 4 == 0 (row = source token, column = edit token); its columns [S, m_ld) and the
+ * columns of masked edit tokens are never read and may hold anything.  D: fp32 [R, S].  mask: [N, S] of 0/1 floats or NULL.
+ * V' is accumulated in fp32 by FMAs over j ascending and rounded once; V'' is one product, rounded once.  Gate off: V' is
+ * exact zeros and V'' is v_c[r] bit for bit.  One block per (8 source tokens, 64 16-byte channel chunks, row): a row's bits
+ * do not depend on R.  C % 8 == 0 (bf16) / % 4 == 0 (fp32), 16-byte aligned tensors, R <= 65535.
+ *
+ * mdm_ctrl_gather_qkv -- qkv [N, L, 3C] -> qkv_self [R, L, 3C]: q and k columns of row (gate ? s : r), v columns of row r;
+ * q_src [R, L, 3C]: the q columns of row s (its k and v columns are NOT written: mdm_attn_cross_bias with base == out
+ * reads q only).  Copies of 16 bytes, bit for bit.
+ *
+ * Both: dtype MDM_F32 (the fp32-split mode has fp32 tensors) or MDM_BF16.  No allocation, no workspace, no host sync, no
+ * atomics: capturable, and two runs are bit-identical.  Outputs alias neither each other nor the input.  Invalid host
+ * arguments: a negative status, nothing launched.  Forward only. */
+int mdm_ctrl_mix_kv(const void* kvc, const int* own_rows, const int* src_rows, const float* M, int m_ld, const float* D,
+                    const float* mask, const float* gate, void* kv_a, void* kv_b, int N, int R, int S, int C, int dtype,
+                    void* stream);
+int mdm_ctrl_gather_qkv(const void* qkv, const int* own_rows, const int* src_rows, const float* gate, void* qkv_self,
+                        void* q_src, int N, int R, int L, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

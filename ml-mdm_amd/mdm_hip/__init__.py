@@ -21,6 +21,8 @@ Layout of the package
   pag.py          perturbed-attention guidance: select / perturbed (the samplers' pag_scale / pag_layers)
   regions.py      regional prompts and token weights, a bias on the text cross-attention logits: RegionPrompts / concat /
                   applied (the samplers' regions / region_layers)
+  attn_control.py prompt-to-prompt attention control, an edited batch row computing with its source row's attention maps:
+                  AttnControl / applied (the samplers' control)
   attn_maps.py    cross-attention maps, the text term's probabilities recorded per token: AttnMaps / record / applied (the
                   samplers' attn_maps); GradRows / cross_probs: the maps on the autograd tape, for the samplers' map_guide
                   (samplers.MapGuide, samplers.AttendExcite: attention-map guidance, Attend-and-Excite)
@@ -60,6 +62,8 @@ from . import regions  # noqa: F401,E402
 from .regions import RegionPrompts  # noqa: F401,E402
 from . import attn_maps  # noqa: F401,E402
 from .attn_maps import AttnMaps  # noqa: F401,E402
+from . import attn_control  # noqa: F401,E402
+from .attn_control import AttnControl  # noqa: F401,E402
 from . import freeu  # noqa: F401,E402
 from .freeu import FreeU  # noqa: F401,E402
 from . import guidance  # noqa: F401,E402
@@ -81,6 +85,8 @@ __all__ = [
     "RegionPrompts",
     "attn_maps",
     "AttnMaps",
+    "attn_control",
+    "AttnControl",
     "UNet",
     "UNetConfig",
     "ResNetConfig",

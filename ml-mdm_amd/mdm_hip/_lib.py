@@ -20,7 +20,7 @@ EXT_HEADER = os.path.join(_ROOT, "include", "mdm_hip_ext.h")    # capabilities t
 LIB_PATH = os.environ.get("MDM_HIP_LIB") or os.path.join(_HERE, "libmdm_hip.so")
 SOURCES = ["gemm_conv.hip", "norm.hip", "attention.hip", "elementwise.hip", "optim.hip", "diffusion_ops.hip",
            "text_encoder.hip", "text_encoder_bwd.hip", "lora.hip", "fp8.hip", "stem.hip", "freeu.hip", "guidance.hip", "tiles.hip", "quantile.hip",
-           "sa_solver.hip", "invert.hip"]
+           "sa_solver.hip", "invert.hip", "attn_control.hip"]
 
 ABI_VERSION = int(re.search(r"#define\s+MDM_HIP_ABI_VERSION\s+(\d+)", open(HEADER).read()).group(1))
 

@@ -17,7 +17,7 @@ is one kernel per scale, the image pyramid one ``mdm_avgpool`` per level, and pr
 pipeline where the torch formulation needs ~25.  CPU tensors (host-logic tests against the reference goldens) take
 the torch formulation of the same formulas; nothing falls back from the GPU path.
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import List
 
 import numpy as np
@@ -262,6 +262,17 @@ class Inverted:
     num_inference_steps: int = None
     resample_steps: bool = True
     ddim_eta: float = None
+
+    def repeat(self, n):
+        """-> the record with the rows of ``x_t`` and of every noise map repeated ``n`` times in BLOCK order ([rows | rows |
+        ...]): the start of a batch whose first block replays the inverted images -- the sources of
+        ``sample_from(..., control=AttnControl(...))`` -- and whose other blocks are their edits under other prompts."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError("Inverted.repeat: n = %r (wanted an int >= 1)" % (n,))
+        rep = lambda t: torch.cat([t] * n)
+        both = lambda v: None if v is None else ([rep(t) for t in v] if isinstance(v, (list, tuple)) else rep(v))
+        noise = None if self.step_noise is None else [both(z) for z in self.step_noise]
+        return replace(self, x_t=both(self.x_t), step_noise=noise)
 
 
 class NestedModel(Model):

@@ -62,7 +62,8 @@ class GraphedDenoiser(nn.Module):
         if torch.is_grad_enabled() or self.model.training or micros:
             return self.model(x_t, times, conditioning, cond_mask, micros)
         switches = switch_state(self._switchable)
-        if any(h is not None for h in switches["_cross_bias"] + switches["_attn_rec"]):   # (a recorder: the caller's too)
+        # (a recorder: the caller's too; an attention control: its tables and gates are the caller's as well)
+        if any(h is not None for h in switches["_cross_bias"] + switches["_attn_rec"] + switches["_attn_ctrl"]):
             return self.model(x_t, times, conditioning, cond_mask, micros)
         if ops.adapter_epoch() != self._adapter_epoch:   # LoRA adapters attached / detached / merged / unmerged since
             self._graphs.clear()
@@ -104,12 +105,13 @@ class GraphedDenoiser(nn.Module):
         return static_out.clone()
 
 
-def _predict(smp, vm, opts, guidance, names, xs, times, cond_s, micros_s, out_scale, bias_s=None, rec_s=None, tiled=None):
+def _predict(smp, vm, opts, guidance, names, xs, times, cond_s, micros_s, out_scale, bias_s=None, rec_s=None, tiled=None,
+             ctrl_s=None):
     """The denoiser call of a graph body: the vision model ``vm`` on the static images ``xs`` (hi -> lo) at ``times`` [B], with
     the static conditioning ``cond_s`` = (cond_emb, cond_states, cond_mask) and micros -> (conditional predictions,
     unconditional ones or Nones, perturbed ones or None), one entry per scale.  The model's batch: [uncond | cond] under
     classifier-free guidance, + [perturbed] under perturbed-attention guidance (the static conditioning and micros buffers
-    hold that many rows), under ``opts.switches`` with the body's static bias / recorder handles.  ``tiled`` = (tiles,
+    hold that many rows), under ``opts.switches`` with the body's static bias / recorder / attention-control handles.  ``tiled`` = (tiles,
     ratios, canvases, T): one gather per scale in place of the row repeat, one merge behind the model -- whole canvases out."""
     uncond, pert = opts.blocks(guidance)
     reps = 1 + uncond + pert
@@ -119,7 +121,7 @@ def _predict(smp, vm, opts, guidance, names, xs, times, cond_s, micros_s, out_sc
     else:
         tiles, ratios, canvases, T = tiled
         xin, tin = gather_windows(xs, tiles, ratios, reps), _tiling.time_rows(times, T, reps)
-    with opts.switches(vm, guidance, xs[0].shape[0] * T, names=names, bias=bias_s, rec=rec_s):
+    with opts.switches(vm, guidance, xs[0].shape[0] * T, names=names, bias=bias_s, rec=rec_s, ctrl=ctrl_s):
         preds = vm.forward_denoising(smp._from_scales(xin), tin, *cond_s, micros_s)
     preds = list(preds) if isinstance(preds, (list, tuple)) else [preds]
     if out_scale != 0:
@@ -236,6 +238,14 @@ class GraphedSampler:
         if opts.attn_maps is not None:
             rec_s = _attn_maps.StaticRows(opts.attn_maps.rows_for(*opts.blocks(guidance), dev))
             rec_gate = torch.ones(len(t_host), dtype=torch.float32, device=dev)
+        # attention control: static copies of M, D and the row tables (a handle of this entry's own, not the one the eager
+        # samplers share), and the two gate tables, one row per replay; sample() fills M, D and the tables.  Until then:
+        # both gates on -- what the warm-up passes run with
+        ctrl_s = ctrl_gc = ctrl_gs = None
+        if opts.control is not None and opts.control.R > 0:
+            ctrl_s = opts.control.rows_for(*opts.blocks(guidance), dev, cached=False)
+            ctrl_gc = torch.ones(len(t_host), dtype=torch.float32, device=dev)
+            ctrl_gs = torch.ones(len(t_host), dtype=torch.float32, device=dev)
 
         def body():
             t = tab_t.index_select(0, idx)
@@ -247,8 +257,10 @@ class GraphedSampler:
             times = (t - 1).expand(B)
             if rec_s is not None:
                 rec_s.gate = rec_gate.index_select(0, idx)
+            if ctrl_s is not None:
+                ctrl_s.gate_c, ctrl_s.gate_s = ctrl_gc.index_select(0, idx), ctrl_gs.index_select(0, idx)
             preds, pus, pps = _predict(smp, vm, opts, guidance, names, x_static, times, (ce_s, cs_s, cm_s), micros_s, out_scale,
-                                       bias_s, rec_s, None if tiles is None else (tiles, ratios, canvases, T))
+                                       bias_s, rec_s, None if tiles is None else (tiles, ratios, canvases, T), ctrl_s)
             # the step of every scale as the eager sampler takes it (dynamic thresholds: x0 kernel -> ops.abs_quantile, the
             # library's radix select, -> update kernel, all captured), drawing in its order (use_device_rng())
             cfg_kw = {} if cfg is None else dict(cfg_state=cfg_state, cfg_gates=(cfg_run_gate.index_select(0, idx),
@@ -297,7 +309,7 @@ class GraphedSampler:
         ent = dict(graph=graph, x=x_static, ce=ce_s, cs=cs_s, cm=cm_s, idx=idx, rng=rng, n=len(t_host), micros=micros_s,
                    t_host=t_host, s_host=s_host, rows=tab_rule, bias=bias_s, kn_img=kn_img, kn_mask=kn_mask, kn_rng=kn_rng,
                    cfg_run_gate=cfg_run_gate, cfg_w_gate=cfg_w_gate, rec=rec_s, rec_gate=rec_gate, noise=noise_tab,
-                   keep=(tab_t, tab_s, tab_jump, tab_prev, state, cfg_state))
+                   ctrl=ctrl_s, ctrl_gc=ctrl_gc, ctrl_gs=ctrl_gs, keep=(tab_t, tab_s, tab_jump, tab_prev, state, cfg_state))
         self._graphs[key] = ent
         return ent
 
@@ -450,6 +462,10 @@ class GraphedSampler:
         call outside the graph, and a table of gates, one per row, that the call fills from ``attn_maps.interval``: a row
         outside it launches the same kernel, which returns before it loads anything.  After the last replay the accumulators
         are copied into ``attn_maps``.  The graph key holds ("attn_maps", S, ld, the resolved layer names).
+        ``control``: each graph entry owns static copies of M, D and the row tables (``attn_control.BatchCtrl``) and two gate
+        tables, one row per replay, that every call fills from the control's intervals (M and D by ``copy_``).  The graph key
+        holds ("control", S, ld, source, self_max_queries, the resolved layer names): other ``mapper`` / ``keep`` / ``scale`` /
+        interval values replay the same graph.  A control whose rows are all sources adds nothing to the key or the graph.
         ``pag_scale`` / ``pag_layers``: the static conditioning and micros buffers carry the perturbed block's rows and one
         combine kernel per scale precedes the step; the scale and the resolved layer names are part of the graph key.
         ``tiles``: ``image_side`` may be (H, W).  The static conditioning and micros buffers carry every row once per
@@ -514,6 +530,10 @@ class GraphedSampler:
         if maps is not None and (maps.rows != xs[0].shape[0] or maps.S != cond.shape[1]):
             raise ValueError("attn_maps over %d rows of %d tokens for a batch of %d images with %d tokens"
                              % (maps.rows, maps.S, xs[0].shape[0], cond.shape[1]))
+        control = opts.control if (opts.control is not None and opts.control.R > 0) else None
+        if opts.control is not None and (opts.control.rows != xs[0].shape[0] or opts.control.S != cond.shape[1]):
+            raise ValueError("control over %d rows of %d tokens for a batch of %d images with %d tokens"
+                             % (opts.control.rows, opts.control.S, xs[0].shape[0], cond.shape[1]))
         names = opts.layer_names(model.vision_model)
         # the perturbed block repeats the conditional rows of everything per-row; tiles repeat every row once per window
         T = 1
@@ -573,6 +593,11 @@ class GraphedSampler:
             rec_on = np.asarray([maps.on(t, smp.n_steps) for t in ent["t_host"]], dtype="float32")
             ent["rec_gate"].copy_(torch.from_numpy(rec_on))
             ent["rec"].zero()
+        if control is not None:
+            ent["ctrl"].fill(control)
+            g = np.asarray([control.gates(t, smp.n_steps) for t in ent["t_host"]], dtype="float32").reshape(-1, 2)
+            ent["ctrl_gc"].copy_(torch.from_numpy(np.ascontiguousarray(g[:, 0])))
+            ent["ctrl_gs"].copy_(torch.from_numpy(np.ascontiguousarray(g[:, 1])))
         # the rule's rows of this call, counted from its first row: a late start is a trajectory of its own
         ent["rows"][first:].copy_(torch.from_numpy(rule.rows(smp, ent["t_host"][first:], ent["s_host"][first:])))
         if step_noise is not None:

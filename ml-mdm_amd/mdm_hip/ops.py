@@ -2228,6 +2228,157 @@ def attention_biased(qkv, kvc, mask, bias, heads, pag_rows=0):
     return out
 
 
+def _ctrl_tables(what, own, src, gate, device):
+    """the row tables and the gate of the attention-control kernels: int32 [R] twice and one fp32 value, on ``device``"""
+    for name, t in (("own", own), ("src", src)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.device != device or not t.is_contiguous():
+            raise _lib.MdmHipError("%s: %s rows are a contiguous int32 [R] on the tensors' device (got %s %s on %s)"
+                                   % (what, name, t.dtype, tuple(t.shape), t.device))
+    if own.numel() != src.numel() or own.numel() < 1:
+        raise _lib.MdmHipError("%s: %d own rows for %d source rows" % (what, own.numel(), src.numel()))
+    if gate.dtype != torch.float32 or gate.numel() != 1 or gate.device != device:
+        raise _lib.MdmHipError("%s: gate is one fp32 value on the tensors' device (got %s %s on %s)"
+                               % (what, gate.dtype, tuple(gate.shape), gate.device))
+    return own.numel()
+
+
+@torch.no_grad()
+def ctrl_mix_kv(kvc, own, src, M, D, mask, gate):
+    """The text keys / values of prompt-to-prompt's edited rows (include/mdm_hip_ext.h mdm_ctrl_mix_kv) -> (kv_a, kv_b),
+    [R, S, 2C] each of kvc's dtype: kv_a[r] = (k_c[src[r]] | gate * sum_{j live} M[r][:, j] v_c[own[r]][j]), kv_b[r] =
+    (k_c[own[r]] | (gate ? D[r] : 1) * v_c[own[r]]).  ``kvc`` [N, S, 2C]; ``own``, ``src``: int32 [R] batch rows on the device;
+    ``M`` fp32 [R, S, ld] (ld >= S, ld % 4 == 0; columns [S, ld) are never read), ``D`` fp32 [R, S]; ``mask`` [N, S] or
+    None; ``gate``: a device float[1].  CPU tensors: ``attn_control.mix_kv``."""
+    _require_gpu(kvc)
+    kvc = _c(kvc.detach())
+    if kvc.dim() != 3 or kvc.shape[-1] % 2:
+        raise _lib.MdmHipError("ctrl_mix_kv: kvc %s (wanted [N, S, 2C])" % (tuple(kvc.shape),))
+    N, S, C = kvc.shape[0], kvc.shape[1], kvc.shape[2] // 2
+    R = _ctrl_tables("ctrl_mix_kv", own, src, gate, kvc.device)
+    if (M.dim() != 3 or tuple(M.shape[:2]) != (R, S) or M.shape[2] < S or M.shape[2] % 4 or M.dtype != torch.float32
+            or not M.is_contiguous() or M.device != kvc.device):
+        raise _lib.MdmHipError("ctrl_mix_kv: M %s %s for R = %d, S = %d (wanted a contiguous fp32 [R, S, ld], ld >= S, "
+                               "ld %% 4 == 0)" % (tuple(M.shape), M.dtype, R, S))
+    if tuple(D.shape) != (R, S) or D.dtype != torch.float32 or not D.is_contiguous() or D.device != kvc.device:
+        raise _lib.MdmHipError("ctrl_mix_kv: D %s %s for R = %d, S = %d (wanted a contiguous fp32 [R, S])"
+                               % (tuple(D.shape), D.dtype, R, S))
+    m32 = None
+    if mask is not None:
+        if mask.numel() != N * S or mask.shape[0] != N or mask.device != kvc.device:
+            raise _lib.MdmHipError("ctrl_mix_kv: mask %s for N = %d, S = %d" % (tuple(mask.shape), N, S))
+        m32 = _c(mask.detach().float())
+    kv_a = torch.empty((R, S, 2 * C), dtype=kvc.dtype, device=kvc.device)
+    kv_b = torch.empty_like(kv_a)
+    _prof_wrap("ctrl_mix_kv_kernel S=%d" % S, 2.0 * R * S * S * C, lambda: _lib.check(
+        _lib.lib().mdm_ctrl_mix_kv(_p(kvc), _p(own), _p(src), _p(M), M.shape[2], _p(D), _p(m32), _p(gate), _p(kv_a), _p(kv_b),
+                                   N, R, S, C, _dt(kvc), _stream()),
+        "mdm_ctrl_mix_kv",
+    ), kind="attn")
+    return kv_a, kv_b
+
+
+@torch.no_grad()
+def ctrl_gather_qkv(qkv, own, src, gate):
+    """The self-attention operands of prompt-to-prompt's edited rows (include/mdm_hip_ext.h mdm_ctrl_gather_qkv) ->
+    (qkv_self, q_src), [R, L, 3C] each: qkv_self[r] has the q and k columns of row ``gate ? src[r] : own[r]`` and the v
+    columns of row own[r]; q_src[r] has the q columns of row src[r] and NOTHING DEFINED in its k and v columns.  Copies, bit
+    for bit.  CPU tensors: ``attn_control.gather_qkv``."""
+    _require_gpu(qkv)
+    qkv = _c(qkv.detach())
+    if qkv.dim() < 3 or qkv.shape[-1] % 3:
+        raise _lib.MdmHipError("ctrl_gather_qkv: qkv %s (wanted [N, L, 3C])" % (tuple(qkv.shape),))
+    N, C = qkv.shape[0], qkv.shape[-1] // 3
+    L = qkv.numel() // max(N * 3 * C, 1)
+    R = _ctrl_tables("ctrl_gather_qkv", own, src, gate, qkv.device)
+    qkv_self = torch.empty((R, L, 3 * C), dtype=qkv.dtype, device=qkv.device)
+    q_src = torch.empty_like(qkv_self)
+    _prof_wrap("ctrl_gather_qkv_kernel L=%d" % L, float(R * L * 7 * C * qkv.element_size()), lambda: _lib.check(
+        _lib.lib().mdm_ctrl_gather_qkv(_p(qkv), _p(own), _p(src), _p(gate), _p(qkv_self), _p(q_src), N, R, L, C, _dt(qkv),
+                                       _stream()),
+        "mdm_ctrl_gather_qkv",
+    ), kind="hbm")
+    return qkv_self, q_src
+
+
+_CTRL_ZERO = {}   # (device, R, L, ld) -> the static zero bias of the controlled rows' two cross launches
+
+
+def attention_controlled(qkv, kvc, mask, heads, ctrl_rows, pag_rows=0):
+    """``attention`` of a model batch [uncond | sources, edits | perturbed] under prompt-to-prompt control
+    (``mdm_hip.AttnControl``; include/mdm_hip_ext.h): an edited row r computes with the maps of its source row s,
+        out_h[r] = A_h(g_s ? s : r) v_h[r] + P_h(s) V'_h[r] + P_h(r) V''_h[r].
+    ``ctrl_rows``: the handle of one layer -- ``row0`` / ``R`` (the edited rows are [row0, row0 + R); what follows them is the
+    perturbed block: ``pag_rows`` is its size in a layer that perturbs it, 0 in one that runs it as ordinary rows), ``own`` /
+    ``src`` (int32 [R] on the device: absolute batch rows), ``src_host`` (the
+    source rows again, for the checks), ``M`` fp32 [R, S, ld] and ``D`` fp32 [R, S] (unused without text keys), ``gate_c`` /
+    ``gate_s`` (device float[1] each).  Launches: ``mdm_attn_fwd`` with the text keys on the leading ``row0`` rows, exactly as
+    ``attention_pag`` runs them; on the edited rows ``mdm_ctrl_gather_qkv``, ``mdm_attn_fwd`` without text keys on what it
+    gathered, ``mdm_ctrl_mix_kv`` and two ``mdm_attn_cross_bias`` in place with a zero bias -- (q of s, kv_a, the mask of s),
+    then (q of r, kv_b, the mask of r); ``mdm_attn_cross_addv`` on the perturbed rows.  With both gates 0 an edited row has
+    the uncontrolled value up to rounding, not bit for bit: its self and text parts are added in another order.  Inference
+    only: the cross kernels have no backward."""
+    _require_gpu(qkv)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, kvc)):
+        raise _lib.MdmHipError("attention_controlled is inference only (mdm_attn_cross_bias has no backward): run it under "
+                               "torch.no_grad(), or without control")
+    N = qkv.shape[0]
+    rows, row0, R = int(pag_rows), int(ctrl_rows.row0), int(ctrl_rows.R)
+    tail = N - row0 - R   # the block behind the conditional one: perturbed here (pag_rows), or ordinary rows in this layer
+    if R < 1 or row0 < 0 or tail < 0 or rows not in (0, tail):
+        raise _lib.MdmHipError("attention_controlled: edited rows [%d, %d) and %d perturbed rows of a batch of %d (wanted "
+                               "[uncond | sources, edits | perturbed])" % (row0, row0 + R, rows, N))
+    if any(not 0 <= s < row0 for s in ctrl_rows.src_host):
+        raise _lib.MdmHipError("attention_controlled: source rows %r outside the leading %d rows"
+                               % (tuple(ctrl_rows.src_host), row0))
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach() if kvc is not None else None)
+    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    qkv = qkv.reshape(N, L, 3 * C)
+    m32 = _c(mask.float()) if (mask is not None and kvc is not None) else None
+    out = torch.empty((N, L, C), dtype=qkv.dtype, device=qkv.device)
+    dt = _dt_mm(qkv)
+    at = lambda t, r: None if t is None else t.data_ptr() + r * (t.numel() // t.shape[0]) * t.element_size()
+    off = lambda t: at(t, row0)
+
+    def ordinary(first, n):   # mdm_attn_fwd with the text keys on the rows [first, first + n), as ``attention`` runs them
+        oc = torch.empty((n, L, C), dtype=out.dtype, device=out.device) if kvc is not None else None
+        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * n * heads * L * (L + S) * d, lambda: _lib.check(
+            _lib.lib().mdm_attn_fwd(at(qkv, first), at(kvc, first), at(m32, first), at(out, first), _p(oc), None, None, n, L, S,
+                                    heads, d, dt, _stream()),
+            "mdm_attn_fwd",
+        ), kind="attn")
+
+    if row0 > 0:   # the uncond block and the sources
+        ordinary(0, row0)
+    if tail > 0 and rows == 0:   # a perturbed block that this layer does not perturb
+        ordinary(row0 + R, tail)
+    qs, qx = ctrl_gather_qkv(qkv, ctrl_rows.own, ctrl_rows.src, ctrl_rows.gate_s)
+    _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * R * heads * L * L * d, lambda: _lib.check(
+        _lib.lib().mdm_attn_fwd(_p(qs), None, None, off(out), None, None, None, R, L, 0, heads, d, dt, _stream()),
+        "mdm_attn_fwd",
+    ), kind="attn")
+    if kvc is not None:
+        kv_a, kv_b = ctrl_mix_kv(kvc, ctrl_rows.own, ctrl_rows.src, ctrl_rows.M, ctrl_rows.D, m32, ctrl_rows.gate_c)
+        ld = (S + 3) // 4 * 4
+        zkey = (qkv.device, R, L, ld)
+        zero = _CTRL_ZERO.get(zkey)
+        if zero is None:
+            if len(_CTRL_ZERO) > 64:
+                _CTRL_ZERO.clear()
+            zero = _CTRL_ZERO[zkey] = torch.zeros(R, L, ld, dtype=torch.float32, device=qkv.device)
+        m_src = None if m32 is None else m32.reshape(N, S).index_select(0, ctrl_rows.src)
+        cross = lambda q, kv, m: _prof_wrap(
+            "attn_cross_addv_kernel<d=%d, bias> L=%d" % (d, L), 4.0 * R * heads * L * S * d, lambda: _lib.check(
+                _lib.lib().mdm_attn_cross_bias(q, _p(kv), m, _p(zero), ld, off(out), C, off(out), R, L, S, heads, d, dt,
+                                               _stream()),
+                "mdm_attn_cross_bias",
+            ), kind="attn")
+        cross(_p(qx), kv_a, _p(m_src))
+        cross(off(qkv), kv_b, off(m32))
+    if rows > 0:
+        _cross_addv_launch(qkv, kvc, m32, out, N - rows, rows, heads)
+    return out
+
+
 @torch.no_grad()
 def attn_cross_maps(qkv, kvc, mask, heads, acc, bias=None, weight=1.0, gate=None, row0=0, rows=None):
     """acc[r - row0] += weight * gate / heads * sum_h softmax(q_h k_c,h^T / sqrt(d) [+ bias] [masked; bias <= -1e30

@@ -46,6 +46,7 @@ from . import guidance as _guidance
 from . import ops, pag
 from . import regions as _regions
 from . import attn_maps as _attn_maps
+from . import attn_control as _attn_control
 from . import tiling as _tiling
 from .unet import switched
 
@@ -925,14 +926,24 @@ class SampleOptions:
     is the ready-made ``fn``) -- in the steps of its interval, x_t is first moved down the gradient of a loss on the text
     cross-attention maps of the conditional rows (one more forward + backward over B rows per iteration, with only the
     recorder switch on), then the step runs unchanged with every other option on the moved x_t.  Eager samplers only.
+    ``control = ctl`` (a ``mdm_hip.AttnControl`` over the conditional rows and the S tokens of ``lm_outputs``): prompt-to-prompt
+    attention control (Hertz et al. 2022; ``mdm_hip/attn_control.py``) -- the conditional block is [sources | edits], and in
+    the layers ``ctl.cross_layers`` / ``ctl.self_layers`` select an edited row computes with its source row's text
+    cross-attention probabilities (through ``mapper`` / ``keep`` / ``scale``) and, early in the trajectory, its
+    self-attention map (``ops.attention_controlled``).  Those layers take the split path for the edited rows in EVERY step;
+    the two intervals only set the device gates of the step, so outside them an edited row agrees with the uncontrolled
+    sampler to rounding, not bit for bit.  Sources, the unconditional and the perturbed rows take the ordinary launches.
+    Composes with ``cfg``, ``pag_scale``, ``freeu``, ``attn_maps`` (the recorder still reads each row's OWN q and k_c: an
+    edited row's recorded map is its own, not the one it computed with), every solver, ``known_images``, a late start and
+    ``step_noise``.  A control whose rows are all sources launches nothing new.
 
     The model switches (perturbed rows, region bias, FreeU, the map recorder) are held around each step's denoiser call only
     (``switches``), never across a ``yield``, and a switch that is off is not even resolved.  What excludes what
     (``check``: NotImplementedError): ``guide`` with each of the other four, because their kernels have no backward or, for
     ``cfg``, no Jacobian; ``pag_scale`` with ``cfg``; ``guide`` with ``tiles`` (no backward); ``regions`` with ``tiles``
     (the bias is laid out over the whole canvas); and ``attn_maps`` with ``tiles`` (a window's queries are not the
-    canvas's); ``map_guide`` with ``guide`` (two corrections of one step), with ``tiles`` and with an SA solver.  Everything
-    else composes.
+    canvas's); ``map_guide`` with ``guide`` (two corrections of one step), with ``tiles`` and with an SA solver; ``control``
+    with ``guide`` and ``map_guide`` (no backward), with ``regions`` and with ``tiles``.  Everything else composes.
 
     Not a field here: ``step_noise=maps`` (``Sampler.noise_maps`` -> ``sample``) replaces the noise the ancestral update adds,
     so it is a plain keyword of ``sample`` beside ``solver_noise_fn``; every option above composes with it, because the maps
@@ -949,8 +960,17 @@ class SampleOptions:
     tiles: object = None
     attn_maps: object = None
     map_guide: object = None
+    control: object = None
 
     REFUSED = {
+        ("control", "guide"): "control= together with guide=: the controlled rows' cross kernel (mdm_attn_cross_bias) has no "
+                              "backward, so the guide's input gradient cannot pass it",
+        ("control", "map_guide"): "control= together with map_guide=: the map loss is differentiated through each row's own "
+                                  "attention, and an edited row's output depends on its source's maps, which have no backward",
+        ("control", "regions"): "control= together with regions=: both act on the text cross-attention of the conditional "
+                                "rows, and mixing biased probabilities over the token axis is not implemented",
+        ("control", "tiles"): "control= together with tiles=: every image is a block of windows, and pairing the windows of an "
+                              "edit with those of its source is not implemented",
         ("guide", "pag"): "guide= together with pag_scale != 0: the perturbed rows' attention kernel (mdm_attn_cross_addv) "
                           "has no backward, so the guide's input gradient cannot pass it",
         ("guide", "regions"): "guide= together with regions=: the biased cross-attention kernel (mdm_attn_cross_bias) has "
@@ -984,7 +1004,8 @@ class SampleOptions:
         tiles"""
         on = dict(guide=self.guide is not None, pag=self.pag_scale != 0, regions=self.regions is not None,
                   freeu=self.freeu is not None, cfg=self.cfg is not None, tiles=self.tiles is not None,
-                  attn_maps=self.attn_maps is not None, map_guide=self.map_guide is not None)
+                  attn_maps=self.attn_maps is not None, map_guide=self.map_guide is not None,
+                  control=self.control is not None)
 
         def refuse(a, b):
             if on[a] and on[b]:
@@ -1018,6 +1039,12 @@ class SampleOptions:
             raise TypeError("map_guide must be an mdm_hip.MapGuide (got %r)" % (type(self.map_guide).__name__,))
         refuse("map_guide", "guide")
         refuse("map_guide", "tiles")
+        if on["control"] and not isinstance(self.control, _attn_control.AttnControl):
+            raise ValueError("control = %r (wanted a mdm_hip.AttnControl)" % (self.control,))
+        refuse("control", "guide")
+        refuse("control", "map_guide")
+        refuse("control", "regions")
+        refuse("control", "tiles")
         return self
 
     def blocks(self, guidance_scale):
@@ -1029,14 +1056,16 @@ class SampleOptions:
         """the ``CFG`` that acts at this guidance scale: None at 1, where there is nothing to combine"""
         return self.cfg if guidance_scale != 1 else None
 
-    def switches(self, model, guidance_scale, B, device=None, names=None, bias=None, rec=None, step=None):
+    def switches(self, model, guidance_scale, B, device=None, names=None, bias=None, rec=None, step=None, ctrl=None):
         """-> the context manager of one denoiser call over ``B`` images: the model switches that are on -- perturbed rows,
         region bias, FreeU, the map recorder -- as ONE ``unet.switched``.  They touch disjoint attributes, so there is no
         order among them to get right.  A captured graph body passes the names it resolved (``layer_names``), its
         ``StaticBias`` and its ``attn_maps.StaticRows`` (``rec``); the eager samplers pass none of them, and ``step`` =
         (the time the step starts from, ``num_diffusion_steps``), by which ``attn_maps.interval`` decides whether this call
-        records (None: it does)."""
-        if self.pag_scale == 0 and self.regions is None and self.freeu is None and self.attn_maps is None:
+        records (None: it does) and ``control``'s intervals set the gates of this call (None: both on).  ``ctrl``: a graph
+        body's static ``attn_control.BatchCtrl``, whose gates the body has set."""
+        controlled = self.control is not None and self.control.R > 0   # (all rows sources: nothing to control)
+        if self.pag_scale == 0 and self.regions is None and self.freeu is None and self.attn_maps is None and not controlled:
             return _UNCHANGED
         vision_model = getattr(model, "vision_model", model)
         pag_layers, region_layers = (self.pag_layers, self.region_layers) if names is None else names[:2]
@@ -1058,17 +1087,27 @@ class SampleOptions:
                 rec = self.attn_maps.rows_for(*self.blocks(guidance_scale), device)
             if rec is not None:
                 on.append(_attn_maps.applied(vision_model, rec, self.attn_maps.layers if names is None else names[2]))
+        if controlled:
+            if ctrl is None:
+                if self.control.rows != B:
+                    raise ValueError("control over %d rows for a batch of %d images" % (self.control.rows, B))
+                ctrl = self.control.rows_for(*self.blocks(guidance_scale), device)
+                ctrl.set_gates(*((1.0, 1.0) if step is None else self.control.gates(*step)))
+            on.append(_attn_control.applied(vision_model, ctrl, self.control, None if names is None else names[-1]))
         if not on:   # a recorder outside its interval: this call launches what it always did
             return _UNCHANGED
         return switched(s for one in on for s in one.settings)
 
     def layer_names(self, vision_model):
         """-> (perturbed layers, biased layers) as tuples of module names: hashable; () where the option is off; with
-        ``attn_maps``, and only then, a third: the recording layers"""
+        ``attn_maps``, and only then, a third: the recording layers; with a ``control`` that has edited rows, and only then,
+        a last one: its (cross layers, self layers)"""
         names = (pag.layer_names(vision_model, self.pag_layers) if self.pag_scale != 0 else (),
                  _regions.layer_names(vision_model, self.region_layers) if self.regions is not None else ())
         if self.attn_maps is not None:
             names += (_attn_maps.layer_names(vision_model, self.attn_maps.layers),)
+        if self.control is not None and self.control.R > 0:
+            names += (self.control.layer_sets(vision_model),)
         return names
 
     def graph_key(self, vision_model, guidance_scale, names):
@@ -1087,6 +1126,9 @@ class SampleOptions:
             key += (self.tiles.graph_key(),)
         if self.attn_maps is not None:   # (the interval is a table of gates that every call rewrites: no part of the key)
             key += (("attn_maps", self.attn_maps.S, self.attn_maps.ld, names[2]),)
+        if self.control is not None and self.control.R > 0:
+            # (mapper, keep, scale and the intervals are static buffers and gate tables that every call rewrites)
+            key += (("control", self.control.S, self.control.ld, self.control.source, self.control.self_max_queries, names[-1]),)
         return key
 
 
@@ -1791,6 +1833,8 @@ class Sampler(nn.Module):
                "implicit step that mdm_sampler_invert_step solves takes the plain combine p_u + w (p_c - p_u) only",
         "pag": "pag_scale != 0: mdm_sampler_invert_step takes the plain combine p_u + w (p_c - p_u) only, a combine of three "
                "predictions in front of it is not implemented",
+        "control": "control=: inversion finds the trajectory of a GIVEN image under its own prompt -- there is no source row to "
+                   "take attention maps from; control belongs to the replay (sample_from)",
     }
 
     def _inversion_options(self, what, options, refused):
@@ -1799,8 +1843,9 @@ class Sampler(nn.Module):
         on = {name: options.pop(name, None) is not None for name in ("known_images", "known_mask")}
         opts = SampleOptions(**options).check()
         on = dict(guide=opts.guide is not None, map_guide=opts.map_guide is not None, tiles=opts.tiles is not None,
-                  known_images=on["known_images"] or on["known_mask"], cfg=opts.cfg is not None, pag=opts.pag_scale != 0)
-        for name in refused:
+                  known_images=on["known_images"] or on["known_mask"], cfg=opts.cfg is not None, pag=opts.pag_scale != 0,
+                  control=opts.control is not None)
+        for name in tuple(refused) + ("control",):   # (no inversion call takes a control)
             if on[name]:
                 raise NotImplementedError("%s does not take %s" % (what, self.INVERSION_REFUSED[name]))
         return opts

@@ -266,6 +266,10 @@ class SelfAttention(nn.Module):
     # cross-attention maps (mdm_hip.attn_maps.applied / record): a handle whose record(qkv, kvc, cond_mask, heads, bias, N,
     # H, W) accumulates the text term's probabilities after the attention call (ops.attn_cross_maps).  None: as above.
     _attn_rec = None
+    # prompt-to-prompt attention control (mdm_hip.attn_control.applied): a handle whose rows(N, L, kvc) says which batch rows
+    # are edits of which source rows; they compute with the source's attention maps (ops.attention_controlled).  It takes
+    # precedence over _pag_rows and carries it through.  None: as above.
+    _attn_ctrl = None
 
     def forward(self, x, cond=None, cond_mask=None):
         N, H, W, C = x.shape
@@ -298,7 +302,10 @@ class SelfAttention(nn.Module):
                     kvc = kvc.reshape(*cn.shape[:-1], kvc.shape[-1])
                 else:
                     kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
-        if self._cross_bias is not None and kvc is not None:
+        if self._attn_ctrl is not None:
+            a = ops.attention_controlled(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None,
+                                         self.num_heads, self._attn_ctrl.rows(N, H * W, kvc), self._pag_rows)
+        elif self._cross_bias is not None and kvc is not None:
             a = ops.attention_biased(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask, self._cross_bias.bias(N, H, W),
                                      self.num_heads, self._pag_rows)
         elif self._pag_rows:
@@ -402,9 +409,9 @@ class ResNetBlock(nn.Module):
 # --------------------------------------------------------------------------------------
 # The sampling switches: the class attributes above that an instance attribute overrides for the duration of a ``with``
 # block (``pag.perturbed``: _pag_rows; ``regions.applied``: _cross_bias; ``freeu.applied``: _freeu, _freeu_name;
-# ``attn_maps.applied``: _attn_rec).
+# ``attn_maps.applied``: _attn_rec; ``attn_control.applied``: _attn_ctrl).
 # --------------------------------------------------------------------------------------
-SWITCHES = ("_pag_rows", "_cross_bias", "_freeu", "_attn_rec")   # what changes the launches of a forward (_freeu_name only names a block)
+SWITCHES = ("_pag_rows", "_cross_bias", "_freeu", "_attn_rec", "_attn_ctrl")   # what changes the launches of a forward (_freeu_name only names a block)
 
 
 class switched:
