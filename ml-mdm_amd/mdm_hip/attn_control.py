@@ -13,7 +13,9 @@ it over the token axis is linear in v_c: (P M) v_c = P (M v_c)); g_c, g_s: the g
 ``self_interval``; g_s also needs L <= ``self_max_queries``).  A selected layer takes this split path for its edited rows in
 EVERY step -- only the gates change, and they are device values -- so one captured graph serves a trajectory and the eager and
 the graphed sampler issue the same launches.  Outside the intervals an edited row therefore agrees with the uncontrolled
-sampler to rounding, not bit for bit.  Sources, unselected layers and the other two blocks take the ordinary launch.
+sampler to rounding, not bit for bit.  Sources, unselected layers and the other two blocks take the ordinary launch: a
+selected layer calls ``ops.attention(..., ctrl_rows=rows)``, whose block table is ``ops._attn_blocks``
+(``ops.attention_controlled`` is that call on its own).
 
 ``AttnControl``  sources, alignment (``mapper``), ``keep``, ``scale``, intervals and layers; ``AttnControl.aligned`` builds the
                  matrices from token pairs.  The project ships no tokenizer: alignments are token indices.
@@ -226,7 +228,7 @@ class LayerCtrl:
         self.handle, self.cross, self.self_ = handle, bool(cross), bool(self_)
 
     def rows(self, N, L, kvc):
-        """-> the ``ctrl_rows`` of ``ops.attention_controlled`` for this layer at a batch of N rows of L queries"""
+        """-> the ``ctrl_rows`` of ``ops.attention`` for this layer at a batch of N rows of L queries"""
         h = self.handle
         if N != h.total:
             raise ValueError("AttnControl: a batch of %d rows for control over %d rows of a model batch of %d; "
@@ -247,7 +249,7 @@ class _Rows:
 
 class applied(switched):
     """``with applied(vision_model, handle, control=None, names=None):`` -- inside, the ``SelfAttention`` layers that
-    ``control.cross_layers`` (those with text keys) or ``control.self_layers`` select run ``ops.attention_controlled`` with
+    ``control.cross_layers`` (those with text keys) or ``control.self_layers`` select run ``ops.attention(..., ctrl_rows=)`` with
     ``handle`` (a ``BatchCtrl``); on exit (also by an exception) every layer has what it had before.  ``names``: the two
     layer sets already resolved (``AttnControl.layer_sets``)."""
 

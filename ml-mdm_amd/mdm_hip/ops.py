@@ -2053,20 +2053,13 @@ class AttentionFn(torch.autograd.Function):
     def forward(ctx, qkv, kvc, mask, heads, keep):
         _require_gpu(qkv)
         qkv, kvc = _c(qkv), _c(kvc)
-        B = qkv.shape[0]
-        C = qkv.shape[-1] // 3
-        L = qkv.numel() // (B * 3 * C)
-        S = kvc.shape[1] if kvc is not None else 0
-        d = C // heads
+        B, C, L, _, _ = _attn_dims(qkv, kvc, heads)
         m32 = _c(mask.float()) if mask is not None else None
         out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
         lse_s = torch.empty((B, heads, L), dtype=torch.float32, device=qkv.device) if keep else None
         lse_c = torch.empty((B, heads, L), dtype=torch.float32, device=qkv.device) if (keep and kvc is not None) else None
         oc = torch.empty_like(out) if kvc is not None else None   # also the kernel's staging buffer for the cross part
-        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * B * heads * L * (L + S) * d, lambda: _lib.check(
-            _lib.lib().mdm_attn_fwd(_p(qkv), _p(kvc), _p(m32), _p(out), _p(oc), _p(lse_s), _p(lse_c), B, L, S, heads, d, _dt_mm(qkv), _stream()),
-            "mdm_attn_fwd",
-        ), kind="attn")
+        _fwd_launch(qkv, kvc, m32, out, 0, B, heads, oc=oc, lse=(lse_s, lse_c))
         ctx.save_for_backward(qkv, kvc, m32, out, oc, lse_s, lse_c)
         ctx.heads = heads
         return out
@@ -2093,10 +2086,6 @@ class AttentionFn(torch.autograd.Function):
         return dqkv, dkvc, None, None, None
 
 
-def attention(qkv, kvc, mask, heads):
-    return AttentionFn.apply(qkv, kvc, mask, heads, torch.is_grad_enabled())
-
-
 def _attn_dims(qkv, kvc, heads):
     B = qkv.shape[0]
     C = qkv.shape[-1] // 3
@@ -2105,14 +2094,74 @@ def _attn_dims(qkv, kvc, heads):
     return B, C, L, S, C // heads
 
 
+# ---- the launchers: each C entry of the attention layer is called from one place -----------------------------------------
+def _row_ptr(t, row):
+    """the address of batch row ``row`` of a contiguous tensor (None for None)"""
+    return None if t is None else t.data_ptr() + row * (t.numel() // t.shape[0]) * t.element_size()
+
+
+def _fwd_launch(qkv, kvc, m32, out, first, n, heads, oc=None, lse=(None, None)):
+    """mdm_attn_fwd on batch rows [first, first + n) of contiguous tensors, into the same rows of ``out``.  ``kvc=None``
+    leaves the text keys out: S = 0 with null kvc, mask and oc.  ``oc``: the kernel's staging buffer for the cross part,
+    allocated here for the launched rows unless given; ``lse``: the pair a backward needs."""
+    _, _, L, S, d = _attn_dims(qkv, kvc, heads)
+    if oc is None and kvc is not None:
+        oc = torch.empty((n,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
+    _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * n * heads * L * (L + S) * d, lambda: _lib.check(
+        _lib.lib().mdm_attn_fwd(_row_ptr(qkv, first), _row_ptr(kvc, first), _row_ptr(m32, first), _row_ptr(out, first), _p(oc),
+                                _p(lse[0]), _p(lse[1]), n, L, S, heads, d, _dt_mm(qkv), _stream()),
+        "mdm_attn_fwd",
+    ), kind="attn")
+
+
 def _cross_addv_launch(qkv, kvc, m32, out, row0, rows, heads):
     """mdm_attn_cross_addv on batch rows [row0, row0 + rows) of contiguous tensors, into the same rows of ``out``"""
     _, C, L, S, d = _attn_dims(qkv, kvc, heads)
-    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
     _prof_wrap("attn_cross_addv_kernel<d=%d> L=%d" % (d, L), 4.0 * rows * heads * L * S * d, lambda: _lib.check(
-        _lib.lib().mdm_attn_cross_addv(off(qkv), off(kvc), off(m32), off(out), rows, L, S, heads, d, _dt_mm(qkv), _stream()),
+        _lib.lib().mdm_attn_cross_addv(_row_ptr(qkv, row0), _row_ptr(kvc, row0), _row_ptr(m32, row0), _row_ptr(out, row0), rows,
+                                       L, S, heads, d, _dt_mm(qkv), _stream()),
         "mdm_attn_cross_addv",
     ), kind="attn")
+
+
+def _cross_bias_launch(geom, q, kv, m, bias, bias_ld, base, base_ld, out, rows):
+    """mdm_attn_cross_bias on ``rows`` batch rows; ``geom`` = (L, S, heads, d, dtype code), everything else the address of a
+    first row: ``q`` in [.., L, 3C], ``kv`` [.., S, 2C], ``m`` the fp32 mask or None, ``bias`` fp32 [.., L, bias_ld], ``base``
+    the v columns of qkv (``base_ld`` = 3C) or [.., L, C] (C; ``out`` itself: in place), ``out`` [.., L, C]"""
+    L, S, heads, d, dt = geom
+    _prof_wrap("attn_cross_addv_kernel<d=%d, bias> L=%d" % (d, L), 4.0 * rows * heads * L * S * d, lambda: _lib.check(
+        _lib.lib().mdm_attn_cross_bias(q, kv, m, bias, bias_ld, base, base_ld, out, rows, L, S, heads, d, dt, _stream()),
+        "mdm_attn_cross_bias",
+    ), kind="attn")
+
+
+# ---- the operand checks ----------------------------------------------------------------------------------------------------
+def _inference_only(what, kernel, *tensors):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise _lib.MdmHipError("%s is inference only (%s has no backward): run it under torch.no_grad()" % (what, kernel))
+
+
+def _check_f32_3d(what, name, t, rows, L, S, device, contiguous=True):
+    """``t`` is fp32 [rows, L, ld], ld >= S, ld % 4 == 0, on ``device``; ``contiguous=False``: the caller copies it"""
+    if (t.dim() != 3 or tuple(t.shape[:2]) != (rows, L) or t.shape[2] < S or t.shape[2] % 4 or t.dtype != torch.float32
+            or t.device != device or (contiguous and not t.is_contiguous())):
+        raise _lib.MdmHipError("%s: %s %s %s on %s (wanted %sfp32 [%d, %d, ld], ld >= %d, ld %% 4 == 0, on %s)" % (
+            what, name, tuple(t.shape), t.dtype, t.device, "a contiguous " if contiguous else "", rows, L, S, device))
+
+
+def _check_gate(what, gate, device):
+    if gate.dtype != torch.float32 or gate.numel() != 1 or gate.device != device:
+        raise _lib.MdmHipError("%s: gate is one fp32 value on the tensors' device (got %s %s on %s)"
+                               % (what, gate.dtype, tuple(gate.shape), gate.device))
+
+
+def _check_bias(what, qkv, kvc, bias):
+    """the bias of mdm_attn_cross_bias -> as the kernel reads it (fp32, contiguous [N, L, ld])"""
+    if kvc is None:
+        raise _lib.MdmHipError("%s: no text keys (kvc is None) -- there are no logits to bias" % what)
+    N, _, L, S, _ = _attn_dims(qkv, kvc, 1)
+    _check_f32_3d(what, "bias", bias, N, L, S, qkv.device, contiguous=False)
+    return _c(bias.detach())
 
 
 def attn_cross_addv(qkv, kvc, mask, heads):
@@ -2126,106 +2175,25 @@ def attn_cross_addv(qkv, kvc, mask, heads):
     return out
 
 
-def attention_pag(qkv, kvc, mask, heads, rows):
-    """``attention`` on the leading N - rows batch rows, ``attn_cross_addv`` on the trailing ``rows`` (the perturbed block
-    of a perturbed-attention-guidance batch), into one output [N, L, C].  The leading part is the same entry with the same
-    B as ``attention`` on that slice alone.  Inference only: the perturbed kernel has no backward."""
-    _require_gpu(qkv)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, kvc)):
-        raise _lib.MdmHipError("attention_pag is inference only (mdm_attn_cross_addv has no backward): run it under "
-                               "torch.no_grad(), or without perturbed rows")
-    N = qkv.shape[0]
-    rows = int(rows)
-    if not 0 < rows <= N:
-        raise _lib.MdmHipError("attention_pag: rows = %d of a batch of %d" % (rows, N))
-    qkv, kvc = _c(qkv.detach()), _c(kvc.detach() if kvc is not None else None)
-    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
-    m32 = _c(mask.float()) if (mask is not None and kvc is not None) else None
-    out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
-    B = N - rows
-    if B > 0:
-        oc = torch.empty((B,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device) if kvc is not None else None
-        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * B * heads * L * (L + S) * d, lambda: _lib.check(
-            _lib.lib().mdm_attn_fwd(_p(qkv), _p(kvc), _p(m32), _p(out), _p(oc), None, None, B, L, S, heads, d, _dt_mm(qkv), _stream()),
-            "mdm_attn_fwd",
-        ), kind="attn")
-    _cross_addv_launch(qkv, kvc, m32, out, B, rows, heads)
-    return out
-
-
-def _cross_bias_check(what, qkv, kvc, bias):
-    """the operands of mdm_attn_cross_bias -> bias as the kernel reads it (fp32, contiguous [N, L, ld])"""
-    _require_gpu(qkv)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, kvc, bias)):
-        raise _lib.MdmHipError("%s is inference only (mdm_attn_cross_bias has no backward): run it under torch.no_grad()"
-                               % what)
-    if kvc is None:
-        raise _lib.MdmHipError("%s: no text keys (kvc is None) -- there are no logits to bias" % what)
-    N, L, S = qkv.shape[0], qkv.numel() // max(qkv.shape[0] * qkv.shape[-1], 1), kvc.shape[1]
-    if bias.dim() != 3 or bias.shape[0] != N or bias.shape[1] != L or bias.shape[2] < S or bias.shape[2] % 4:
-        raise _lib.MdmHipError("%s: bias %s for N = %d, L = %d, S = %d (wanted [N, L, ld], ld >= S, ld %% 4 == 0)"
-                               % (what, tuple(bias.shape), N, L, S))
-    if bias.dtype != torch.float32 or bias.device != qkv.device:
-        raise _lib.MdmHipError("%s: the bias is fp32 on the tensors' device (got %s on %s)" % (what, bias.dtype, bias.device))
-    return _c(bias.detach())
-
-
-def _cross_bias_launch(qkv, kvc, m32, bias, base, out, row0, rows, heads):
-    """mdm_attn_cross_bias on batch rows [row0, row0 + rows) of contiguous tensors, into the same rows of ``out``.
-    ``base``: None = v of qkv, else a contiguous [N, L, C] tensor (``out`` itself: in place)."""
-    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
-    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
-    bp, bld = (off(qkv) + 2 * C * qkv.element_size(), 3 * C) if base is None else (off(base), C)
-    _prof_wrap("attn_cross_addv_kernel<d=%d, bias> L=%d" % (d, L), 4.0 * rows * heads * L * S * d, lambda: _lib.check(
-        _lib.lib().mdm_attn_cross_bias(off(qkv), off(kvc), off(m32), off(bias), bias.shape[-1], bp, bld, off(out), rows, L, S,
-                                       heads, d, _dt_mm(qkv), _stream()),
-        "mdm_attn_cross_bias",
-    ), kind="attn")
-
-
 def attn_cross_bias(qkv, kvc, mask, bias, heads, base=None):
     """out = base + softmax(q k_c^T / sqrt(d) + bias [masked; bias <= -1e30 excludes]) v_c  (include/mdm_hip_ext.h
     mdm_attn_cross_bias).  ``bias``: fp32 [N, L, ld], ld >= S, ld % 4 == 0.  ``base=None``: v of ``qkv``, into a new tensor;
     a contiguous [N, L, C] tensor of qkv's dtype: the term is added onto it IN PLACE and it is returned.  Forward only."""
-    bias = _cross_bias_check("attn_cross_bias", qkv, kvc, bias)
+    if base is None:   # every row a perturbed one
+        return _attn_blocks("attn_cross_bias", qkv, kvc, mask, heads, qkv.shape[0], bias, None)
+    _require_gpu(qkv)
+    _inference_only("attn_cross_bias", "mdm_attn_cross_bias", qkv, kvc, bias)
+    bias = _check_bias("attn_cross_bias", qkv, kvc, bias)
     qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
     m32 = _c(mask.float()) if mask is not None else None
-    shape = qkv.shape[:-1] + (qkv.shape[-1] // 3,)
-    if base is None:
-        out = torch.empty(shape, dtype=qkv.dtype, device=qkv.device)
-    else:
-        if tuple(base.shape) != tuple(shape) or base.dtype != qkv.dtype or not base.is_contiguous() or base.device != qkv.device:
-            raise _lib.MdmHipError("attn_cross_bias: base %s %s (wanted a contiguous %s %s)"
-                                   % (tuple(base.shape), base.dtype, tuple(shape), qkv.dtype))
-        out = base
-    _cross_bias_launch(qkv, kvc, m32, bias, base, out, 0, qkv.shape[0], heads)
-    return out
-
-
-def attention_biased(qkv, kvc, mask, bias, heads, pag_rows=0):
-    """``attention`` with ``bias`` [N, L, ld] added to the text logits (regional prompts, token weights): on the leading
-    N - pag_rows batch rows ``mdm_attn_fwd`` without text keys writes the self part and ``mdm_attn_cross_bias`` adds the
-    biased cross part in place; the trailing ``pag_rows`` (the perturbed block of perturbed-attention guidance) are the same
-    kernel on base = v.  Inference only: the kernel has no backward."""
-    bias = _cross_bias_check("attention_biased", qkv, kvc, bias)
-    N = qkv.shape[0]
-    rows = int(pag_rows)
-    if not 0 <= rows <= N:
-        raise _lib.MdmHipError("attention_biased: pag_rows = %d of a batch of %d" % (rows, N))
-    qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
-    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
-    m32 = _c(mask.float()) if mask is not None else None
-    out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
-    B = N - rows
-    if B > 0:
-        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * B * heads * L * L * d, lambda: _lib.check(
-            _lib.lib().mdm_attn_fwd(_p(qkv), None, None, _p(out), None, None, None, B, L, 0, heads, d, _dt_mm(qkv), _stream()),
-            "mdm_attn_fwd",
-        ), kind="attn")
-        _cross_bias_launch(qkv, kvc, m32, bias, out, out, 0, B, heads)
-    if rows > 0:
-        _cross_bias_launch(qkv, kvc, m32, bias, None, out, B, rows, heads)
-    return out
+    N, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    shape = qkv.shape[:-1] + (C,)
+    if tuple(base.shape) != tuple(shape) or base.dtype != qkv.dtype or not base.is_contiguous() or base.device != qkv.device:
+        raise _lib.MdmHipError("attn_cross_bias: base %s %s (wanted a contiguous %s %s)"
+                               % (tuple(base.shape), base.dtype, tuple(shape), qkv.dtype))
+    geom = (L, S, heads, d, _dt_mm(qkv))
+    _cross_bias_launch(geom, _p(qkv), _p(kvc), _p(m32), _p(bias), bias.shape[-1], _p(base), C, _p(base), N)
+    return base
 
 
 def _ctrl_tables(what, own, src, gate, device):
@@ -2236,9 +2204,7 @@ def _ctrl_tables(what, own, src, gate, device):
                                    % (what, name, t.dtype, tuple(t.shape), t.device))
     if own.numel() != src.numel() or own.numel() < 1:
         raise _lib.MdmHipError("%s: %d own rows for %d source rows" % (what, own.numel(), src.numel()))
-    if gate.dtype != torch.float32 or gate.numel() != 1 or gate.device != device:
-        raise _lib.MdmHipError("%s: gate is one fp32 value on the tensors' device (got %s %s on %s)"
-                               % (what, gate.dtype, tuple(gate.shape), gate.device))
+    _check_gate(what, gate, device)
     return own.numel()
 
 
@@ -2255,10 +2221,7 @@ def ctrl_mix_kv(kvc, own, src, M, D, mask, gate):
         raise _lib.MdmHipError("ctrl_mix_kv: kvc %s (wanted [N, S, 2C])" % (tuple(kvc.shape),))
     N, S, C = kvc.shape[0], kvc.shape[1], kvc.shape[2] // 2
     R = _ctrl_tables("ctrl_mix_kv", own, src, gate, kvc.device)
-    if (M.dim() != 3 or tuple(M.shape[:2]) != (R, S) or M.shape[2] < S or M.shape[2] % 4 or M.dtype != torch.float32
-            or not M.is_contiguous() or M.device != kvc.device):
-        raise _lib.MdmHipError("ctrl_mix_kv: M %s %s for R = %d, S = %d (wanted a contiguous fp32 [R, S, ld], ld >= S, "
-                               "ld %% 4 == 0)" % (tuple(M.shape), M.dtype, R, S))
+    _check_f32_3d("ctrl_mix_kv", "M", M, R, S, S, kvc.device)
     if tuple(D.shape) != (R, S) or D.dtype != torch.float32 or not D.is_contiguous() or D.device != kvc.device:
         raise _lib.MdmHipError("ctrl_mix_kv: D %s %s for R = %d, S = %d (wanted a contiguous fp32 [R, S])"
                                % (tuple(D.shape), D.dtype, R, S))
@@ -2303,6 +2266,97 @@ def ctrl_gather_qkv(qkv, own, src, gate):
 _CTRL_ZERO = {}   # (device, R, L, ld) -> the static zero bias of the controlled rows' two cross launches
 
 
+def _attn_blocks(what, qkv, kvc, mask, heads, pag_rows, bias, ctrl):
+    """The inference attention of a model batch laid out [ordinary lead | controlled | ordinary-or-perturbed tail]: the checks,
+    once, under the caller's name ``what``, then the launches block by block into one output (the block table: DESIGN
+    section 4.25).  ``ctrl`` (None: no controlled block) places the controlled rows at [row0, row0 + R); the tail is perturbed
+    where ``pag_rows``, its size, is not 0.  Order: the lead, a tail that is not perturbed, the controlled block, a perturbed
+    tail."""
+    _require_gpu(qkv)
+    _inference_only(what, "mdm_attn_cross_addv" if bias is None and ctrl is None else "mdm_attn_cross_bias", qkv, kvc, bias)
+    N, pag_rows = qkv.shape[0], int(pag_rows)
+    row0, R = (N - pag_rows, 0) if ctrl is None else (int(ctrl.row0), int(ctrl.R))
+    tail = row0 + R   # the block behind the controlled one: perturbed here (pag_rows), or ordinary rows in this layer
+    if ctrl is None:
+        if not (1 if bias is None else 0) <= pag_rows <= N:   # without a bias, no perturbed row means no switch is on
+            raise _lib.MdmHipError("%s: %d perturbed rows (pag_rows) of a batch of %d" % (what, pag_rows, N))
+    else:
+        if R < 1 or row0 < 0 or tail > N or pag_rows not in (0, N - tail):
+            raise _lib.MdmHipError("%s: edited rows [%d, %d) and %d perturbed rows of a batch of %d (wanted [uncond | sources, "
+                                   "edits | perturbed])" % (what, row0, tail, pag_rows, N))
+        if any(not 0 <= s < row0 for s in ctrl.src_host):
+            raise _lib.MdmHipError("%s: source rows %r outside the leading %d rows" % (what, tuple(ctrl.src_host), row0))
+        if bias is not None:
+            raise _lib.MdmHipError("%s: a bias together with ctrl_rows -- the controlled rows' cross launches run with a zero "
+                                   "bias; mixing biased probabilities is not implemented" % what)
+    if bias is not None:
+        bias = _check_bias(what, qkv, kvc, bias)
+    qkv, kvc = _c(qkv.detach()), _c(kvc.detach() if kvc is not None else None)
+    m32 = _c(mask.float()) if (mask is not None and kvc is not None) else None
+    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
+    out = torch.empty(qkv.shape[:-1] + (C,), dtype=qkv.dtype, device=qkv.device)
+    geom = (L, S, heads, d, _dt_mm(qkv))
+    kv, m = (kvc, m32) if bias is None else (None, None)   # with a bias mdm_attn_fwd leaves the text keys to the cross launch
+
+    def cross_bias(first, n, on_v):   # the biased text term of the rows [first, first + n): onto v, or in place onto out
+        q, o = _row_ptr(qkv, first), _row_ptr(out, first)
+        base, base_ld = (q + 2 * C * qkv.element_size(), 3 * C) if on_v else (o, C)
+        _cross_bias_launch(geom, q, _row_ptr(kvc, first), _row_ptr(m32, first), _row_ptr(bias, first), bias.shape[-1], base,
+                           base_ld, o, n)
+
+    for first, n in ((0, row0), (tail, 0 if pag_rows else N - tail)):   # the ordinary blocks
+        if n > 0:
+            _fwd_launch(qkv, kv, m, out, first, n, heads)
+            if bias is not None:
+                cross_bias(first, n, False)
+    if R:
+        qs, qx = ctrl_gather_qkv(qkv, ctrl.own, ctrl.src, ctrl.gate_s)
+        _fwd_launch(qs, None, None, out[row0:tail], 0, R, heads)
+        if kvc is not None:
+            kv_a, kv_b = ctrl_mix_kv(kvc, ctrl.own, ctrl.src, ctrl.M, ctrl.D, m32, ctrl.gate_c)
+            ld = (S + 3) // 4 * 4
+            zkey = (qkv.device, R, L, ld)
+            zero = _CTRL_ZERO.get(zkey)
+            if zero is None:
+                if len(_CTRL_ZERO) > 64:
+                    _CTRL_ZERO.clear()
+                zero = _CTRL_ZERO[zkey] = torch.zeros(R, L, ld, dtype=torch.float32, device=qkv.device)
+            m_src = None if m32 is None else m32.reshape(N, S).index_select(0, ctrl.src)
+            o = _row_ptr(out, row0)
+            _cross_bias_launch(geom, _p(qx), _p(kv_a), _p(m_src), _p(zero), ld, o, C, o, R)
+            _cross_bias_launch(geom, _row_ptr(qkv, row0), _p(kv_b), _row_ptr(m32, row0), _p(zero), ld, o, C, o, R)
+    if pag_rows and bias is None:
+        _cross_addv_launch(qkv, kvc, m32, out, tail, pag_rows, heads)
+    elif pag_rows:
+        cross_bias(tail, pag_rows, True)
+    return out
+
+
+def attention(qkv, kvc, mask, heads, pag_rows=0, bias=None, ctrl_rows=None):
+    """The attention of one layer.  No switch: ``AttentionFn``, with its backward.  ``pag_rows``: the trailing rows get the
+    identity self-attention map (``attention_pag``); ``bias``: fp32 [N, L, ld] added to the text logits
+    (``attention_biased``); ``ctrl_rows``: prompt-to-prompt control (``attention_controlled``) -- inference only, one batch
+    layout and one sequence of launches (``_attn_blocks``)."""
+    if not pag_rows and bias is None and ctrl_rows is None:
+        return AttentionFn.apply(qkv, kvc, mask, heads, torch.is_grad_enabled())
+    return _attn_blocks("attention", qkv, kvc, mask, heads, pag_rows, bias, ctrl_rows)
+
+
+def attention_pag(qkv, kvc, mask, heads, rows):
+    """``attention`` on the leading N - rows batch rows, ``attn_cross_addv`` on the trailing ``rows`` (the perturbed block
+    of a perturbed-attention-guidance batch), into one output [N, L, C].  The leading part is the same entry with the same
+    B as ``attention`` on that slice alone.  Inference only: the perturbed kernel has no backward."""
+    return _attn_blocks("attention_pag", qkv, kvc, mask, heads, rows, None, None)
+
+
+def attention_biased(qkv, kvc, mask, bias, heads, pag_rows=0):
+    """``attention`` with ``bias`` [N, L, ld] added to the text logits (regional prompts, token weights): on the leading
+    N - pag_rows batch rows ``mdm_attn_fwd`` without text keys writes the self part and ``mdm_attn_cross_bias`` adds the
+    biased cross part in place; the trailing ``pag_rows`` (the perturbed block of perturbed-attention guidance) are the same
+    kernel on base = v.  Inference only: the kernel has no backward."""
+    return _attn_blocks("attention_biased", qkv, kvc, mask, heads, pag_rows, bias, None)
+
+
 def attention_controlled(qkv, kvc, mask, heads, ctrl_rows, pag_rows=0):
     """``attention`` of a model batch [uncond | sources, edits | perturbed] under prompt-to-prompt control
     (``mdm_hip.AttnControl``; include/mdm_hip_ext.h): an edited row r computes with the maps of its source row s,
@@ -2317,66 +2371,8 @@ def attention_controlled(qkv, kvc, mask, heads, ctrl_rows, pag_rows=0):
     then (q of r, kv_b, the mask of r); ``mdm_attn_cross_addv`` on the perturbed rows.  With both gates 0 an edited row has
     the uncontrolled value up to rounding, not bit for bit: its self and text parts are added in another order.  Inference
     only: the cross kernels have no backward."""
-    _require_gpu(qkv)
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (qkv, kvc)):
-        raise _lib.MdmHipError("attention_controlled is inference only (mdm_attn_cross_bias has no backward): run it under "
-                               "torch.no_grad(), or without control")
-    N = qkv.shape[0]
-    rows, row0, R = int(pag_rows), int(ctrl_rows.row0), int(ctrl_rows.R)
-    tail = N - row0 - R   # the block behind the conditional one: perturbed here (pag_rows), or ordinary rows in this layer
-    if R < 1 or row0 < 0 or tail < 0 or rows not in (0, tail):
-        raise _lib.MdmHipError("attention_controlled: edited rows [%d, %d) and %d perturbed rows of a batch of %d (wanted "
-                               "[uncond | sources, edits | perturbed])" % (row0, row0 + R, rows, N))
-    if any(not 0 <= s < row0 for s in ctrl_rows.src_host):
-        raise _lib.MdmHipError("attention_controlled: source rows %r outside the leading %d rows"
-                               % (tuple(ctrl_rows.src_host), row0))
-    qkv, kvc = _c(qkv.detach()), _c(kvc.detach() if kvc is not None else None)
-    _, C, L, S, d = _attn_dims(qkv, kvc, heads)
-    qkv = qkv.reshape(N, L, 3 * C)
-    m32 = _c(mask.float()) if (mask is not None and kvc is not None) else None
-    out = torch.empty((N, L, C), dtype=qkv.dtype, device=qkv.device)
-    dt = _dt_mm(qkv)
-    at = lambda t, r: None if t is None else t.data_ptr() + r * (t.numel() // t.shape[0]) * t.element_size()
-    off = lambda t: at(t, row0)
-
-    def ordinary(first, n):   # mdm_attn_fwd with the text keys on the rows [first, first + n), as ``attention`` runs them
-        oc = torch.empty((n, L, C), dtype=out.dtype, device=out.device) if kvc is not None else None
-        _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * n * heads * L * (L + S) * d, lambda: _lib.check(
-            _lib.lib().mdm_attn_fwd(at(qkv, first), at(kvc, first), at(m32, first), at(out, first), _p(oc), None, None, n, L, S,
-                                    heads, d, dt, _stream()),
-            "mdm_attn_fwd",
-        ), kind="attn")
-
-    if row0 > 0:   # the uncond block and the sources
-        ordinary(0, row0)
-    if tail > 0 and rows == 0:   # a perturbed block that this layer does not perturb
-        ordinary(row0 + R, tail)
-    qs, qx = ctrl_gather_qkv(qkv, ctrl_rows.own, ctrl_rows.src, ctrl_rows.gate_s)
-    _prof_wrap("attn_fwd_kernel<d=%d> L=%d" % (d, L), 4.0 * R * heads * L * L * d, lambda: _lib.check(
-        _lib.lib().mdm_attn_fwd(_p(qs), None, None, off(out), None, None, None, R, L, 0, heads, d, dt, _stream()),
-        "mdm_attn_fwd",
-    ), kind="attn")
-    if kvc is not None:
-        kv_a, kv_b = ctrl_mix_kv(kvc, ctrl_rows.own, ctrl_rows.src, ctrl_rows.M, ctrl_rows.D, m32, ctrl_rows.gate_c)
-        ld = (S + 3) // 4 * 4
-        zkey = (qkv.device, R, L, ld)
-        zero = _CTRL_ZERO.get(zkey)
-        if zero is None:
-            if len(_CTRL_ZERO) > 64:
-                _CTRL_ZERO.clear()
-            zero = _CTRL_ZERO[zkey] = torch.zeros(R, L, ld, dtype=torch.float32, device=qkv.device)
-        m_src = None if m32 is None else m32.reshape(N, S).index_select(0, ctrl_rows.src)
-        cross = lambda q, kv, m: _prof_wrap(
-            "attn_cross_addv_kernel<d=%d, bias> L=%d" % (d, L), 4.0 * R * heads * L * S * d, lambda: _lib.check(
-                _lib.lib().mdm_attn_cross_bias(q, _p(kv), m, _p(zero), ld, off(out), C, off(out), R, L, S, heads, d, dt,
-                                               _stream()),
-                "mdm_attn_cross_bias",
-            ), kind="attn")
-        cross(_p(qx), kv_a, _p(m_src))
-        cross(off(qkv), kv_b, off(m32))
-    if rows > 0:
-        _cross_addv_launch(qkv, kvc, m32, out, N - rows, rows, heads)
-    return out
+    qkv = qkv.reshape(qkv.shape[0], -1, qkv.shape[-1])   # [N, L, 3C]: the output is [N, L, C] whatever the rank of qkv
+    return _attn_blocks("attention_controlled", qkv, kvc, mask, heads, pag_rows, None, ctrl_rows)
 
 
 @torch.no_grad()
@@ -2397,29 +2393,16 @@ def attn_cross_maps(qkv, kvc, mask, heads, acc, bias=None, weight=1.0, gate=None
     rows = N - row0 if rows is None else int(rows)
     if not (0 <= row0 and 0 < rows and row0 + rows <= N):
         raise _lib.MdmHipError("attn_cross_maps: rows [%d, %d) of a batch of %d" % (row0, row0 + rows, N))
-    if (acc.dim() != 3 or tuple(acc.shape[:2]) != (rows, L) or acc.shape[2] < S or acc.shape[2] % 4
-            or not acc.is_contiguous()):
-        raise _lib.MdmHipError("attn_cross_maps: acc %s for rows = %d, L = %d, S = %d (wanted a contiguous [rows, L, ld], "
-                               "ld >= S, ld %% 4 == 0)" % (tuple(acc.shape), rows, L, S))
-    if acc.dtype != torch.float32 or acc.device != qkv.device:
-        raise _lib.MdmHipError("attn_cross_maps: acc is fp32 on the tensors' device (got %s on %s)" % (acc.dtype, acc.device))
+    _check_f32_3d("attn_cross_maps", "acc", acc, rows, L, S, qkv.device)
     if bias is not None:
-        if bias.dim() != 3 or bias.shape[0] != N or bias.shape[1] != L or bias.shape[2] < S or bias.shape[2] % 4:
-            raise _lib.MdmHipError("attn_cross_maps: bias %s for N = %d, L = %d, S = %d (wanted [N, L, ld], ld >= S, "
-                                   "ld %% 4 == 0)" % (tuple(bias.shape), N, L, S))
-        if bias.dtype != torch.float32 or bias.device != qkv.device:
-            raise _lib.MdmHipError("attn_cross_maps: the bias is fp32 on the tensors' device (got %s on %s)"
-                                   % (bias.dtype, bias.device))
-        bias = _c(bias.detach())
-    if gate is not None and (gate.dtype != torch.float32 or gate.numel() != 1 or gate.device != qkv.device):
-        raise _lib.MdmHipError("attn_cross_maps: gate is one fp32 value on the tensors' device (got %s %s on %s)"
-                               % (gate.dtype, tuple(gate.shape), gate.device))
+        bias = _check_bias("attn_cross_maps", qkv, kvc, bias)
+    if gate is not None:
+        _check_gate("attn_cross_maps", gate, qkv.device)
     m32 = _c(mask.detach().float()) if mask is not None else None
-    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
     _prof_wrap("attn_cross_maps_kernel<d=%d> L=%d" % (d, L), 2.0 * rows * heads * L * S * d, lambda: _lib.check(
-        _lib.lib().mdm_attn_cross_maps(off(qkv), off(kvc), off(m32), off(bias), 0 if bias is None else bias.shape[-1],
-                                       _p(acc), acc.shape[-1], float(weight), _p(gate), rows, L, S, heads, d, _dt_mm(qkv),
-                                       _stream()),
+        _lib.lib().mdm_attn_cross_maps(_row_ptr(qkv, row0), _row_ptr(kvc, row0), _row_ptr(m32, row0), _row_ptr(bias, row0),
+                                       0 if bias is None else bias.shape[-1], _p(acc), acc.shape[-1], float(weight), _p(gate),
+                                       rows, L, S, heads, d, _dt_mm(qkv), _stream()),
         "mdm_attn_cross_maps",
     ), kind="attn")
     return acc
@@ -2457,20 +2440,17 @@ def attn_cross_maps_bwd(qkv, kvc, mask, heads, dacc, dqkv, weight=1.0, row0=0, r
     row0, rows = _cross_probs_check("attn_cross_maps_bwd", qkv, kvc, mask, heads, row0, rows)
     qkv, kvc = _c(qkv.detach()), _c(kvc.detach())
     N, C, L, S, d = _attn_dims(qkv, kvc, heads)
-    if (dacc.dim() != 3 or tuple(dacc.shape[:2]) != (rows, L) or dacc.shape[2] < S or dacc.shape[2] % 4
-            or not dacc.is_contiguous() or dacc.dtype != torch.float32 or dacc.device != qkv.device):
-        raise _lib.MdmHipError("attn_cross_maps_bwd: dacc %s %s for rows = %d, L = %d, S = %d (wanted a contiguous fp32 "
-                               "[rows, L, ld], ld >= S, ld %% 4 == 0)" % (tuple(dacc.shape), dacc.dtype, rows, L, S))
+    _check_f32_3d("attn_cross_maps_bwd", "dacc", dacc, rows, L, S, qkv.device)
     if (dqkv.numel() != qkv.numel() or dqkv.shape[0] != N or dqkv.shape[-1] != 3 * C or dqkv.dtype != qkv.dtype
             or not dqkv.is_contiguous() or dqkv.device != qkv.device):
         raise _lib.MdmHipError("attn_cross_maps_bwd: dqkv %s %s (wanted a contiguous %s %s)"
                                % (tuple(dqkv.shape), dqkv.dtype, tuple(qkv.shape), qkv.dtype))
     m32 = _c(mask.detach().float()) if mask is not None else None
-    off = lambda t: None if t is None else t.data_ptr() + row0 * (t.numel() // t.shape[0]) * t.element_size()
     flops = (4.0 if S <= 64 else 6.0) * rows * heads * L * S * d   # QK^T per sweep (one, or two beyond a key tile) + dS K
     _prof_wrap("attn_cross_maps_bwd_kernel<d=%d> L=%d" % (d, L), flops, lambda: _lib.check(
-        _lib.lib().mdm_attn_cross_maps_bwd(off(qkv), off(kvc), off(m32), _p(dacc.detach()), dacc.shape[-1], float(weight),
-                                           off(dqkv), L * 3 * C, 3 * C, rows, L, S, heads, d, _dt_mm(qkv), _stream()),
+        _lib.lib().mdm_attn_cross_maps_bwd(_row_ptr(qkv, row0), _row_ptr(kvc, row0), _row_ptr(m32, row0), _p(dacc.detach()),
+                                           dacc.shape[-1], float(weight), _row_ptr(dqkv, row0), L * 3 * C, 3 * C, rows, L, S,
+                                           heads, d, _dt_mm(qkv), _stream()),
         "mdm_attn_cross_maps_bwd",
     ), kind="attn")
     return dqkv

@@ -4,8 +4,9 @@ ECCV 2024) -- which layers are perturbed, and the switch that perturbs them.
 PAG evaluates the denoiser once more with the self-attention map of a few ``SelfAttention`` layers replaced by the
 identity (every query attends to itself only: softmax(q k^T) v becomes v; the text-cross term stays) and pushes the
 prediction away from that degraded one:  p = p_u + w (p_c - p_u) + s (p_c - p_hat).  Here the perturbed evaluation is
-a block of extra ROWS of the one model batch -- [uncond | cond | perturbed] -- and a selected layer runs
-``ops.attention_pag``: ``mdm_attn_fwd`` on the leading rows, ``mdm_attn_cross_addv`` on the trailing ``rows``.  The
+a block of extra ROWS of the one model batch -- [uncond | cond | perturbed] -- and a selected layer calls
+``ops.attention(..., pag_rows=rows)``: ``mdm_attn_fwd`` on the leading rows, ``mdm_attn_cross_addv`` on the trailing
+``rows`` (``ops.attention_pag`` is that call on its own; with a bias or control on the layer, ``ops._attn_blocks``).  The
 samplers do the rest (``Sampler.sample(..., pag_scale=s, pag_layers="mid")``, ``GraphedSampler.sample`` alike).
 """
 import re

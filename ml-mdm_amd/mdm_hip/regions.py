@@ -8,8 +8,9 @@ to its logits before the softmax multiplies the token's unnormalised attention w
 
 a weight w scales a token's share by w, a region of 0 / 1 switches it off / leaves it alone per position, and a feathered
 region fades it out smoothly (log 0 = -inf excludes the key exactly as ``lm_mask == 0`` does).  The bias touches the small
-L x S pass only: a selected layer runs ``ops.attention_biased`` -- ``mdm_attn_fwd`` without text keys, then
-``mdm_attn_cross_bias`` in place (include/mdm_hip_ext.h).  Training-free and sampling only: the kernel has no backward.
+L x S pass only: a selected layer with text keys and no attention control calls ``ops.attention(..., bias=b)`` --
+``mdm_attn_fwd`` without text keys, then ``mdm_attn_cross_bias`` in place (include/mdm_hip_ext.h; ``ops.attention_biased``
+is that call on its own).  Training-free and sampling only: the kernel has no backward.
 
 ``RegionPrompts``  the spans of ONE token sequence the caller already has (``lm_outputs`` [rows, S, D], ``lm_mask``) and
                    their regions / weights -> the bias of every attention resolution, cached.

@@ -257,18 +257,19 @@ class SelfAttention(nn.Module):
     _lora = None
     # MXFP8 sampling path of the plain-GEMM projections (mdm_hip.fp8.attach): the same kind of handle.  None: as above.
     _fp8 = None
+    # _pag_rows, _cross_bias and _attn_ctrl switch the one attention call below (ops.attention; its blocks: ops._attn_blocks).
     # perturbed-attention guidance (mdm_hip.pag.perturbed): the trailing _pag_rows batch rows get the identity self-attention
-    # map (ops.attention_pag).  0: as above.
+    # map (pag_rows=).  0: as above.
     _pag_rows = 0
     # regional prompts / token weights (mdm_hip.regions.applied): a handle whose bias(N, H, W) -> fp32 [N, H * W, ld] is added
-    # to the text logits (ops.attention_biased).  None: as above.
+    # to the text logits (bias=) of a layer with text keys and no control.  None: as above.
     _cross_bias = None
     # cross-attention maps (mdm_hip.attn_maps.applied / record): a handle whose record(qkv, kvc, cond_mask, heads, bias, N,
     # H, W) accumulates the text term's probabilities after the attention call (ops.attn_cross_maps).  None: as above.
     _attn_rec = None
     # prompt-to-prompt attention control (mdm_hip.attn_control.applied): a handle whose rows(N, L, kvc) says which batch rows
-    # are edits of which source rows; they compute with the source's attention maps (ops.attention_controlled).  It takes
-    # precedence over _pag_rows and carries it through.  None: as above.
+    # are edits of which source rows; they compute with the source's attention maps (ctrl_rows=).  It takes precedence over
+    # _cross_bias and carries _pag_rows through.  None: as above.
     _attn_ctrl = None
 
     def forward(self, x, cond=None, cond_mask=None):
@@ -302,17 +303,12 @@ class SelfAttention(nn.Module):
                     kvc = kvc.reshape(*cn.shape[:-1], kvc.shape[-1])
                 else:
                     kvc = ops.linear(cn, self.kv_cond.weight, self.kv_cond.bias)
-        if self._attn_ctrl is not None:
-            a = ops.attention_controlled(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None,
-                                         self.num_heads, self._attn_ctrl.rows(N, H * W, kvc), self._pag_rows)
-        elif self._cross_bias is not None and kvc is not None:
-            a = ops.attention_biased(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask, self._cross_bias.bias(N, H, W),
-                                     self.num_heads, self._pag_rows)
-        elif self._pag_rows:
-            a = ops.attention_pag(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads,
-                                  self._pag_rows)
-        else:
-            a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads)
+        ctrl = self._attn_ctrl
+        # the precedence of the switches: the bias acts only on a layer with text keys and no control; _pag_rows rides along
+        biased = self._cross_bias is not None and kvc is not None and ctrl is None
+        a = ops.attention(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask if kvc is not None else None, self.num_heads,
+                          self._pag_rows, self._cross_bias.bias(N, H, W) if biased else None,
+                          ctrl.rows(N, H * W, kvc) if ctrl is not None else None)
         if self._attn_rec is not None and kvc is not None:   # reads q, k_c, the mask and the bias; writes its own buffer
             self._attn_rec.record(qkv.reshape(N, H * W, 3 * C), kvc, cond_mask, self.num_heads,
                                   self._cross_bias.bias(N, H, W) if self._cross_bias is not None else None, N, H, W)
